@@ -10,6 +10,12 @@ scatter and a VIX-style n0).  N > 1: configs[3], the same shapes as 200k windows
 (weak scaling: every rank owns its own 25k windows at every N); a step ends with the RCCL gather of the weights to
 rank 0 (`--config 5`: k=1000, n=500, 125k windows per rank).  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what the headline does not need, after
+the timed region: the parity spot check against the CPU oracle, the CPU baselines, the general-layout legs and the
+PCIe-inclusive legs (each still switched off by its own `--no-*` option).  `--dump-outputs DIR` writes what the last
+timed step computed - weights, status and aux of every window, float64, a fixed sample of windows above 64 MB - to
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
 An RCCL failure is fatal (exit code != 0): there is no other transport in the timed path.  `--rehearse-world N`
 rehearses the N-rank HOST logic on a box with fewer GPUs (ranks share devices, RCCL is skipped by construction and
 the JSON line says so); without it, fewer GPUs than ranks is refused.
@@ -35,6 +41,8 @@ N_SIMD = 1024                  # 256 CUs x 4 SIMDs
 FLOPS_PER_MFMA_F64 = 2048      # v_mfma_f64_16x16x4_f64: 16 x 16 x 4 multiply-adds
 WINDOWS_PER_RANK = {4: 25_000, 5: 125_000}     # configs[3] / configs[4]: 200k resp. 1M windows over 8 GPUs
 HF_PANEL_BUDGET_BYTES = 24e9   # host bytes of the synthetic intraday panels of ALL ranks above which they wrap (hf_period)
+DUMP_BUDGET_BYTES = 63_000_000 # --dump-outputs: all files together below 64 MB, .npy headers included; else a sample
+DUMP_SAMPLE_SEED = 20240099
 # the unmodified reference, one window per call, measured in the survey container (8 cores)
 REFERENCE_AS_SHIPPED = {100: {"windows_per_s": 29.0, "check_off_windows_per_s": 74.0},
                         10: {"windows_per_s": 52.0, "check_off_windows_per_s": 84.0},
@@ -68,6 +76,12 @@ def parse_args():
                     help="BASELINE.json config id (default: 2 = k100/n250/10k windows at N=1, 4 = its 8-GPU form at N>1)")
     ap.add_argument("--windows", type=int, default=0, help="override windows per GPU")
     ap.add_argument("--strategy", default="conjugate", choices=["conjugate", "jeffreys"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the oracle parity spot check, the CPU baselines, the "
+                         "general-layout legs and the PCIe-inclusive legs (off: a plain run does only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's weights / status / aux as DIR/<name>.npy (float64; a fixed "
+                         "seeded sample of windows when all of them would exceed 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the PCIe-inclusive legs (N=1 only, after the timed region)")
     ap.add_argument("--rehearse-gather", action="store_true",
@@ -309,22 +323,27 @@ def worker(args):
     launch = dev.last_launch()
     info = dev.info()
 
-    # parity spot check against the CPU oracle on the first windows of this rank (not timed)
-    from oracle import oracle
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cp, weights, status, aux)
 
-    def oracle_kw(n):
-        o = dict(panel=inp["panel"], start=inp["start"][:n], n_r=n_r)
-        if conj:
-            o.update(hf_panel=inp["hf_panel"], hf_start=inp["hf_start"][:n], m=m, w0=inp["w0"][:n], n0=inp["n0"][:n])
-        return o
+    parity = None
+    if args.full:
+        # parity spot check against the CPU oracle on the first windows of this rank (not timed)
+        from oracle import oracle
 
-    ns = min(W, 64 if k <= 239 else 8)
-    ref, rstat, _ = oracle.posterior_batch_c(args.strategy, k, N, 5.0, **oracle_kw(ns))
-    okw = (status[:ns] == 0) & (rstat == 0)
-    parity = cp.max(float(np.abs(weights[:ns][okw] - ref[okw]).max()) if okw.any() else 0.0)
+        def oracle_kw(n):
+            o = dict(panel=inp["panel"], start=inp["start"][:n], n_r=n_r)
+            if conj:
+                o.update(hf_panel=inp["hf_panel"], hf_start=inp["hf_start"][:n], m=m, w0=inp["w0"][:n], n0=inp["n0"][:n])
+            return o
+
+        ns = min(W, 64 if k <= 239 else 8)
+        ref, rstat, _ = oracle.posterior_batch_c(args.strategy, k, N, 5.0, **oracle_kw(ns))
+        okw = (status[:ns] == 0) & (rstat == 0)
+        parity = cp.max(float(np.abs(weights[:ns][okw] - ref[okw]).max()) if okw.any() else 0.0)
 
     cpu = cpu1 = cpu16 = None
-    if cp.rank == 0 and not args.no_cpu_baseline:
+    if args.full and cp.rank == 0 and not args.no_cpu_baseline:
         # the oracle's C restatement (OpenMP over windows) on a bounded sample of the same workload
         def time_cpu(threads, sample, budget_s):
             oracle.posterior_batch_c(args.strategy, k, N, 5.0, threads=threads, **oracle_kw(min(sample, 2 * threads)))
@@ -353,7 +372,7 @@ def worker(args):
     # take its whole 16-row blocks from Gram sums all windows share; a real backtest (changing universes ref:611-658,
     # resampled windows ref:149-156) arrives in the index layout, which pushes every row through the MFMAs.
     general = None
-    if cp.world == 1 and not args.no_general_layout and args.layout == "contiguous":
+    if args.full and cp.world == 1 and not args.no_general_layout and args.layout == "contiguous":
         general = {}
         for layout in ("no-shared-gram", "index"):
             gb = make_batch(layout)
@@ -384,7 +403,7 @@ def worker(args):
 
     # PCIe-inclusive legs (never `value`): host buffers in, host buffers out
     e2e = None
-    if cp.world == 1 and not args.no_end_to_end and k <= 239:
+    if args.full and cp.world == 1 and not args.no_end_to_end and k <= 239:
         e2e = end_to_end(dev, _native, args.strategy, k, N, n_r, m, W, conj, kw, weights)
 
     # HBM traffic per launch from the committed PMC passes (rocprofv3 cannot run inside this process);
@@ -418,6 +437,7 @@ def worker(args):
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
+            "full": args.full,
             "config": {"workload": (f"BASELINE configs[{config - 1}]" if not args.k else f"shapes of configs[{config - 1}] at another universe size")
                                    + f": k={k} assets, n={N}-day window, "
                                    f"{W} windows per GPU, {args.strategy} prior"
@@ -468,6 +488,31 @@ def worker(args):
     batch.close()
     dev.close()
     cp.close()
+
+
+def dump_outputs(out_dir, cp, weights, status, aux):
+    """--dump-outputs: what a caller of the timed path receives after the last step, every rank's windows in rank order,
+    as float64 .npy files on rank 0.  When all windows exceed DUMP_BUDGET_BYTES, every rank keeps the same fixed seeded
+    sample of its window indices, and `sample_windows.npy` holds their global indices (rank * W + index)."""
+    import numpy as np
+    W, k = weights.shape
+    per_window = 8 * (k + 1 + aux.shape[1])
+    rows = np.arange(W)
+    if cp.world * W * per_window > DUMP_BUDGET_BYTES:
+        n = max(1, DUMP_BUDGET_BYTES // (cp.world * (per_window + 8)))
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(W, n, replace=False))
+    mine = np.hstack([weights[rows], status[rows, None].astype(np.float64), aux[rows]])
+    parts = cp.gather_host(mine, root=0)             # one host gather, outside the timed region
+    if cp.rank != 0:
+        return
+    allw = np.concatenate(parts)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "weights.npy"), allw[:, :k])
+    np.save(os.path.join(out_dir, "status.npy"), allw[:, k])
+    np.save(os.path.join(out_dir, "aux.npy"), allw[:, k + 1:])
+    if len(rows) < W:
+        np.save(os.path.join(out_dir, "sample_windows.npy"),
+                np.concatenate([r * W + rows for r in range(cp.world)]).astype(np.float64))
 
 
 def executed_from_pmc(layout, k, W, strategy, kernel_ms):

@@ -139,12 +139,15 @@ def test_native_tracks_live_objects_and_finalisers_stand_down():
             calls.append(("batch_destroy", b.value))
             return 0
 
+    import weakref
     real = _native.lib
+    saved = (_native._live_devices, _native._live_pinned, _native._default_device, _native._default_group)
     try:
         _native.lib = FakeLib()
+        # registries of this test alone: shutdown() must not reach devices or pinned blocks other tests left alive
+        _native._live_devices, _native._live_pinned = weakref.WeakSet(), weakref.WeakSet()
         d = _native.Device.__new__(_native.Device)
         d._h = _native.c_void_p(1234)
-        import weakref
         d._batches = weakref.WeakSet()
         b = _native.Batch.__new__(_native.Batch)
         b.dev, b._b = d, _native.c_void_p(99)
@@ -163,3 +166,4 @@ def test_native_tracks_live_objects_and_finalisers_stand_down():
     finally:
         _native.lib = real
         _native._closed_for_exit = False
+        _native._live_devices, _native._live_pinned, _native._default_device, _native._default_group = saved

@@ -1,11 +1,14 @@
 #!/bin/bash
 # per-kernel totals of one bench run under rocprofv3.  usage (GPU box): tools/kernel_times_cfg.sh <tag> <bench.py args...>
+# Output: $PROF_OUT/kst_<tag> (PROF_OUT: an absolute path, default prof_out/ in the repository).
 TAG=$1; shift
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${PROF_OUT:-$ROOT/prof_out}/kst_$TAG
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -f csv -d $GRAFT_REPO_ROOT/gpurun_out/kst_$TAG -- python3 $GRAFT_REPO_ROOT/bench.py "$@" --no-cpu-baseline --no-end-to-end > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -f csv -d "$OUT" -- python3 "$ROOT/bench.py" --full "$@" --no-cpu-baseline --no-end-to-end > /dev/null 2>&1
 python3 - <<PY
 import csv,glob
-f=glob.glob("$GRAFT_REPO_ROOT/gpurun_out/kst_$TAG/**/*kernel_stats.csv", recursive=True)[0]
+f=glob.glob("$OUT/**/*kernel_stats.csv", recursive=True)[0]
 rows=list(csv.DictReader(open(f)))
 tot=sum(float(r["TotalDurationNs"]) for r in rows)
 for r in rows:

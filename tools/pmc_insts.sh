@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in "$@"; do
   export TANGENCY_LIB=$ROOT/incorporating_different_sources_amd/$lib
   rm -rf "$OUT/$lib"
-  rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAVE_CYCLES -f csv -d "$OUT/$lib" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/$lib.log" 2>&1 || { echo "pass failed"; tail -5 "$OUT/$lib.log"; }
+  rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAVE_CYCLES -f csv -d "$OUT/$lib" -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/$lib.log" 2>&1 || { echo "pass failed"; tail -5 "$OUT/$lib.log"; }
   python3 - "$OUT/$lib" "$lib" <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(list)

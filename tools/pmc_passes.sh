@@ -1,8 +1,10 @@
 #!/bin/bash
 # Stall / utilisation counters of the fused kernel, one rocprofv3 --pmc pass per counter group (never
-# combined with tracing).  Usage on the GPU box: tools/pmc_passes.sh <outdir under gpurun_out> [kernel substring] [bench.py args]
+# combined with tracing).  Usage on the GPU box: tools/pmc_passes.sh <name> [kernel substring] [bench.py args]
+# Output: $PROF_OUT/<name> (PROF_OUT: an absolute path, default prof_out/ in the repository).
 set -e
-OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out/${1:-pmc_stall}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${PROF_OUT:-$ROOT/prof_out}/${1:-pmc_stall}
 KERNEL=${2:-posterior_wave_kernel}
 BENCH_ARGS=${3:---steps 2 --warmup 1}
 mkdir -p "$OUT"
@@ -15,7 +17,7 @@ for grp in \
   "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS SQ_VALU_MFMA_COEXEC_CYCLES" \
   "SQ_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVES SQ_LEVEL_WAVES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_THREAD_CYCLES_VALU"; do
   i=$((i+1))
-  rocprofv3 --pmc $grp -f csv -d "$OUT/pass$i" -- python3 "${GRAFT_REPO_ROOT:-$PWD}/bench.py" $BENCH_ARGS --no-cpu-baseline --no-end-to-end > "$OUT/pass$i.log" 2>&1 || { echo "pass $i failed"; tail -5 "$OUT/pass$i.log"; }
+  rocprofv3 --pmc $grp -f csv -d "$OUT/pass$i" -- python3 "$ROOT/bench.py" --full $BENCH_ARGS --no-cpu-baseline --no-end-to-end > "$OUT/pass$i.log" 2>&1 || { echo "pass $i failed"; tail -5 "$OUT/pass$i.log"; }
 done
 python3 - "$OUT" "$KERNEL" <<'PY'
 import csv, glob, sys, collections

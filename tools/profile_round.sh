@@ -10,25 +10,25 @@ ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench done"
 if [ -z "$QUICK" ]; then
-python3 bench.py --strategy jeffreys --no-cpu-baseline --no-end-to-end > "$OUT/bench_c2j.json" 2>> "$OUT/bench.err"
-python3 bench.py --config 1 --no-cpu-baseline --no-end-to-end > "$OUT/bench_c1.json" 2>> "$OUT/bench.err"
-python3 bench.py --config 3 --windows 4096 --steps 5 --warmup 1 --no-end-to-end > "$OUT/bench_c3.json" 2>> "$OUT/bench.err"
-python3 bench.py --config 5 --windows 384 --steps 3 --warmup 1 --no-end-to-end > "$OUT/bench_c5.json" 2>> "$OUT/bench.err"
-python3 bench.py --config 5 --windows 4096 --steps 2 --warmup 1 --no-end-to-end --no-cpu-baseline --no-general-layout > "$OUT/bench_c5_4096_windows.json" 2>> "$OUT/bench.err"
+python3 bench.py --full --strategy jeffreys --no-cpu-baseline --no-end-to-end > "$OUT/bench_c2j.json" 2>> "$OUT/bench.err"
+python3 bench.py --full --config 1 --no-cpu-baseline --no-end-to-end > "$OUT/bench_c1.json" 2>> "$OUT/bench.err"
+python3 bench.py --full --config 3 --windows 4096 --steps 5 --warmup 1 --no-end-to-end > "$OUT/bench_c3.json" 2>> "$OUT/bench.err"
+python3 bench.py --full --config 5 --windows 384 --steps 3 --warmup 1 --no-end-to-end > "$OUT/bench_c5.json" 2>> "$OUT/bench.err"
+python3 bench.py --full --config 5 --windows 4096 --steps 2 --warmup 1 --no-end-to-end --no-cpu-baseline --no-general-layout > "$OUT/bench_c5_4096_windows.json" 2>> "$OUT/bench.err"
 echo "c3 / c5 done"
 # configs[2] at its stated 50,000 windows with the intraday panel NOT wrapped (15.6 GB), Jeffreys there for throughput
 # (singular at k=500 > N-2), and configs[3]'s per-GPU shard with the overlapped RCCL gather on a one-rank communicator
-python3 bench.py --config 3 --steps 3 --warmup 1 --no-end-to-end --no-general-layout > "$OUT/bench_c3_50k.json" 2>> "$OUT/bench.err"
+python3 bench.py --full --config 3 --steps 3 --warmup 1 --no-end-to-end --no-general-layout > "$OUT/bench_c3_50k.json" 2>> "$OUT/bench.err"
 echo "c3 50k done"
-python3 bench.py --config 3 --strategy jeffreys --steps 3 --warmup 1 --no-end-to-end --no-cpu-baseline --no-general-layout > "$OUT/bench_c3j_50k.json" 2>> "$OUT/bench.err"
-python3 bench.py --config 4 --rehearse-gather --steps 20 --warmup 3 --no-cpu-baseline --no-end-to-end > "$OUT/bench_c4_shard.json" 2>> "$OUT/bench.err"
+python3 bench.py --full --config 3 --strategy jeffreys --steps 3 --warmup 1 --no-end-to-end --no-cpu-baseline --no-general-layout > "$OUT/bench_c3j_50k.json" 2>> "$OUT/bench.err"
+python3 bench.py --full --config 4 --rehearse-gather --steps 20 --warmup 3 --no-cpu-baseline --no-end-to-end > "$OUT/bench_c4_shard.json" 2>> "$OUT/bench.err"
 fi
 cd /tmp && export TMPDIR=/tmp
 B="$ROOT/bench.py"
-Q="--no-cpu-baseline --no-end-to-end --no-general-layout"
+Q="--full --no-cpu-baseline --no-end-to-end --no-general-layout"
 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/stats" -- python3 $B --steps 20 --warmup 3 $Q > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err"
 for L in no-shared-gram index; do
   rocprofv3 --kernel-trace --stats -f csv -d "$OUT/stats_$L" -- python3 $B --layout $L --steps 20 --warmup 3 $Q > "$OUT/bench_${L}_under_rocprof.json" 2>> "$OUT/rocprof.err"
