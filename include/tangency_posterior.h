@@ -192,6 +192,15 @@ int tp_batch_run(tp_batch_t b);                             /* async on the hand
  * launches anything itself: without a run after tp_batch_keep_rhs it fails with TP_ERR_INVALID. */
 int tp_batch_keep_rhs(tp_batch_t b, int on);
 int tp_batch_download_rhs(tp_batch_t b, double* rhs_out /* [W x k] */);
+/* Keep the k x k matrix each window of [w_begin, w_begin + w_count) factorises - S1 (ref:358) for the conjugate
+ * strategy, J (ref:600-601) for Jeffreys, with a tp_batch_set_shift shift included: the same matrix
+ * TP_MATRIX_POSTERIOR reads back - in every later tp_batch_run.  Written by the kernels of the run itself (no extra
+ * launch on the register-tile path, and the same kernel as without it); w_count = 0 stops it.  Device memory:
+ * w_count * k * k doubles, allocated in this call (TP_ERR_HIP names the byte count when that fails) and freed by
+ * w_count = 0 or tp_batch_destroy.  A range outside [0, W) is TP_ERR_INVALID. */
+int tp_batch_keep_posterior(tp_batch_t b, int64_t w_begin, int64_t w_count);
+/* The matrices the LAST tp_batch_run kept; without a run after tp_batch_keep_posterior: TP_ERR_INVALID. */
+int tp_batch_download_posterior(tp_batch_t b, double* M /* [w_count x k x k], symmetric, full storage */);
 int tp_batch_download(tp_batch_t b, double* weights /* [W x k] */, int32_t* status /* [W] */,
                       double* aux /* optional [W x TP_AUX_STRIDE] */); /* waits for the stream, D2H */
 int tp_batch_download_S1(tp_batch_t b, int64_t w, double* S1 /* [k x k] */); /* posterior scale matrix

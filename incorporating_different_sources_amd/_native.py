@@ -42,7 +42,7 @@ EXPORTS = [
     "tp_batch_shared_gram_blocks",
     "tp_batch_shared_intraday_blocks",
     "tp_host_alloc", "tp_host_free", "tp_batch_set_rhs", "tp_batch_set_shift", "tp_batch_keep_rhs",
-    "tp_batch_download_rhs", "tp_batch_run", "tp_batch_download", "tp_batch_download_S1", "tp_batch_download_matrix",
+    "tp_batch_download_rhs", "tp_batch_keep_posterior", "tp_batch_download_posterior", "tp_batch_run", "tp_batch_download", "tp_batch_download_S1", "tp_batch_download_matrix",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
     "tp_comm_count", "tp_comm_init_all", "tp_group_gather",
@@ -103,6 +103,8 @@ def _load():
     lib.tp_batch_set_rhs.argtypes = [c_void_p, POINTER(c_double)]
     lib.tp_batch_set_shift.argtypes = [c_void_p, POINTER(c_double)]
     lib.tp_batch_download_rhs.argtypes = [c_void_p, POINTER(c_double)]
+    lib.tp_batch_keep_posterior.argtypes = [c_void_p, c_int64, c_int64]
+    lib.tp_batch_download_posterior.argtypes = [c_void_p, POINTER(c_double)]
     lib.tp_batch_run.argtypes = [c_void_p]
     lib.tp_batch_download.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download_S1.argtypes = [c_void_p, c_int64, POINTER(c_double)]
@@ -394,6 +396,7 @@ class Batch:
         dev._check(lib.tp_batch_create(dev._h, ctypes.byref(self.params), self.W, ctypes.byref(self._b)))
         dev._batches.add(self)
         self._keep = None
+        self._post = (0, 0)          # window range of keep_posterior
 
     def close(self):
         if self._b:
@@ -483,6 +486,28 @@ class Batch:
         """Keep the right-hand side every window is solved for in later runs (`download_rhs` reads the last run's)."""
         self.dev._check(lib.tp_batch_keep_rhs(self._b, 1 if on else 0))
         return self
+
+    def keep_posterior(self, begin=0, count=None):
+        """Keep the k x k matrix every window of [begin, begin + count) factorises (S1, or J for Jeffreys, shift included)
+        in later runs; count None: to the end of the batch, 0: stop.  `download_posterior` reads the last run's."""
+        begin = int(begin)
+        count = self.W - begin if count is None else int(count)
+        self.dev._check(lib.tp_batch_keep_posterior(self._b, begin, count))
+        self._post = (begin, count)
+        return self
+
+    def download_posterior(self, out=None) -> np.ndarray:
+        """[count x k x k] matrices kept by the last run (`keep_posterior` before it).  `out`: a C-contiguous float64
+        array of that shape (e.g. `pinned_empty`) to write into."""
+        shape = (self._post[1], self.k, self.k)
+        if out is not None:
+            if out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
+                raise ValueError(f"out: C-contiguous float64 {shape} expected")
+        else:
+            out = np.empty(shape, dtype=np.float64)
+        buf = out if out.size else np.empty(1, dtype=np.float64)     # (the library reports a missing keep / run)
+        self.dev._check(lib.tp_batch_download_posterior(self._b, _ptr(buf, c_double)))
+        return out
 
     def set_rhs(self, rhs):
         """Right-hand side [W x k] in place of the border column (None: default t / c S0 w0 + t)."""
@@ -644,8 +669,9 @@ def default_device() -> Device:
 def posterior_batch(strategy, k, N, gamma, panel, start=None, n_r=None, hf_panel=None, hf_start=None, m=0,
                     w0=None, n0=None, row_idx=None, n_rows=None, col_idx=None, rf_adj=None,
                     hf_row_idx=None, hf_count=None, device: Device | None = None, want_aux=True, rhs=None, flags=0,
-                    shift=None, ret_pairs=None, hf_ret_pairs=None):
-    """Upload + run + download.  Same argument meaning as `oracle.posterior_batch` (tests compare them)."""
+                    shift=None, ret_pairs=None, hf_ret_pairs=None, want_posterior=False):
+    """Upload + run + download.  Same argument meaning as `oracle.posterior_batch` (tests compare them).
+    `want_posterior`: a 4th result, the [W x k x k] matrices the windows factorised (`Batch.keep_posterior`)."""
     dev = device or default_device()
     W = len(start) if start is not None else len(row_idx)
     b = Batch(dev, strategy, k, N, n_r, gamma, W, m or 0, flags)
@@ -657,7 +683,11 @@ def posterior_batch(strategy, k, N, gamma, panel, start=None, n_r=None, hf_panel
         b.upload(panel, start=start, hf_panel=hf_panel, hf_start=hf_start, w0=w0, n0=n0, row_idx=row_idx,
                  n_rows=n_rows, col_idx=col_idx, rf_adj=rf_adj, hf_row_idx=hf_row_idx, hf_count=hf_count,
                  ret_pairs=ret_pairs, hf_ret_pairs=hf_ret_pairs)
+        if want_posterior:
+            b.keep_posterior()
         b.run()
+        if want_posterior:
+            return (*b.download(want_aux=want_aux), b.download_posterior())
         return b.download(want_aux=want_aux)
     finally:
         b.close()

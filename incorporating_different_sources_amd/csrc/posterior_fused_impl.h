@@ -926,6 +926,28 @@ __device__ __forceinline__ void window_body(const tp_kargs_t& A, double* lds, co
         });
     }
     }
+    if (A.out_post != nullptr) {
+        // the kept posterior matrix (tp_batch_keep_posterior): complete here, shift included, before phase F overwrites it;
+        // each wave its own tiles, both halves from the upper triangle (wave_post_tile, posterior_wave_impl.h)
+        double* P = tp_post_window(A, w);
+        if (P != nullptr) {
+            TP_LANE_CONSTANTS();
+            wave_sel<NW, FIX>(wv, [&](auto wc) __attribute__((always_inline)) {
+                for_tiles<C, decltype(wc)::value>([&](auto sc_, auto Ic, auto Jc) __attribute__((always_inline)) {
+                    constexpr int s = decltype(sc_)::value, I = decltype(Ic)::value, J = decltype(Jc)::value;
+                    const int gj = 16 * J + fr;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int gi = 16 * I + fq + 4 * r;
+                        if (gi < k && gj < k && (I < J || gi <= gj)) {
+                            tp_post_store(P + (long long)gi * k + gj, acc[s][r]);
+                            if (I < J || gi < gj) tp_post_store(P + (long long)gj * k + gi, acc[s][r]);
+                        }
+                    }
+                });
+            });
+        }
+    }
     if (dbg == 3) dump_matrix();
 #ifdef TP_STAMP
     if (A.phase_limit == 1) {      // diagnostic build only: time the Gram phases alone (keep the tiles alive)

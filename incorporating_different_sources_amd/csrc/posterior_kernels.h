@@ -74,6 +74,8 @@ struct tp_kargs_t {
     double* dbg_S1;       // optional [k*k + k]: S1 (or J) and the right-hand side of window dbg_w
     long long dbg_w;
     int dbg_mode;         // 1 prior (S0 | c S0 w0), 2 canonical statistics (T | t), 3 posterior (S1 or J | rhs)
+    double* out_post;     // optional [post_count x k x k] (tp_batch_keep_posterior): the k x k matrix window post_w0 + i
+    long long post_w0, post_count;   // factorises (S1 or J, shift included), symmetric, full storage; written by every run
     long long w_first, w_count;
     int panel_ld, hf_ld;
     int panel_off32, hf_off32;   // bit 0: explicit-row windows, bit 1: contiguous windows may use 32-bit byte offsets (u24 x u24)
@@ -109,10 +111,32 @@ hipError_t tp_window_sums_launch(const double* G, double* Q, int nblk, size_t sl
 // tp_kopts_t::wave_kernel >= 0 overrides the automatic pick (A/B measurements)
 int tp_pick_wave_kernel(int nt, int choice);
 // 0 / 1: a plain conjugate / Jeffreys batch (weights, statuses, aux only) - what the one-wave kernel is built for;
-// 2: a batch with a matrix read-back, a custom right-hand side, tp_batch_keep_rhs, a shift or a non-default centring
+// 2: a batch with a matrix read-back, a custom right-hand side, tp_batch_keep_rhs, a shift or a non-default centring.
+// Kept posterior matrices (out_post) do not count: such a batch runs on the kernel it would run on without them (the
+// one- and two-wave kernels have instantiations with the store, tp_post_mode)
 inline int wave_mode(const tp_kargs_t& a) {
     const bool plain = a.dbg_S1 == nullptr && a.rhs == nullptr && a.out_rhs == nullptr && a.shift == nullptr && a.center_rows == 0;
     return plain ? (a.strategy == 0 ? 0 : 1) : 2;
+}
+
+// instantiation of the one- / two-wave kernels for a plain mode m (0 / 1): m + 3 also stores the posterior matrices
+inline int tp_post_mode(const tp_kargs_t& a, int m) { return a.out_post != nullptr ? m + 3 : m; }
+// the kept matrix of window w (tp_batch_keep_posterior), or null when w is outside the kept range
+__host__ __device__ inline double* tp_post_window(const tp_kargs_t& a, long long w) {
+    const long long p = w - a.post_w0;
+    return (a.out_post != nullptr && p >= 0 && p < a.post_count) ? a.out_post + p * (long long)a.k * a.k : nullptr;
+}
+// Stores of the kept matrices: written once, read by nobody on the device - non-temporal, so that they do not evict the
+// panel rows the windows share from L2 / MALL.  TP_POST_NT=0 builds plain stores (A/B measurements).
+#ifndef TP_POST_NT
+#define TP_POST_NT 1
+#endif
+__device__ __forceinline__ void tp_post_store(double* p, double v) {
+#if TP_POST_NT
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
 }
 
 // register-tile fused kernel (posterior_fused.hip): k <= tp_fused_max_assets()

@@ -796,6 +796,40 @@ __global__ void __launch_bounds__(NTHREADS) tiled_clear_kernel(const tp_kargs_t 
     if (threadIdx.x == 0) ws.flags[wl] = 0;
 }
 
+// tp_batch_keep_posterior: the k x k matrix of every kept window of the sub-batch, from the arena to out_post, after
+// tiled_clear_kernel and before the first diagonal step factorises the arena in place.  Every Gram variant leaves the same
+// arena: the super-tiles (I, J), I <= J, rows 64 I .., columns 64 J .. (Jeffreys: J = T - t t'/N and the shift applied).
+// One workgroup per (window, super-tile): the tile through LDS, written row-wise to block (I, J) of the output and, read
+// column-wise from LDS, to block (J, I) - both coalesced.  A diagonal super-tile takes its lower half from its upper half,
+// so the kept matrix is exactly symmetric.  Launched only when matrices are kept.
+__global__ void __launch_bounds__(NTHREADS) tiled_post_kernel(const tp_kargs_t A, const tp_tiled_ws_t ws) {
+    const int NS = ws.NS, KP = ws.KP, k = A.k;
+    long long wl;
+    int tile;
+    if (!xcd_window_tile(NS * (NS + 1) / 2, A.w_count, wl, tile)) return;
+    double* P = tp_post_window(A, A.w_first + wl);
+    if (P == nullptr) return;
+    int I, J;
+    pair_decode(tile, NS, I, J);
+    __shared__ double t[SB][SB + 1];
+    const double* M = ws.arena + wl * (long long)KP * KP + (long long)(SB * I) * KP + SB * J;
+    const int c = threadIdx.x & (SB - 1), r0 = threadIdx.x >> 6;
+    for (int r = r0; r < SB; r += NTHREADS / SB) t[r][c] = M[(long long)r * KP + c];
+    __syncthreads();
+    const int gc = SB * J + c;
+    for (int r = r0; r < SB; r += NTHREADS / SB) {
+        const int gr = SB * I + r;
+        if (gr < k && gc < k) tp_post_store(P + (long long)gr * k + gc, (I < J || r <= c) ? t[r][c] : t[c][r]);
+    }
+    if (I == J) return;
+    // block (J, I): row SB J + r, column SB I + c is element (SB I + c, SB J + r) of the upper triangle
+    const int gc2 = SB * I + c;
+    for (int r = r0; r < SB; r += NTHREADS / SB) {
+        const int gr2 = SB * J + r;
+        if (gr2 < k && gc2 < k) tp_post_store(P + (long long)gr2 * k + gc2, t[c][r]);
+    }
+}
+
 }  // namespace
 
 int tp_tiled_max_assets(void) { return 64 * 32 - 1; }
@@ -1014,6 +1048,8 @@ hipError_t tp_tiled_launch(const tp_kargs_t& a_in, const tp_tiled_ws_t& ws, hipS
     else hipLaunchKernelGGL(tile64_kernel<MODE_GRAM>, xcd_grid(NS * (NS + 1) / 2, G), dim3(NTHREADS), 0, stream, a, ws, 0);
     if (!conj && !(use_wave && a.opts.tiled_wave != 2)) hipLaunchKernelGGL(tiled_rank1_kernel, xcd_grid(NS * (NS + 1) / 2, G), dim3(NTHREADS), 0, stream, a, ws);
     hipLaunchKernelGGL(tiled_clear_kernel, dim3(G), dim3(NTHREADS), 0, stream, a, ws);
+    if (a.out_post != nullptr && a.w_first < a.post_w0 + a.post_count && a.w_first + G > a.post_w0)
+        hipLaunchKernelGGL(tiled_post_kernel, xcd_grid(NS * (NS + 1) / 2, G), dim3(NTHREADS), 0, stream, a, ws);
     // Left-looking blocked Cholesky: block row j first receives the updates of ALL earlier block rows in one
     // pass (every arena tile is read and written once per factorisation, not once per block step), then its
     // diagonal block is factorised and the rest of the row is solved.

@@ -297,7 +297,9 @@ __device__ __forceinline__ void w2_stage_rows(const WRows& src, int tid, int nth
 
 template <int NT, int NWV, int WV, bool LEAN, int MODE>
 __device__ __forceinline__ void w2_body(const tp_kargs_t& A, double* lds) {
-    using C = W2Cfg<NT, NWV, w2_dataflow(NT, LEAN, MODE)>;
+    constexpr bool POST = MODE >= 3;                          // MODE 3 / 4: MODE 0 / 1 + the kept posterior matrices
+    constexpr int PLAIN = POST ? MODE - 3 : MODE;
+    using C = W2Cfg<NT, NWV, w2_dataflow(NT, LEAN, PLAIN)>;
     constexpr int NS = w2_count<NT, NWV>(WV);
     constexpr int kI = NT - 1;
     constexpr int OWN_KI = w2_owner<NT, NWV>(kI);            // the wave that holds the border column (b, then y)
@@ -357,7 +359,7 @@ __device__ __forceinline__ void w2_body(const tp_kargs_t& A, double* lds) {
     }
 
     double n0 = 0.0, cc = 0.0, q0 = 0.0;
-    constexpr bool conj = MODE == 0;
+    constexpr bool conj = PLAIN == 0;
 
     TP_MARK(0);
     if constexpr (conj) {
@@ -615,6 +617,20 @@ __device__ __forceinline__ void w2_body(const tp_kargs_t& A, double* lds) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
+    }
+
+    if constexpr (POST) {
+        // every wave keeps the tile columns it owns, complete after phase E; no barrier (its own registers only)
+        double* P = tp_post_window(A, w);
+        if (P != nullptr) {
+            static_for<0, NT>([&](auto Ic) __attribute__((always_inline)) {
+                constexpr int I = decltype(Ic)::value;
+                static_for<I, NT>([&](auto Jc) __attribute__((always_inline)) {
+                    constexpr int J = decltype(Jc)::value;
+                    if constexpr (w2_owner<NT, NWV>(J) == WV) wave_post_tile<I, J>(P, k, fr, fq, acc[w2_slot<NT, NWV>(I, J)]);
+                });
+            });
+        }
     }
 
     TP_MARK(4);
@@ -972,17 +988,25 @@ __global__ void __launch_bounds__(64 * NWV, TP_WAVE2_OCC) posterior_wave2_kernel
 
 template <int NT, int NWV, bool LEAN, int MODE>
 inline int wave2_lds_bytes(const tp_kargs_t& a) {
-    return W2Cfg<NT, NWV, w2_dataflow(NT, LEAN, MODE)>::LDS_BYTES + (LEAN ? 0 : wave_idx_bytes(a.n_r, a.m, a.strategy == 0));
+    return W2Cfg<NT, NWV, w2_dataflow(NT, LEAN, MODE >= 3 ? MODE - 3 : MODE)>::LDS_BYTES + (LEAN ? 0 : wave_idx_bytes(a.n_r, a.m, a.strategy == 0));
 }
+
+// as wave_post_built (posterior_wave_impl.h): the general-layout conjugate kernel of 12 tiles per side with the store fails the
+// hazard check; its batches keep their matrices on the multi-wave kernel
+constexpr bool wave2_post_built(int nt, bool lean, int mode) { return !(mode == 3 && nt == 12 && !lean); }
 
 template <int NT, int NWV, bool LEAN, int MODE>
 hipError_t wave2_launch_mode(const tp_kargs_t& a, int grid8, hipStream_t stream) {
-    const int lds_bytes = wave2_lds_bytes<NT, NWV, LEAN, MODE>(a);
-    if (lds_bytes > WAVE2_LDS_LIMIT) return hipErrorNotSupported;     // nothing launched: launch_one falls back
-    static std::atomic<unsigned long long> attr_done{0};      // one bit per device (tp_allow_dynamic_lds)
-    { hipError_t e = tp_allow_dynamic_lds(attr_done, posterior_wave2_kernel<NT, NWV, LEAN, MODE>, WAVE2_LDS_LIMIT); if (e != hipSuccess) return e; }
-    hipLaunchKernelGGL((posterior_wave2_kernel<NT, NWV, LEAN, MODE>), dim3(grid8), dim3(64 * NWV), lds_bytes, stream, a);
-    return hipGetLastError();
+    if constexpr (!wave2_post_built(NT, LEAN, MODE)) {
+        return hipErrorNotSupported;
+    } else {
+        const int lds_bytes = wave2_lds_bytes<NT, NWV, LEAN, MODE>(a);
+        if (lds_bytes > WAVE2_LDS_LIMIT) return hipErrorNotSupported;     // nothing launched: launch_one falls back
+        static std::atomic<unsigned long long> attr_done{0};      // one bit per device (tp_allow_dynamic_lds)
+        { hipError_t e = tp_allow_dynamic_lds(attr_done, posterior_wave2_kernel<NT, NWV, LEAN, MODE>, WAVE2_LDS_LIMIT); if (e != hipSuccess) return e; }
+        hipLaunchKernelGGL((posterior_wave2_kernel<NT, NWV, LEAN, MODE>), dim3(grid8), dim3(64 * NWV), lds_bytes, stream, a);
+        return hipGetLastError();
+    }
 }
 
 template <int NT, int NWV, bool LEAN>
@@ -992,9 +1016,12 @@ hipError_t wave2_launch_variant(const tp_kargs_t& a, int grid, hipStream_t strea
         info->lds_bytes = wave_mode(a) == 1 ? wave2_lds_bytes<NT, NWV, LEAN, 1>(a) : wave2_lds_bytes<NT, NWV, LEAN, 0>(a);
     }
     const int grid8 = 8 * ((grid + 7) / 8);
-    switch (wave_mode(a)) {
+    const int mode = wave_mode(a);
+    switch (mode == 2 ? 2 : tp_post_mode(a, mode)) {
         case 0: return wave2_launch_mode<NT, NWV, LEAN, 0>(a, grid8, stream);
         case 1: return wave2_launch_mode<NT, NWV, LEAN, 1>(a, grid8, stream);
+        case 3: return wave2_launch_mode<NT, NWV, LEAN, 3>(a, grid8, stream);
+        case 4: return wave2_launch_mode<NT, NWV, LEAN, 4>(a, grid8, stream);
         default: return hipErrorNotSupported;        // launch_one keeps such batches on the multi-wave kernel
     }
 }

@@ -56,6 +56,23 @@ __host__ __device__ inline int wave_idx_bytes(int n_r, int m, bool conj) { retur
 // row-major index of upper-triangle tile (I, J), I <= J - the numbering of the shared Gram tables
 constexpr int wtile(int NT, int I, int J) { return I * NT - I * (I - 1) / 2 + (J - I); }
 
+// Accumulator tile (I, J), I <= J, of a finished matrix into the kept posterior matrix P (k x k, row-major,
+// tp_batch_keep_posterior; one- and two-wave kernels).  Register r of lane (fr, fq) holds element (16 I + fq + 4 r, 16 J + fr):
+// the tile goes out as 128-byte row pieces (16 lanes), its mirror as 32-byte ones (the 4 lanes of a column fr).  Elements
+// below the diagonal of a diagonal tile are not read: both halves of P come from the upper triangle, so P is exactly symmetric.
+template <int I, int J>
+__device__ __forceinline__ void wave_post_tile(double* P, int k, int fr, int fq, const d4& t) {
+    const int gj = 16 * J + fr;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int gi = 16 * I + fq + 4 * r;
+        if (gi < k && gj < k && (I < J || gi <= gj)) {
+            tp_post_store(P + (long long)gi * k + gj, t[r]);
+            if (I < J || gi < gj) tp_post_store(P + (long long)gj * k + gi, t[r]);
+        }
+    }
+}
+
 // The MFMAs of the Gram loops are inline assembly, which the compiler's hazard recogniser does not see: a
 // v_mfma_f64_16x16x4 result may be read by anything but the SrcC of the next MFMA on the same registers only 19
 // wait states after issue (what hipcc inserts behind the builtin).  Every pass over rows ends here; the asm
@@ -284,6 +301,8 @@ __device__ __forceinline__ void wave_stage_rows(const WRows& src, int lane, int*
     __builtin_amdgcn_wave_barrier();
 }
 
+// MODE 3 / 4: MODE 0 / 1 plus the store of the posterior matrix (tp_batch_keep_posterior) - instantiations of their own, so
+// that the plain modes' code is exactly what it was without the feature.
 // MODE 0: conjugate, 1: Jeffreys - the plain product paths, compiled without the read-back / custom right-hand side /
 // shift branches: every branch that merges two versions of the accumulators costs register copies or spills here (one
 // kernel with all of them decided at run time, MODE 2, needs 2.2 KB of scratch per lane against 44 bytes, and spill code
@@ -293,6 +312,8 @@ __device__ __forceinline__ void wave_stage_rows(const WRows& src, int lane, int*
 template <int NT, bool LEAN, int MODE>
 __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* lds) {
     constexpr bool FULL = MODE == 2;
+    constexpr bool POST = MODE >= 3;
+    constexpr int PLAIN = POST ? MODE - 3 : MODE;
     using C = WCfg<NT, LEAN>;
     const int lane = threadIdx.x;
     const int fr = lane & 15, fq = lane >> 4;
@@ -348,7 +369,7 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
     }
 
     double n0 = 0.0, cc = 0.0, q0 = 0.0;
-    const bool conj = MODE == 0 ? true : MODE == 1 ? false : (A.strategy == 0);
+    const bool conj = PLAIN == 0 ? true : PLAIN == 1 ? false : (A.strategy == 0);
     const int dbg = (FULL && A.dbg_S1 != nullptr && w == A.dbg_w) ? A.dbg_mode : 0;
 
     auto dump_matrix = [&]() __attribute__((always_inline)) {
@@ -665,6 +686,19 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
         });
     }
     if (dbg == 3) dump_matrix();
+    if constexpr (POST) {
+        // the matrix is complete (phase E applied): keep it before phase F factorises it in place
+        double* P = tp_post_window(A, w);
+        if (P != nullptr) {
+            static_for<0, NT>([&](auto Ic) __attribute__((always_inline)) {
+                constexpr int I = decltype(Ic)::value;
+                static_for<I, NT>([&](auto Jc) __attribute__((always_inline)) {
+                    constexpr int J = decltype(Jc)::value;
+                    wave_post_tile<I, J>(P, k, fr, fq, acc[wtile(NT, I, J)]);
+                });
+            });
+        }
+    }
 
     TP_MARK(4);
     // ---- phase F: blocked upper Cholesky S1 = R'R with the border column riding along (y = R^-T b)
@@ -852,23 +886,36 @@ inline int wave_lds_bytes(const tp_kargs_t& a) {
     return WCfg<NT, LEAN>::LDS_BYTES + (LEAN ? 0 : wave_idx_bytes(a.n_r, a.m, a.strategy == 0));
 }
 
+// Instantiations with the posterior store that are not built: in the general-layout conjugate kernel of 8 tiles per side the
+// store's extra live values make the register allocator move an accumulator tile between the register files INSIDE the row
+// loop (a read of an MFMA result too soon after its issue: tools/check_mfma_hazards.py rejects it).  Such a batch keeps its
+// matrices on the multi-wave kernel (hipErrorNotSupported: launch_one falls back).
+constexpr bool wave_post_built(int nt, bool lean, int mode) { return !(mode == 3 && nt == 8 && !lean); }
+
 template <int NT, bool LEAN, int MODE>
 hipError_t wave_launch_mode(const tp_kargs_t& a, int grid8, hipStream_t stream) {
-    const int lds_bytes = wave_lds_bytes<NT, LEAN>(a);
-    if (lds_bytes > WAVE_LDS_LIMIT) return hipErrorNotSupported;     // nothing launched: launch_one falls back to the multi-wave kernel
-    static std::atomic<unsigned long long> attr_done{0};      // one bit per device (tp_allow_dynamic_lds)
-    { hipError_t e = tp_allow_dynamic_lds(attr_done, posterior_wave_kernel<NT, LEAN, MODE>, WAVE_LDS_LIMIT); if (e != hipSuccess) return e; }
-    hipLaunchKernelGGL((posterior_wave_kernel<NT, LEAN, MODE>), dim3(grid8), dim3(64), lds_bytes, stream, a);
-    return hipGetLastError();
+    if constexpr (!wave_post_built(NT, LEAN, MODE)) {
+        return hipErrorNotSupported;
+    } else {
+        const int lds_bytes = wave_lds_bytes<NT, LEAN>(a);
+        if (lds_bytes > WAVE_LDS_LIMIT) return hipErrorNotSupported;     // nothing launched: launch_one falls back to the multi-wave kernel
+        static std::atomic<unsigned long long> attr_done{0};      // one bit per device (tp_allow_dynamic_lds)
+        { hipError_t e = tp_allow_dynamic_lds(attr_done, posterior_wave_kernel<NT, LEAN, MODE>, WAVE_LDS_LIMIT); if (e != hipSuccess) return e; }
+        hipLaunchKernelGGL((posterior_wave_kernel<NT, LEAN, MODE>), dim3(grid8), dim3(64), lds_bytes, stream, a);
+        return hipGetLastError();
+    }
 }
 
 template <int NT, bool LEAN>
 hipError_t wave_launch_variant(const tp_kargs_t& a, int grid, hipStream_t stream, tp_launch_info_t* info) {
     if (info) { info->grid = grid; info->block = 64; info->lds_bytes = wave_lds_bytes<NT, LEAN>(a); info->ntile = NT; }
     const int grid8 = 8 * ((grid + 7) / 8);
-    switch (wave_mode(a)) {
+    const int mode = wave_mode(a);
+    switch (mode == 2 ? 2 : tp_post_mode(a, mode)) {
         case 0: return wave_launch_mode<NT, LEAN, 0>(a, grid8, stream);
         case 1: return wave_launch_mode<NT, LEAN, 1>(a, grid8, stream);
+        case 3: return wave_launch_mode<NT, LEAN, 3>(a, grid8, stream);
+        case 4: return wave_launch_mode<NT, LEAN, 4>(a, grid8, stream);
         default: return hipErrorNotSupported;        // launch_one keeps such batches on the multi-wave kernel
     }
 }

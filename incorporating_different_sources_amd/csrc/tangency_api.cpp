@@ -84,6 +84,8 @@ struct tp_batch_s {
     int panel_ld = 0, hf_ld = 0;
     DevBuf panel, start, row_idx, n_rows, col_idx, rf_adj, hf_panel, hf_start, hf_row_idx, hf_count, w0, n0;
     DevBuf weights, status, aux, dbg, gather_w, gather_s, weights2, status2, stamps, rhs, out_rhs, shift;
+    DevBuf post;                                              // kept posterior matrices [post_count x k x k] (tp_batch_keep_posterior)
+    int64_t post_w0 = 0, post_count = 0;
     DevBuf fe_prices, fe_num, fe_den, fe_hf_prices, fe_hf_num, fe_hf_den;   // price front-end staging (freed after a synchronous upload)
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)
@@ -107,6 +109,7 @@ struct tp_batch_s {
     bool uploaded = false;
     bool gathered = false;
     bool rhs_valid = false;                          // out_rhs was allocated before the last run (tp_batch_keep_rhs)
+    bool post_valid = false;                         // post was allocated before the last run (tp_batch_keep_posterior)
     hipEvent_t ran = nullptr;                        // end of this batch's last launch (recorded by every tp_batch_run)
     hipEvent_t upload_done = nullptr;                // tp_batch_upload_async: end of the copies on the copy stream
     bool upload_pending = false;
@@ -260,6 +263,9 @@ tp_kargs_t make_kargs(tp_batch_t b) {
     a.status = (int*)b->out_status();
     a.aux = (double*)b->aux.p;
     a.out_rhs = (double*)b->out_rhs.p;
+    a.out_post = (double*)b->post.p;
+    a.post_w0 = b->post_w0;
+    a.post_count = b->post.p ? b->post_count : 0;
     a.stamps = (long long*)b->stamps.p;
     a.dbg_S1 = nullptr;
     a.dbg_w = -1;
@@ -592,7 +598,7 @@ int destroy_batch(tp_batch_t b, bool device_calls) {
                          &b->panel, &b->start, &b->row_idx, &b->n_rows, &b->col_idx, &b->rf_adj, &b->hf_panel, &b->hf_start,
                          &b->hf_row_idx, &b->hf_count, &b->w0, &b->n0, &b->weights, &b->status, &b->aux, &b->dbg,
                          &b->gather_w, &b->gather_s, &b->weights2, &b->status2, &b->stamps, &b->rhs, &b->out_rhs, &b->shift,
-                         &b->prefix, &b->hf_prefix};
+                         &b->prefix, &b->hf_prefix, &b->post};
         for (DevBuf* d : all) release(*d);
         for (int l = 0; l < TP_MAX_LANES; ++l)
             for (DevBuf* d : {&b->t_arena[l], &b->t_rinv[l], &b->t_ybar[l], &b->t_zc[l], &b->t_scal[l], &b->t_flags[l], &b->t_part[l]}) release(*d);
@@ -1067,6 +1073,47 @@ int tp_batch_keep_rhs(tp_batch_t b, int on) {
     return ensure(h, b->out_rhs, sizeof(double) * (size_t)b->W * b->p.k);
 }
 
+int tp_batch_keep_posterior(tp_batch_t b, int64_t w_begin, int64_t w_count) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    if (w_begin < 0 || w_count < 0 || w_begin > b->W || w_count > b->W - w_begin)
+        return fail(h, TP_ERR_INVALID, "tp_batch_keep_posterior: windows [%lld, %lld + %lld) outside the batch's %lld",
+                    (long long)w_begin, (long long)w_begin, (long long)w_count, (long long)b->W);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // a running launch may still write the old buffer
+    b->post_valid = false;
+    release(b->post);
+    b->post_w0 = 0;
+    b->post_count = 0;
+    if (w_count == 0) return TP_OK;
+    const size_t bytes = sizeof(double) * (size_t)w_count * (size_t)b->p.k * (size_t)b->p.k;
+    const hipError_t e = hipMalloc(&b->post.p, bytes);
+    if (e != hipSuccess) {
+        b->post.p = nullptr;
+        (void)hipGetLastError();                       // not left behind for the next launch's error check
+        return fail(h, TP_ERR_HIP, "tp_batch_keep_posterior: cannot allocate %zu bytes (%lld windows of %d x %d doubles): %s",
+                    bytes, (long long)w_count, b->p.k, b->p.k, hipGetErrorString(e));
+    }
+    b->post.bytes = bytes;
+    b->post_w0 = w_begin;
+    b->post_count = w_count;
+    return TP_OK;
+}
+
+int tp_batch_download_posterior(tp_batch_t b, double* M) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (!b->post.p || !b->post_valid)
+        return fail(h, TP_ERR_INVALID, "tp_batch_download_posterior: call tp_batch_keep_posterior before the tp_batch_run "
+                                       "whose matrices are wanted");
+    if (!M) return fail(h, TP_ERR_INVALID, "tp_batch_download_posterior: M is NULL");
+    HIP_TRY(h, hipMemcpyAsync(M, b->post.p, b->post.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return harvest_kernel_time(h);
+}
+
 int tp_batch_run(tp_batch_t b) {
     if (!b) return TP_ERR_INVALID;
     tp_handle_t h = b->h;
@@ -1077,6 +1124,7 @@ int tp_batch_run(tp_batch_t b) {
         b->upload_pending = false;
     }
     if (b->out_rhs.p) b->rhs_valid = true;
+    if (b->post.p) b->post_valid = true;
     if (b->pingpong) {
         b->parity ^= 1;
         if (b->gather_pending[b->parity]) {
@@ -1170,6 +1218,8 @@ int tp_batch_download_matrix(tp_batch_t b, int64_t w, int what, double* M, doubl
     HIP_TRY(h, hipMemsetAsync(b->dbg.p, 0, sizeof(double) * (kk + b->p.k), h->stream));
     tp_kargs_t a = make_kargs(b);
     a.dbg_S1 = (double*)b->dbg.p;
+    a.out_post = nullptr;                              // the kept matrices are those of the last tp_batch_run
+    a.post_count = 0;
     a.dbg_w = w;
     a.dbg_mode = what;
     a.w_first = w;

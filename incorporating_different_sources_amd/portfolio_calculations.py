@@ -981,6 +981,27 @@ def calculate_portfolio_weights_batch(trading_dates, portfolio_spec, market_data
     return [pd.DataFrame({"Weight": weights[i]}, index=pd.Index(labels[i], name="Stock")) for i in range(len(labels))]
 
 
+def calculate_posterior_scale_matrices_batch(trading_dates, portfolio_spec, market_data):
+    """The posterior scale matrix of MANY rebalancing dates with one device batch: S1 = S0 + T (ref:358) for the conjugate
+    specs, J = T - t t'/N (ref:600-601) for `jeffreys` - the matrices the weights of `calculate_portfolio_weights_batch`
+    factorise, stored by the same kernels (`Batch.keep_posterior`).  One k x k DataFrame per date; index and columns are
+    that date's tickers in the order of its weights.  Replaces a per-date loop of `calculate_conjugate_posterior_S`.
+    One device even with sharding opted in."""
+    strategy = portfolio_spec["weighting_strategy"]
+    if strategy not in _CONJUGATE and strategy != "jeffreys":
+        raise ValueError(f"calculate_posterior_scale_matrices_batch: no posterior scale matrix for strategy {strategy!r} "
+                         "(conjugate strategies and 'jeffreys' have one)")
+    trading_dates = list(trading_dates)
+    if not trading_dates:
+        return []
+    k, N = portfolio_spec["size"], portfolio_spec["rolling_window"]
+    gamma = portfolio_spec.get("risk_aversion") or 1.0           # the matrices do not depend on it
+    kw, labels = batch.pack_windows(trading_dates, portfolio_spec, market_data, members_of=_members_provider(market_data))
+    _, _, _, M = _native.posterior_batch("conjugate" if strategy in _CONJUGATE else "jeffreys", k, N, gamma, **kw,
+                                         want_aux=False, want_posterior=True)
+    return [pd.DataFrame(M[i], index=pd.Index(labels[i]), columns=pd.Index(labels[i])) for i in range(len(labels))]
+
+
 def _members_provider(market_data):
     """Index membership per date for the batch packer: None = every column (synthetic panels)."""
     provider = market_data.get("index_constituents") if isinstance(market_data, dict) else None
