@@ -118,6 +118,8 @@ typedef struct tp_inputs {
 const char* tp_version(void);
 /* largest portfolio_spec["size"] the built kernels cover */
 int tp_max_assets(void);
+/* largest k the solve-sweep kernel covers (tp_batch_solve_sweep); at least 143, at most tp_max_assets() */
+int tp_sweep_max_assets(void);
 /* number of visible HIP devices (0 when there is none: tp_create will then fail) */
 int tp_device_count(void);
 
@@ -143,6 +145,8 @@ int tp_destroy(tp_handle_t h);
  *   "hf_share_min_blocks"  large-k path, conjugate: intraday windows that advance by a fixed stride share the Grams of
  *                      their whole stride-long blocks from this many whole blocks per window on (default 6; takes effect
  *                      at the next upload; "no_shared_gram" switches the scheme off)
+ *   "sweep_chunk_windows"  windows per sub-range of tp_batch_solve_sweep (0 automatic: as many as 256 MiB of k x k matrices
+ *                      hold); results do not depend on it
  * Replaces nothing in the reference. */
 int tp_set_option(tp_handle_t h, const char* name, int value);
 const char* tp_last_error(tp_handle_t h); /* h may be NULL: last error of a failed tp_create */
@@ -201,6 +205,44 @@ int tp_batch_download_rhs(tp_batch_t b, double* rhs_out /* [W x k] */);
 int tp_batch_keep_posterior(tp_batch_t b, int64_t w_begin, int64_t w_count);
 /* The matrices the LAST tp_batch_run kept; without a run after tp_batch_keep_posterior: TP_ERR_INVALID. */
 int tp_batch_download_posterior(tp_batch_t b, double* M /* [w_count x k x k], symmetric, full storage */);
+/* Solve sweep: many shifts and right-hand sides per window from ONE Gram pass.  With S = max(n_shift, 1) and
+ * R = (default_rhs ? 1 : 0) + n_rhs, for every window w, shift s and right-hand side r
+ *     x[w][s][r] = (M_w + d_ws I + e_ws 1 1')^-1 rhs_wr / gamma          (the / gamma is tp_batch_set_rhs's convention)
+ * M_w is the matrix a plain tp_batch_run of this batch factorises: S1 (conjugate) or J (Jeffreys, with
+ * TP_FLAG_CENTER_BY_ROWS / TP_FLAG_NO_CENTER honoured); a tp_batch_set_shift shift of the batch is NOT included, and
+ * its tp_batch_set_rhs is not used.  With default_rhs != 0 slot r = 0 is the window's own right-hand side (t, or
+ * c S0 w0 + t) and the caller's n_rhs columns follow.  shift == NULL (n_shift 0 or 1) is one unshifted solve; a shift
+ * needs the Jeffreys strategy and finite d, e >= 0.  TP_ERR_INVALID: a shift on a conjugate batch, a negative or
+ * non-finite d or e, R outside [1, TP_SWEEP_MAX_RHS], n_shift < 0, n_shift > 1 without shift, n_rhs > 0 without rhs, a
+ * batch that was not uploaded.  TP_ERR_UNSUPPORTED: k > tp_sweep_max_assets().  TP_ERR_HIP: an allocation failed (the
+ * message names the byte count).
+ * How it runs: the windows go through in sub-ranges ("sweep_chunk_windows"; default: as many as 256 MiB of matrices
+ * hold).  Per sub-range the batch's own run kernel stores M_w and the default right-hand side (the machinery of
+ * tp_batch_keep_posterior / tp_batch_keep_rhs; never with the shared block sums, so M_w depends on the window's rows
+ * alone), then one workgroup per (window, shift) factorises once and solves all R columns.  A (window, shift) result does
+ * not depend on W, S, the window's position or the sub-ranges.  Device memory: W x S x R x k doubles of solutions, four
+ * [W x k]-sized arrays and the sub-range's matrices; kept until tp_batch_destroy.
+ * The call copies shift and rhs to the device (no host pointer is kept) and queues the kernels on the handle's stream
+ * without waiting for THEM.  Unlike tp_batch_run it does wait, on entry, for whatever was queued on the handle's stream
+ * before it (an earlier run or sweep) and for its own two copies.  kernel_ms of tp_last_timing covers Gram passes and
+ * solves; between tp_region_begin and tp_region_end a sweep counts as one step of tp_region_steps.  A gather requested
+ * by tp_batch_gather_async is put on its stream at the end of the call, as at the end of a tp_batch_run; it carries the
+ * results of the run it was requested for.  A later tp_batch_upload_async of the batch waits for the sweep's kernels.  It leaves the batch alone: its
+ * set_rhs / set_shift / keep_rhs / keep_posterior settings stay, and tp_batch_download / tp_batch_download_rhs /
+ * tp_batch_download_posterior return what they returned before.
+ * Binds (T + eta_b/2 I)^-1 [t, 1] over the posterior draws of calculate_greyserman_portfolio (ref:924) and the
+ * V^-1 [mu, 1] pair of calculate_jorion_portfolio (ref:880-891). */
+#define TP_SWEEP_MAX_RHS 16
+int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift /* [W x n_shift x 2] or NULL */,
+                         int32_t n_rhs, const double* rhs /* [W x n_rhs x k] or NULL */, int32_t default_rhs);
+/* Waits for the sweep and copies out x [W x S x R x k] and status [W x S] (TP_STATUS_OK, TP_STATUS_NOT_PD: a pivot <= 0,
+ * TP_STATUS_NONFINITE: NaN / Inf in any of the R solutions); either may be NULL.  Without a sweep before it:
+ * TP_ERR_INVALID. */
+int tp_batch_download_sweep(tp_batch_t b, double* x, int32_t* status);
+/* The default right-hand sides [W x k] (t, or c S0 w0 + t) the Gram pass of the last sweep formed, whether or not the
+ * sweep solved for them (tp_batch_download_rhs keeps answering for the last tp_batch_run).  Waits like
+ * tp_batch_download_sweep; without a sweep before it: TP_ERR_INVALID. */
+int tp_batch_download_sweep_rhs(tp_batch_t b, double* rhs_out);
 int tp_batch_download(tp_batch_t b, double* weights /* [W x k] */, int32_t* status /* [W] */,
                       double* aux /* optional [W x TP_AUX_STRIDE] */); /* waits for the stream, D2H */
 int tp_batch_download_S1(tp_batch_t b, int64_t w, double* S1 /* [k x k] */); /* posterior scale matrix

@@ -33,16 +33,18 @@ FLAG_CENTER_BY_ROWS = 1
 FLAG_NO_CENTER = 2
 FLAG_NO_SHARED_GRAM = 4
 UNIQUE_ID_BYTES = 128
+SWEEP_MAX_RHS = 16
 
 # every symbol include/tangency_posterior.h declares (checked by tests/test_cabi_symbols.py)
 EXPORTS = [
-    "tp_version", "tp_max_assets", "tp_device_count", "tp_create", "tp_destroy", "tp_set_option", "tp_last_error",
+    "tp_version", "tp_max_assets", "tp_sweep_max_assets", "tp_device_count", "tp_create", "tp_destroy", "tp_set_option", "tp_last_error",
     "tp_device_info",
     "tp_log_returns", "tp_batch_create", "tp_batch_upload", "tp_batch_upload_async", "tp_batch_upload_wait",
     "tp_batch_shared_gram_blocks",
     "tp_batch_shared_intraday_blocks",
     "tp_host_alloc", "tp_host_free", "tp_batch_set_rhs", "tp_batch_set_shift", "tp_batch_keep_rhs",
     "tp_batch_download_rhs", "tp_batch_keep_posterior", "tp_batch_download_posterior", "tp_batch_run", "tp_batch_download", "tp_batch_download_S1", "tp_batch_download_matrix",
+    "tp_batch_solve_sweep", "tp_batch_download_sweep", "tp_batch_download_sweep_rhs",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
     "tp_comm_count", "tp_comm_init_all", "tp_group_gather",
@@ -82,6 +84,7 @@ def _load():
     lib.tp_last_error.restype = c_char_p
     lib.tp_last_error.argtypes = [c_void_p]
     lib.tp_max_assets.restype = c_int
+    lib.tp_sweep_max_assets.restype = c_int
     lib.tp_create.argtypes = [c_int, POINTER(c_void_p)]
     lib.tp_destroy.argtypes = [c_void_p]
     lib.tp_set_option.argtypes = [c_void_p, c_char_p, c_int]
@@ -106,6 +109,9 @@ def _load():
     lib.tp_batch_keep_posterior.argtypes = [c_void_p, c_int64, c_int64]
     lib.tp_batch_download_posterior.argtypes = [c_void_p, POINTER(c_double)]
     lib.tp_batch_run.argtypes = [c_void_p]
+    lib.tp_batch_solve_sweep.argtypes = [c_void_p, c_int32, POINTER(c_double), c_int32, POINTER(c_double), c_int32]
+    lib.tp_batch_download_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32)]
+    lib.tp_batch_download_sweep_rhs.argtypes = [c_void_p, POINTER(c_double)]
     lib.tp_batch_download.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download_S1.argtypes = [c_void_p, c_int64, POINTER(c_double)]
     lib.tp_batch_download_matrix.argtypes = [c_void_p, c_int64, c_int, POINTER(c_double), POINTER(c_double)]
@@ -141,6 +147,11 @@ def version() -> str:
 
 def max_assets() -> int:
     return int(lib.tp_max_assets())
+
+
+def sweep_max_assets() -> int:
+    """Largest k `Batch.solve_sweep` covers (`tp_sweep_max_assets`)."""
+    return int(lib.tp_sweep_max_assets())
 
 
 def device_count() -> int:
@@ -272,8 +283,9 @@ class Device:
 
     def set_option(self, name: str, value: int):
         """`tp_set_option`: kernel-selection switches of this handle ("wave_kernel", "tiled_wave", "tiled_fuse",
-        "no_shared_gram", "tiled_arena_gib", "tiled_arena_mib"); the TP_* environment variables are read once, when the
-        Device is created."""
+        "no_shared_gram", "tiled_arena_gib", "tiled_arena_mib", "tiled_lanes", "hf_share_min_blocks",
+        "sweep_chunk_windows": windows per sub-range of `Batch.solve_sweep`, 0 = automatic); the TP_* environment
+        variables are read once, when the Device is created."""
         self._check(lib.tp_set_option(self._h, name.encode(), int(value)))
         return self
 
@@ -531,6 +543,54 @@ class Batch:
     def run(self):
         self.dev._check(lib.tp_batch_run(self._b))
         return self
+
+    def solve_sweep(self, shift=None, rhs=None, default_rhs=True, out=None):
+        """`tp_batch_solve_sweep` + `tp_batch_download_sweep`: x[w, s, r] = (M_w + d_ws I + e_ws 1 1')^-1 rhs_wr / gamma
+        from ONE Gram pass, for `shift` [W x S x 2] = (d, e) (Jeffreys only; None: one unshifted solve) and the
+        right-hand sides `rhs` [W x n x k] (a [W x k] array is one column), behind the window's own right-hand side when
+        `default_rhs`.  Returns (x [W, S, R, k], status [W, S]).  `out=(x, status)`: write into these arrays (e.g.
+        `pinned_empty`).  The batch's results, settings and kept arrays are left alone."""
+        W, k = self.W, self.k
+        sh = None
+        S = 1
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, dtype=np.float64)
+            if sh.ndim != 3 or sh.shape[0] != W or sh.shape[1] < 1 or sh.shape[2] != 2:
+                raise ValueError(f"shift: expected shape ({W}, S, 2) with S >= 1, got {tuple(sh.shape)}")
+            S = sh.shape[1]
+        r = None
+        n_rhs = 0
+        if rhs is not None:
+            r = np.ascontiguousarray(rhs, dtype=np.float64)
+            if r.ndim == 2:
+                r = r[:, None, :]
+            if r.ndim != 3 or r.shape[0] != W or r.shape[2] != k:
+                raise ValueError(f"rhs: expected shape ({W}, n, {k}), got {tuple(r.shape)}")
+            r = np.ascontiguousarray(r)
+            n_rhs = r.shape[1]
+        R = (1 if default_rhs else 0) + n_rhs
+        if R < 1 or R > SWEEP_MAX_RHS:
+            raise ValueError(f"{R} right-hand sides per window: between 1 and {SWEEP_MAX_RHS} expected")
+        if out is not None:
+            x, status = out
+            if x.shape != (W, S, R, k) or x.dtype != np.float64 or not x.flags.c_contiguous:
+                raise ValueError(f"out[0]: C-contiguous float64 {(W, S, R, k)} expected")
+            if status.shape != (W, S) or status.dtype != np.int32 or not status.flags.c_contiguous:
+                raise ValueError(f"out[1]: C-contiguous int32 {(W, S)} expected")
+        else:
+            x = np.empty((W, S, R, k), dtype=np.float64)
+            status = np.empty((W, S), dtype=np.int32)
+        self.dev._check(lib.tp_batch_solve_sweep(self._b, S if sh is not None else 0, _ptr(sh, c_double), n_rhs,
+                                                 _ptr(r if n_rhs else None, c_double), 1 if default_rhs else 0))
+        self.dev._check(lib.tp_batch_download_sweep(self._b, _ptr(x if x.size else None, c_double),
+                                                    _ptr(status if status.size else None, c_int32)))
+        return x, status
+
+    def download_sweep_rhs(self) -> np.ndarray:
+        """[W x k] default right-hand sides (t = X'1, or c S0 w0 + t) the Gram pass of the last `solve_sweep` formed."""
+        out = np.empty((self.W, self.k), dtype=np.float64)
+        self.dev._check(lib.tp_batch_download_sweep_rhs(self._b, _ptr(out if out.size else None, c_double)))
+        return out
 
     def download(self, want_aux=True, out=None):
         """(weights, status, aux).  `out=(weights, status[, aux])`: write into these arrays (e.g. `pinned_empty`)."""

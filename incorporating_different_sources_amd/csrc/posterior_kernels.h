@@ -165,6 +165,24 @@ hipError_t tp_tiled_prefix_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, 
 size_t tp_tiled_prefix_bytes(int k, long long panel_rows, int n_L, int* nblk_out);
 size_t tp_tiled_slot_doubles(int k);
 
+// solve sweep (posterior_sweep.hip): one workgroup per (window, shift) of the windows [w_first, w_first + w_count), whose
+// kept matrices lie in `post` (window w_first first).  All other arrays are indexed by the window's number in the batch.
+#define TP_SWEEP_KMAX_RHS 16
+struct tp_sweep_kargs_t {
+    const double* post;         // [w_count x k x k] matrices M_w of this sub-range, symmetric, full storage
+    const double* default_rhs;  // optional [W x k]: slot r = 0 (the window's own right-hand side)
+    const double* rhs;          // optional [W x n_rhs x k]: the caller's columns, behind the default
+    const double* shift;        // optional [W x S x 2] = (d, e): adds d I + e 1 1'
+    double* x;                  // [W x S x R x k]
+    int* status;                // [W x S]
+    long long w_first, w_count;
+    int k, S, R, n_rhs;
+    double gamma;
+};
+int tp_sweep_max_k(void);
+size_t tp_sweep_lds_bytes(int k, int R);
+hipError_t tp_sweep_launch(const tp_sweep_kargs_t& a, hipStream_t stream);
+
 // price front-end (returns_frontend.hip): out[i][c] = log(prices[num[i]][c] / prices[den[i]][c]), NaN -> 0
 hipError_t tp_log_return_rows_launch(const double* prices, int ld, const int* num, const int* den, long long n_out,
                                      double* out, hipStream_t stream);

@@ -58,6 +58,7 @@ struct tp_handle_s {
     int tiled_arena_gib = 0;        // TP_TILED_ARENA_GIB / "tiled_arena_gib" (0: default)
     int tiled_arena_mib = 0;        // TP_TILED_ARENA_MIB / "tiled_arena_mib": a sub-GiB arena per lane (depth-first sub-batches)
     int tiled_lanes = 0;            // TP_TILED_LANES / "tiled_lanes": sub-batches in flight on streams of their own (0: default)
+    int sweep_chunk_windows = 0;    // "sweep_chunk_windows": windows per sub-range of tp_batch_solve_sweep (0: automatic)
     hipStream_t lane_stream[TP_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t lane_done[TP_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t lane_start = nullptr;
@@ -86,6 +87,10 @@ struct tp_batch_s {
     DevBuf weights, status, aux, dbg, gather_w, gather_s, weights2, status2, stamps, rhs, out_rhs, shift;
     DevBuf post;                                              // kept posterior matrices [post_count x k x k] (tp_batch_keep_posterior)
     int64_t post_w0 = 0, post_count = 0;
+    // solve sweep (tp_batch_solve_sweep): buffers of its own, so that a sweep leaves the batch's results, kept matrices and
+    // kept right-hand sides alone.  sw_post holds the matrices of ONE sub-range of windows at a time
+    DevBuf sw_weights, sw_status, sw_aux, sw_rhs0, sw_post, sw_shift, sw_rhs, sw_x, sw_xstatus;
+    int sw_S = 0, sw_R = 0;                                   // shape of the last sweep (0: none yet)
     DevBuf fe_prices, fe_num, fe_den, fe_hf_prices, fe_hf_num, fe_hf_den;   // price front-end staging (freed after a synchronous upload)
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)
@@ -598,7 +603,8 @@ int destroy_batch(tp_batch_t b, bool device_calls) {
                          &b->panel, &b->start, &b->row_idx, &b->n_rows, &b->col_idx, &b->rf_adj, &b->hf_panel, &b->hf_start,
                          &b->hf_row_idx, &b->hf_count, &b->w0, &b->n0, &b->weights, &b->status, &b->aux, &b->dbg,
                          &b->gather_w, &b->gather_s, &b->weights2, &b->status2, &b->stamps, &b->rhs, &b->out_rhs, &b->shift,
-                         &b->prefix, &b->hf_prefix, &b->post};
+                         &b->prefix, &b->hf_prefix, &b->post, &b->sw_weights, &b->sw_status, &b->sw_aux, &b->sw_rhs0,
+                         &b->sw_post, &b->sw_shift, &b->sw_rhs, &b->sw_x, &b->sw_xstatus};
         for (DevBuf* d : all) release(*d);
         for (int l = 0; l < TP_MAX_LANES; ++l)
             for (DevBuf* d : {&b->t_arena[l], &b->t_rinv[l], &b->t_ybar[l], &b->t_zc[l], &b->t_scal[l], &b->t_flags[l], &b->t_part[l]}) release(*d);
@@ -644,6 +650,8 @@ extern "C" {
 const char* tp_version(void) { return "tangency-posterior 0.6.0 (gfx950, fp64 MFMA: one wavefront per window k<=143, two or four per window k<=239, tiled pipeline k<=2047 with shared daily and intraday block Grams)"; }
 
 int tp_max_assets(void) { return tp_tiled_max_assets(); }
+
+int tp_sweep_max_assets(void) { return tp_sweep_max_k(); }
 
 int tp_device_count(void) {
     int n = 0;
@@ -710,6 +718,10 @@ int tp_set_option(tp_handle_t h, const char* name, int value) {
     else if (n == "tiled_arena_mib") h->tiled_arena_mib = value;
     else if (n == "tiled_lanes") h->tiled_lanes = value;
     else if (n == "hf_share_min_blocks") h->hf_share_min_blocks = value;
+    else if (n == "sweep_chunk_windows") {
+        if (value < 0) return fail(h, TP_ERR_INVALID, "tp_set_option: sweep_chunk_windows=%d < 0", value);
+        h->sweep_chunk_windows = value;
+    }
     else return fail(h, TP_ERR_INVALID, "tp_set_option: unknown option '%s'", name);
     return TP_OK;
 }
@@ -1143,6 +1155,169 @@ int tp_batch_run(tp_batch_t b) {
     if (!b->ran) HIP_TRY(h, hipEventCreateWithFlags(&b->ran, hipEventDisableTiming));
     HIP_TRY(h, hipEventRecord(b->ran, h->stream));
     return flush_gather(h);      // with the next kernel queued, put the requested gather of the previous run on its stream
+}
+
+// Solve sweep.  Windows go through in sub-ranges of `chunk` windows: the batch's own run kernel stores the matrices of a
+// sub-range (the keep_posterior store) and, once, every window's default right-hand side (the keep_rhs store) into the
+// sweep's workspace, then posterior_sweep_kernel solves the sub-range's (window, shift) pairs.  Default chunk: as many
+// windows as TP_SWEEP_WORKSPACE_BYTES of matrices hold (256 MiB, the size of the Infinity Cache: the solve kernel reads
+// what the Gram pass has just written), never more than 2^30 (window, shift) pairs per launch.
+#define TP_SWEEP_WORKSPACE_BYTES (256ull << 20)
+static int sweep_alloc(tp_handle_t h, DevBuf& buf, size_t bytes, const char* what) {
+    if (bytes == 0) bytes = 8;
+    if (buf.bytes >= bytes) return TP_OK;
+    release(buf);
+    const hipError_t e = hipMalloc(&buf.p, bytes);
+    if (e != hipSuccess) {
+        buf.p = nullptr;
+        (void)hipGetLastError();                       // not left behind for the next launch's error check
+        return fail(h, TP_ERR_HIP, "tp_batch_solve_sweep: cannot allocate %zu bytes (%s): %s", bytes, what, hipGetErrorString(e));
+    }
+    buf.bytes = bytes;
+    return TP_OK;
+}
+
+int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift, int32_t n_rhs, const double* rhs,
+                         int32_t default_rhs) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    const int k = b->p.k;
+    const int64_t W = b->W;
+    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep before tp_batch_upload");
+    if (n_shift < 0) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: n_shift=%d < 0", n_shift);
+    if (n_rhs < 0) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: n_rhs=%d < 0", n_rhs);
+    if (shift && b->p.strategy != TP_STRATEGY_JEFFREYS)
+        return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: a shift applies to the Jeffreys strategy only");
+    if (shift && n_shift < 1) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: shift given with n_shift=0");
+    if (!shift && n_shift > 1) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: n_shift=%d without shift", n_shift);
+    const int S = n_shift > 1 ? n_shift : 1;
+    const long long R = (default_rhs ? 1 : 0) + (long long)n_rhs;
+    if (R < 1 || R > TP_SWEEP_MAX_RHS)
+        return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: %lld right-hand sides per window outside [1, %d]", R, TP_SWEEP_MAX_RHS);
+    if (n_rhs > 0 && !rhs) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: n_rhs=%d without rhs", n_rhs);
+    if (shift)
+        for (int64_t i = 0; i < 2 * W * S; ++i)
+            if (!(shift[i] >= 0.0) || !std::isfinite(shift[i]))
+                return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: shift[%lld] must be finite and >= 0", (long long)i);
+    if (k > tp_sweep_max_assets())
+        return fail(h, TP_ERR_UNSUPPORTED, "tp_batch_solve_sweep: k=%d exceeds the sweep kernel's largest universe %d", k,
+                    tp_sweep_max_assets());
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (b->upload_pending) {          // tp_batch_upload_async: the kernel stream waits for the copy stream's event
+        HIP_TRY(h, hipStreamWaitEvent(h->stream, b->upload_done, 0));
+        b->upload_pending = false;
+    }
+    // Unlike tp_batch_run the call drains the handle's stream here (documented in the header): an earlier sweep may still
+    // read the buffers about to be reallocated or refilled, and ev0 / ev1 may still be waiting to be read
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int rc = harvest_kernel_time(h);
+    if (rc != TP_OK) return rc;
+    b->sw_S = 0; b->sw_R = 0;
+    if (W == 0) { b->sw_S = S; b->sw_R = (int)R; return TP_OK; }
+    // windows per sub-range
+    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
+    int64_t chunk = h->sweep_chunk_windows > 0 ? h->sweep_chunk_windows : (int64_t)(TP_SWEEP_WORKSPACE_BYTES / mat_bytes);
+    if (chunk > (1ll << 30) / S) chunk = (1ll << 30) / S;
+    if (chunk < 1) chunk = 1;
+    if (chunk > W) chunk = W;
+    rc = sweep_alloc(h, b->sw_post, mat_bytes * (size_t)chunk, "kept matrices of one sub-range");
+    if (rc == TP_OK) rc = sweep_alloc(h, b->sw_weights, sizeof(double) * (size_t)W * k, "weights of the Gram pass");
+    if (rc == TP_OK) rc = sweep_alloc(h, b->sw_status, sizeof(int32_t) * (size_t)W, "statuses of the Gram pass");
+    if (rc == TP_OK) rc = sweep_alloc(h, b->sw_aux, sizeof(double) * (size_t)W * TP_AUX_STRIDE, "aux of the Gram pass");
+    if (rc == TP_OK) rc = sweep_alloc(h, b->sw_rhs0, sizeof(double) * (size_t)W * k, "default right-hand sides");
+    if (rc == TP_OK) rc = sweep_alloc(h, b->sw_x, sizeof(double) * (size_t)W * S * (size_t)R * k, "solutions");
+    if (rc == TP_OK) rc = sweep_alloc(h, b->sw_xstatus, sizeof(int32_t) * (size_t)W * S, "solution statuses");
+    if (rc == TP_OK && shift) rc = sweep_alloc(h, b->sw_shift, sizeof(double) * 2 * (size_t)W * S, "shifts");
+    if (rc == TP_OK && n_rhs > 0) rc = sweep_alloc(h, b->sw_rhs, sizeof(double) * (size_t)W * n_rhs * k, "right-hand sides");
+    if (rc != TP_OK) return rc;
+    // the caller's arrays: copied here, no host pointer is kept
+    if (shift) HIP_TRY(h, hipMemcpyAsync(b->sw_shift.p, shift, sizeof(double) * 2 * (size_t)W * S, hipMemcpyHostToDevice, h->stream));
+    if (n_rhs > 0) HIP_TRY(h, hipMemcpyAsync(b->sw_rhs.p, rhs, sizeof(double) * (size_t)W * n_rhs * k, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
+
+    // Gram pass: the batch as a plain run would see it - no custom right-hand side, no shift - writing into the sweep's
+    // buffers, and without the shared block sums (whether those are used depends on W: M_w must not)
+    tp_kargs_t a = make_kargs(b);
+    a.rhs = nullptr;
+    a.shift = nullptr;
+    a.prefix = nullptr; a.winsum = nullptr; a.prefix_nblk = 0;
+    for (int i = 0; i < 4; ++i) a.winsum_L[i] = 0;
+    a.weights = (double*)b->sw_weights.p;
+    a.status = (int*)b->sw_status.p;
+    a.aux = (double*)b->sw_aux.p;
+    a.out_rhs = (double*)b->sw_rhs0.p;
+    a.out_post = (double*)b->sw_post.p;
+    a.stamps = nullptr;
+    tp_sweep_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.post = (const double*)b->sw_post.p;
+    sa.default_rhs = default_rhs ? (const double*)b->sw_rhs0.p : nullptr;
+    sa.rhs = n_rhs > 0 ? (const double*)b->sw_rhs.p : nullptr;
+    sa.shift = shift ? (const double*)b->sw_shift.p : nullptr;
+    sa.x = (double*)b->sw_x.p;
+    sa.status = (int*)b->sw_xstatus.p;
+    sa.k = k; sa.S = S; sa.R = (int)R; sa.n_rhs = n_rhs;
+    sa.gamma = b->p.gamma;
+    const tp_launch_info_t keep_launch = h->last_launch;      // tp_last_launch describes tp_batch_run launches
+    // one event pair around all launches: inside a region the next pair of the ring (a sweep is one step of
+    // tp_region_steps), outside ev0 / ev1 - as launch() does for a run
+    hipEvent_t t0 = h->ev0, t1 = h->ev1;
+    const bool ring = h->in_region && h->ring_used < (int)h->ring0.size();
+    if (ring) { t0 = h->ring0[(size_t)h->ring_used]; t1 = h->ring1[(size_t)h->ring_used]; }
+    HIP_TRY(h, hipEventRecord(t0, h->stream));
+    for (int64_t w0 = 0; w0 < W; w0 += chunk) {
+        const int64_t n = W - w0 < chunk ? W - w0 : chunk;
+        a.w_first = w0; a.w_count = n;
+        a.post_w0 = w0; a.post_count = n;
+        rc = launch(b, a, n, false);
+        if (rc != TP_OK) { h->last_launch = keep_launch; return rc; }
+        sa.w_first = w0; sa.w_count = n;
+        const hipError_t e = tp_sweep_launch(sa, h->stream);
+        if (e != hipSuccess) { h->last_launch = keep_launch; return fail(h, TP_ERR_HIP, "sweep kernel launch failed: %s", hipGetErrorString(e)); }
+    }
+    h->last_launch = keep_launch;
+    HIP_TRY(h, hipEventRecord(t1, h->stream));
+    if (ring) ++h->ring_used; else h->kernel_timed = true;    // tp_last_timing().kernel_ms = Gram passes + solves
+    // the sweep's kernels read the batch's inputs: a later tp_batch_upload_async must wait for them, as for a run
+    if (!b->ran) HIP_TRY(h, hipEventCreateWithFlags(&b->ran, hipEventDisableTiming));
+    HIP_TRY(h, hipEventRecord(b->ran, h->stream));
+    b->sw_S = S; b->sw_R = (int)R;
+    // a gather requested by tp_batch_gather_async goes onto its stream now, as at the end of a tp_batch_run (it reads the
+    // batch's result buffers up to its own snapshot event; the sweep writes none of them)
+    return flush_gather(h);
+}
+
+int tp_batch_download_sweep(tp_batch_t b, double* x, int32_t* status) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    if (b->sw_S < 1 || b->sw_R < 1)
+        return fail(h, TP_ERR_INVALID, "tp_batch_download_sweep: no tp_batch_solve_sweep before it");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int rc = harvest_kernel_time(h);
+    if (rc != TP_OK) return rc;
+    if (b->W == 0) return TP_OK;
+    const size_t n = (size_t)b->W * b->sw_S;
+    if (x) HIP_TRY(h, hipMemcpyAsync(x, b->sw_x.p, sizeof(double) * n * b->sw_R * b->p.k, hipMemcpyDeviceToHost, h->stream));
+    if (status) HIP_TRY(h, hipMemcpyAsync(status, b->sw_xstatus.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return TP_OK;
+}
+
+int tp_batch_download_sweep_rhs(tp_batch_t b, double* rhs_out) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    if (b->sw_S < 1 || b->sw_R < 1)
+        return fail(h, TP_ERR_INVALID, "tp_batch_download_sweep_rhs: no tp_batch_solve_sweep before it");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int rc = harvest_kernel_time(h);
+    if (rc != TP_OK) return rc;
+    if (b->W == 0) return TP_OK;
+    if (!rhs_out) return fail(h, TP_ERR_INVALID, "tp_batch_download_sweep_rhs: rhs_out is NULL");
+    HIP_TRY(h, hipMemcpyAsync(rhs_out, b->sw_rhs0.p, sizeof(double) * (size_t)b->W * b->p.k, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return TP_OK;
 }
 
 static int harvest_kernel_time(tp_handle_t h) {

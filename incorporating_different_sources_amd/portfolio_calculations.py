@@ -569,7 +569,8 @@ def _jorion_from_solves(x_t, x_one, t, T, N, gamma):
 
 
 def _jorion_batch(kw, gamma, k, N):
-    """Two launches over the same resident batch: right-hand side t (default) and right-hand side 1."""
+    """Two launches over the same resident batch: right-hand side t (default) and right-hand side 1.  (One solve sweep
+    with S = 1, R = 2 gives the same pair from one Gram pass, but measured slower at this shape: DESIGN.md section 4e.)"""
     dev = _native.default_device()
     W = len(kw["n_rows"])
     b = _native.Batch(dev, "jeffreys", k, N, kw["n_r"], 1.0, W, 0, flags=_native.FLAG_CENTER_BY_ROWS)
@@ -642,19 +643,59 @@ def _greyserman_from_solves(u_t, u_one, t, n, xi, eta, k, gamma):
     return (scale[:, :, None] * x).mean(axis=1)
 
 
+_GREYSERMAN_SWEEP_BYTES = 1 << 30   # solutions of one sweep (dates x draws x 2 x k doubles, on the device and on the host)
+
+
 def _greyserman_batch(kw, gamma, k, N, draws=None):
-    """All dates of `kw` (the `batch.pack_windows` layout), GREYSERMAN_DRAWS windows per date."""
-    dev = _native.default_device()
+    """All dates of `kw` (the `batch.pack_windows` layout): one window per date and one solve sweep over its
+    GREYSERMAN_DRAWS ridge shifts d = eta_b/2 with the right-hand sides [t, 1] (`Batch.solve_sweep`) - one Gram product
+    per date.  A sweep holds dates x draws x 2 x k solutions on the device and on the host, so the dates go through in
+    groups of at most _GREYSERMAN_SWEEP_BYTES of solutions (1,342 dates at k = 50, 469 at k = 143, with 1000 draws); a
+    date's result does not depend on the grouping.  Above `sweep_max_assets()`: GREYSERMAN_DRAWS repeated windows per
+    date, two launches per 32 dates."""
     n_rows = np.asarray(kw["n_rows"])
     W = len(n_rows)
+    xi, eta = _greyserman_hyper(W, draws)
+    if k > _native.sweep_max_assets():
+        return _greyserman_batch_repeated(kw, gamma, k, N, xi, eta)
+    dev = _native.default_device()
+    B = eta.shape[1]
+    per_window = ("start", "row_idx", "n_rows", "col_idx", "rf_adj")
+    group = max(1, _GREYSERMAN_SWEEP_BYTES // (B * 2 * k * 8))
+    out = np.empty((W, k))
+    for lo in range(0, W, group):
+        hi = min(W, lo + group)
+        sub = {key: (np.asarray(val)[lo:hi] if key in per_window and val is not None else val)
+               for key, val in kw.items() if key not in ("n_r", "m")}
+        shift = np.zeros((hi - lo, B, 2))
+        shift[:, :, 0] = eta[lo:hi] / 2                                                  # eta_b S_h = eta_b/2 (I + 11')
+        b = _native.Batch(dev, "jeffreys", k, N, kw["n_r"], 1.0, hi - lo, 0, flags=_native.FLAG_NO_CENTER)
+        try:
+            b.upload(**sub)
+            u, status = b.solve_sweep(shift=shift, rhs=np.ones((hi - lo, 1, k)), default_rhs=True)
+            _raise_on_status(status.reshape(-1))
+            t = b.download_sweep_rhs()                     # the Gram pass also leaves t = X'1 (ref:222)
+        finally:
+            b.close()
+        out[lo:hi] = _greyserman_from_solves(u[:, :, 0, :], u[:, :, 1, :], t, n_rows[lo:hi], xi[lo:hi], eta[lo:hi], k, gamma)
+    return out
+
+
+def _greyserman_hyper(W, draws):
+    """(xi, eta) [W x B]: drawn date-major, as the reference's day loop draws, or the caller's fixed `draws`."""
     B = GREYSERMAN_DRAWS if draws is None else np.asarray(draws[0]).shape[-1]
     if draws is None:
-        pairs = [_greyserman_draws(B) for _ in range(W)]          # date-major, as the reference's day loop draws
-        xi = np.array([p[0] for p in pairs])
-        eta = np.array([p[1] for p in pairs])
-    else:
-        xi = np.broadcast_to(np.asarray(draws[0], dtype=np.float64), (W, B))
-        eta = np.broadcast_to(np.asarray(draws[1], dtype=np.float64), (W, B))
+        pairs = [_greyserman_draws(B) for _ in range(W)]
+        return np.array([p[0] for p in pairs]), np.array([p[1] for p in pairs])
+    return (np.broadcast_to(np.asarray(draws[0], dtype=np.float64), (W, B)),
+            np.broadcast_to(np.asarray(draws[1], dtype=np.float64), (W, B)))
+
+
+def _greyserman_batch_repeated(kw, gamma, k, N, xi, eta):
+    """The path above `sweep_max_assets()`: every date's index arrays repeated once per draw."""
+    dev = _native.default_device()
+    n_rows = np.asarray(kw["n_rows"])
+    W, B = eta.shape
     per_window = ("start", "row_idx", "n_rows", "col_idx", "rf_adj")
     out = np.empty((W, k))
     for lo in range(0, W, _GREYSERMAN_DATES_PER_LAUNCH):
