@@ -1,0 +1,152 @@
+// tangency_host.h - internal to the host layer of libtangency.so (tangency_api.cpp, tangency_plan.cpp,
+// tangency_comm.cpp): the handle and batch structures and the helpers the three files share.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <cstdint>
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+#include "../../include/tangency_posterior.h"
+#include "host_resources.h"
+#include "posterior_kernels.h"
+
+#define TP_MAX_LANES 4
+#define TP_REGION_MAX_STEPS 512
+
+// Members are destroyed in reverse order of declaration: the kernel stream is declared before every other stream and
+// event, so it goes last (destroy_handle takes the communicator down before any of them).
+struct tp_handle_s {
+    int device = -1;
+    Stream stream;
+    Span kernel_span;               // the last timed launch outside a region (also: a synchronous upload, a download)
+    Span region_span;               // tp_region_begin .. tp_region_end
+    hipDeviceProp_t prop;
+    std::string err;
+    double kernel_ms = 0, h2d_ms = 0, d2h_ms = 0, gather_ms = 0;
+    tp_launch_info_t last_launch{0, 0, 0, 0};
+    ncclComm_t comm = nullptr;
+    int rank = 0, world = 1;
+    // overlapped gather (tp_batch_gather_async): its own high-priority stream next to the kernel stream
+    Stream comm_stream;
+    Span gather_span;
+    // asynchronous uploads (tp_batch_upload_async): a copy stream of their own, so that the H2D copies of the next
+    // batch run under the kernel of the current one
+    Stream copy_stream;
+    Span copy_span;
+    tp_batch_t deferred = nullptr;  // batch whose tp_batch_gather_async is requested but not yet on the gather stream
+    // Tuning switches (A/B measurements, tests): read from the environment ONCE, in tp_create, and changed only through
+    // tp_set_option on this handle - no launch path reads the environment (several host threads launch at once in the
+    // one-process-all-GPUs mode while a test may be changing it).
+    tp_kopts_t opts{};
+    int no_shared_gram = 0;         // TP_NO_SHARED_GRAM / "no_shared_gram"
+    int hf_share_min_blocks = 6;    // "hf_share_min_blocks": whole intraday blocks per window from which the large-k path shares them
+    int tiled_arena_gib = 0;        // TP_TILED_ARENA_GIB / "tiled_arena_gib" (0: default)
+    int tiled_arena_mib = 0;        // TP_TILED_ARENA_MIB / "tiled_arena_mib": a sub-GiB arena per lane (depth-first sub-batches)
+    int tiled_lanes = 0;            // TP_TILED_LANES / "tiled_lanes": sub-batches in flight on streams of their own (0: default)
+    int sweep_chunk_windows = 0;    // "sweep_chunk_windows": windows per sub-range of tp_batch_solve_sweep (0: automatic)
+    Stream lane_stream[TP_MAX_LANES];
+    Event lane_done[TP_MAX_LANES];
+    Event lane_start;
+    int phase_limit = 0;            // TP_PHASE_LIMIT (diagnostic builds only)
+    std::vector<tp_batch_t> batches;   // live batches of this handle (destroyed with it if the caller forgot them)
+    // per-step kernel times inside a tp_region_begin / tp_region_end bracket: every timed launch of the region records
+    // its own span (no host wait in between), tp_region_end reads them all (tp_region_steps returns them)
+    std::vector<Span> ring;         // TP_REGION_MAX_STEPS spans, created whole or not at all
+    int ring_used = 0;
+    bool in_region = false;
+    std::vector<double> step_ms;
+};
+
+struct PriceStaging { DevBuf prices, num, den; };   // price front-end: prices and the row pairs of the returns
+
+struct tp_batch_s {
+    tp_handle_t h = nullptr;
+    tp_params_t p{};
+    int64_t W = 0;
+    int panel_ld = 0, hf_ld = 0;
+    DevBuf panel, start, row_idx, n_rows, col_idx, rf_adj, hf_panel, hf_start, hf_row_idx, hf_count, w0, n0;
+    DevBuf weights, status, aux, dbg, gather_w, gather_s, weights2, status2, stamps, rhs, out_rhs, shift;
+    DevBuf post;                                              // kept posterior matrices [post_count x k x k] (tp_batch_keep_posterior)
+    int64_t post_w0 = 0, post_count = 0;
+    // solve sweep (tp_batch_solve_sweep): buffers of its own, so that a sweep leaves the batch's results, kept matrices and
+    // kept right-hand sides alone.  sw_post holds the matrices of ONE sub-range of windows at a time
+    DevBuf sw_weights, sw_status, sw_aux, sw_rhs0, sw_post, sw_shift, sw_rhs, sw_x, sw_xstatus;
+    int sw_S = 0, sw_R = 0;                                   // shape of the last sweep (0: none yet)
+    PriceStaging fe, fe_hf;                                   // daily and intraday (freed after a synchronous upload)
+    DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
+    int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)
+    int winsum_L[4] = {0, 0, 0, 0};                           // register-tile path: the whole-block counts of the windows
+    DevBuf t_arena[TP_MAX_LANES], t_rinv[TP_MAX_LANES], t_ybar[TP_MAX_LANES], t_zc[TP_MAX_LANES], t_scal[TP_MAX_LANES],
+        t_flags[TP_MAX_LANES];                                // large-k path workspace, one per lane
+    // large-k path, conjugate: shared intraday sums (posterior_tiled_wave.h).  Decided at upload (plan_shared_hf): the
+    // windows' intraday rows are contiguous, of one length, and advance by hf_B rows; the tables are per sub-batch
+    // large-k path: the daily tables cover the blocks of the sub-batch in flight (plan_daily_tables); host copies of
+    // what the block ranges are computed from
+    bool prefix_per_sub = false;
+    std::vector<int64_t> h_start;
+    std::vector<int32_t> h_n_rows;
+    std::vector<int64_t> h_hf_start;                          // host copy of hf_start (the sub-batches' block ranges)
+    int hf_B = 0, hf_L = 0;                                   // rows per block (0 = not shared), whole blocks per window
+    long long hf_phase = 0;                                   // blocks start at rows = hf_phase (mod hf_B)
+    DevBuf hf_prefix;                                         // block Grams + block-window sums of the sub-batch in flight
+    DevBuf t_part[TP_MAX_LANES];                              // pieces of S0 w0 per (window, row block, column block)
+    int64_t tiled_capacity = 0;                               // windows in flight per sub-batch (per lane)
+    int tiled_lanes = 0;                                      // lanes the workspace was sized for
+    bool uploaded = false;
+    bool gathered = false;
+    bool rhs_valid = false;                          // out_rhs was allocated before the last run (tp_batch_keep_rhs)
+    bool post_valid = false;                         // post was allocated before the last run (tp_batch_keep_posterior)
+    Event ran;                                       // end of this batch's last launch (recorded by every tp_batch_run)
+    Event upload_done;                               // tp_batch_upload_async: end of the copies on the copy stream
+    bool upload_pending = false;
+    // tp_batch_gather_async: results alternate between (weights, status) and (weights2, status2), so that the
+    // gather of run i reads one pair while run i+1 writes the other; run i+2 waits for that gather's event
+    bool pingpong = false;
+    int parity = 0;                                  // pair written by the last run
+    Event gather_done[2];
+    bool gather_pending[2] = {false, false};
+    Event snap;                                      // end of the run whose results the requested gather reads
+    bool gather_req = false;                         // requested by tp_batch_gather_async, issued by flush_gather
+    int gather_req_parity = 0, gather_root = 0;
+    double* out_weights() const { return (double*)(parity ? weights2.p : weights.p); }
+    int32_t* out_status() const { return (int32_t*)(parity ? status2.p : status.p); }
+};
+
+namespace tp_host {
+
+// records the message on the handle (h = NULL: for tp_last_error(NULL)) and returns `code`
+int fail(tp_handle_t h, int code, const char* fmt, ...);
+
+#define HIP_TRY(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
+    return tp_host::fail((h), TP_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+#define NCCL_TRY(h, expr) do { ncclResult_t r_ = (expr); if (r_ != ncclSuccess) \
+    return tp_host::fail((h), TP_ERR_RCCL, "%s failed: %s (%s:%d)", #expr, ncclGetErrorString(r_), __FILE__, __LINE__); } while (0)
+
+// the one way to allocate device memory: grow-only, names what could not be had
+int ensure(tp_handle_t h, DevBuf& b, size_t bytes, const char* what);
+
+inline int harvest_kernel_time(tp_handle_t h) {
+    HIP_TRY(h, h->kernel_span.read(h->kernel_ms));
+    return TP_OK;
+}
+
+// drain the kernel stream, read the kernel span, copy what has a destination, drain
+struct Copy { void* dst; const void* src; size_t bytes; };
+int download(tp_handle_t h, std::initializer_list<Copy> copies);
+
+// tangency_plan.cpp: input validation, upload planning, large-k launch planning
+int validate_pairs(tp_handle_t h, const char* what, const int32_t* num, const int32_t* den, int64_t n, int64_t price_rows);
+int validate_inputs(tp_handle_t h, const tp_params_t& p, int64_t W, const tp_inputs_t* in_raw);
+int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int* lanes_out);
+int plan_daily_tables(tp_batch_t b, tp_kargs_t& sub, bool whole);
+int plan_hf_tables(tp_batch_t b, tp_kargs_t& sub);
+int plan_shared_gram(tp_batch_t b, const tp_inputs_t* in);
+void plan_shared_hf(tp_batch_t b, const tp_inputs_t* in);
+
+// tangency_comm.cpp
+int flush_gather(tp_handle_t h);
+
+}  // namespace tp_host
