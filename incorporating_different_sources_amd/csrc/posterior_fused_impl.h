@@ -44,15 +44,9 @@
 //    col_idx select must sit OUTSIDE the load loop: either mistake serialises the loads;
 //  * lane constants are re-derived per phase from a laundered thread id (fresh()): CSE across phases
 //    otherwise keeps ~100 registers alive for the whole kernel.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <type_traits>
-
-#include "posterior_kernels.h"
+#include "posterior_device_prims.h"
 
 // (included by posterior_fused_nt.hip, once per tile count NT)
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 // how many 4-row MFMA k-steps of a staged chunk are unrolled together (operand reads in flight)
 #ifndef TP_KSTEP_UNROLL
@@ -109,30 +103,6 @@ struct Cfg {
     static constexpr int LDS_BYTES = LDS_DOUBLES * 8;
 };
 
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
-// rotate right by N lanes inside each row of 16 lanes (DPP row_ror:N) - no LDS crossbar involved
-template <int N>
-__device__ __forceinline__ double dpp_row_ror(double v) {
-    // every lane of a row_ror has a source lane: no "old" value is needed (mov_dpp leaves it undefined)
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x120 + N, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x120 + N, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
-// sum over the 16 lanes that share lane>>4 (one MFMA row group); every lane gets the sum
-__device__ __forceinline__ double rowgroup_sum16(double v) {
-    v += dpp_row_ror<8>(v);
-    v += dpp_row_ror<4>(v);
-    v += dpp_row_ror<2>(v);
-    v += dpp_row_ror<1>(v);
-    return v;
-}
-
 // An identity the optimiser cannot see through.  Every phase re-derives its lane constants (row/column
 // of the lane, LDS addresses, masks) from a laundered thread id, so that common-subexpression
 // elimination and loop-invariant hoisting cannot stretch those values' live ranges over the whole
@@ -163,22 +133,6 @@ __device__ __forceinline__ double rsqrt_nr(double d) {
     return y;
 }
 
-// 1/sqrt(d) from the v_rsq_f64 seed (23 good bits) by ONE third-order step, y (1 + e/2 + 3 e^2/8) with
-// e = 1 - d y^2: the error term is O(e^3) ~ 2^-68.  Six instructions on a chain of five (rsqrt_nr: nine on
-// seven) - the pivot chain of the factorisation pays for both.
-__device__ __forceinline__ double rsqrt_cubic(double d) {
-    const double y = __builtin_amdgcn_rsq(d);
-    const double e = fma(-(d * y), y, 1.0);
-    const double u = fma(e, 0.375, 0.5);
-    return fma(y * e, u, y);
-}
-
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- compile-time tile bookkeeping -----------------------------------------------------------
 // Upper-triangle tiles (I <= J) are numbered row-major; wave WV of a workgroup owns tiles
 // t = s*NW + WV (slot s).  Everything below is constexpr so that tile coordinates fold into
@@ -187,13 +141,6 @@ template <int NT>
 constexpr int tile_I(int t) { int i = 0, rem = t; while (rem >= NT - i) { rem -= NT - i; ++i; } return i; }
 template <int NT>
 constexpr int tile_J(int t) { int i = 0, rem = t; while (rem >= NT - i) { rem -= NT - i; ++i; } return i + rem; }
-
-template <int V> using ic = std::integral_constant<int, V>;
-
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B < E) { f(ic<B>{}); static_for<B + 1, E>(f); }
-}
 
 // run f(ic<wv>) with the wave index as a compile-time constant (wv is wave-uniform: scalar branches)
 template <int NW, class F>

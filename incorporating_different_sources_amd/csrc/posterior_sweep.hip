@@ -29,7 +29,7 @@
 // Every (window, shift) is computed by its own workgroup from M_w, the two shift values and the R right-hand sides alone,
 // in an order of operations that depends on k and R only: the result does not depend on W, S, the window's position or
 // the chunking of the host loop.  Workgroup barriers only; nothing spins.
-#include "posterior_kernels.h"
+#include "posterior_device_prims.h"
 
 namespace {
 
@@ -37,12 +37,6 @@ constexpr int SWEEP_THREADS = 256;
 constexpr int SWEEP_TX = 32;            // lanes along a column
 constexpr int SWEEP_XREGS = 3;          // solution registers per lane: k <= 64 * 3
 constexpr int SWEEP_MAX_K = 143;        // 16 x 9 - 1: the one-wave kernels' range; 98.3 KiB of LDS at R = 16
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 __global__ void __launch_bounds__(SWEEP_THREADS) posterior_sweep_kernel(const tp_sweep_kargs_t A) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -109,7 +103,7 @@ __global__ void __launch_bounds__(SWEEP_THREADS) posterior_sweep_kernel(const tp
                 const int i = lane + 64 * q;
                 if (i > j && i < k) part += cj[i] * x[q];
             }
-            const double xj = (cj[k + r] - wave_sum(part)) / cj[j];
+            const double xj = (cj[k + r] - wave_sum64(part)) / cj[j];
 #pragma unroll
             for (int q = 0; q < SWEEP_XREGS; ++q)
                 if (lane + 64 * q == j) x[q] = xj;

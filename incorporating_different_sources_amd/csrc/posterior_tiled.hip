@@ -20,14 +20,9 @@
 //
 // Jeffreys (ref:600-606): J = T - t t'/N is applied as a rank-one correction by tile64_kernel<RANK1>
 // after the Gram pass (t is the border column).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdlib.h>
-#include <type_traits>
 
-#include "posterior_kernels.h"
-
-typedef double d4 __attribute__((ext_vector_type(4)));
+#include "posterior_device_prims.h"
 
 namespace {
 
@@ -37,32 +32,6 @@ constexpr int LDX = 2 * SB + 16;       // LDS row stride of a staged chunk (A co
 constexpr int NTHREADS = 256;
 
 enum { MODE_GRAM = 0, MODE_TRSM = 1, MODE_SYRK = 2, MODE_SYRK_DIAG = 3 };   // SYRK_DIAG: the update of tile (j, j) alone
-
-template <int N>
-__device__ __forceinline__ double dpp_row_ror(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x120 + N, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x120 + N, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double rowgroup_sum16(double v) {
-    v += dpp_row_ror<8>(v);
-    v += dpp_row_ror<4>(v);
-    v += dpp_row_ror<2>(v);
-    v += dpp_row_ror<1>(v);
-    return v;
-}
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// upper-triangle pair p -> (a, b), a <= b < n, row-major
-__device__ __forceinline__ void pair_decode(int p, int n, int& a, int& b) {
-    int i = 0, rem = p;
-    while (rem >= n - i) { rem -= n - i; ++i; }
-    a = i; b = i + rem;
-}
 
 // inverse of pair_decode: row-major number of the upper-triangle pair (a, b), a <= b < n
 __device__ __forceinline__ long long pair_index(int a, int b, int n) { return (long long)a * n - (long long)a * (a - 1) / 2 + (b - a); }
@@ -600,15 +569,6 @@ __global__ void __launch_bounds__(NTHREADS) tiled_rank1_kernel(const tp_kargs_t 
 // ------------------------------------------------------------------------------------------------
 // Block step j: upper Cholesky of the 64 x 64 diagonal block in LDS and R_jj^-1.  Rows >= npiv (the
 // last block only: border row and padding) behave as identity rows.
-// compile-time loop (the pivot loop below needs static register indices)
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_t(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for_t<I + 1, N>(f);
-    }
-}
-
 __global__ void __launch_bounds__(NTHREADS) tiled_diag_kernel(const tp_kargs_t A, const tp_tiled_ws_t ws, const int j) {
     constexpr int LD = SB + 1;
     __shared__ double Tt[SB * LD];             // transpose buffer for R^-1 on the way out
@@ -633,7 +593,7 @@ __global__ void __launch_bounds__(NTHREADS) tiled_diag_kernel(const tp_kargs_t A
         a[r] = M[(long long)(64 * j + 4 * r + g) * KP + 64 * j + c];
         m[r] = (4 * r + g == c) ? 1.0 : 0.0;
     }
-    static_for_t<0, 64>([&](auto pc) __attribute__((always_inline)) {
+    static_for<0, 64>([&](auto pc) __attribute__((always_inline)) {
         constexpr int p = decltype(pc)::value, r = p >> 2, g4 = p & 3;
         if (p < npiv) {                                                  // uniform
             if (g == g4) { rowp[p & 1][c] = a[r]; rowp[p & 1][SB + c] = m[r]; }

@@ -90,9 +90,9 @@ __device__ __forceinline__ void tw_gram_pass(const TRows& src, const int (&co)[4
 #pragma unroll
             for (int i = 0; i < NO; ++i) cs[i] += v[i];
         }
-        static_for_t<0, 4>([&](auto ac) __attribute__((always_inline)) {
+        static_for<0, 4>([&](auto ac) __attribute__((always_inline)) {
             constexpr int a = decltype(ac)::value;
-            static_for_t<0, NB>([&](auto bc) __attribute__((always_inline)) {
+            static_for<0, NB>([&](auto bc) __attribute__((always_inline)) {
                 constexpr int b = decltype(bc)::value;
                 // a diagonal super-tile: the tiles below its diagonal are never read (the diagonal-block kernel and the
                 // left-looking update use column >= row only) - 10 MFMAs per k-step instead of 16
@@ -105,24 +105,24 @@ __device__ __forceinline__ void tw_gram_pass(const TRows& src, const int (&co)[4
     double ra = 0.0, rb = 0.0, rc = 0.0;
     load(va, ra, 0);
     load(vb, rb, 1);
-    static_for_t<0, 4 * NB>([&](auto tc) __attribute__((always_inline)) { tw_pin1(acc[decltype(tc)::value]); });
+    static_for<0, 4 * NB>([&](auto tc) __attribute__((always_inline)) { tw_pin1(acc[decltype(tc)::value]); });
     int ks = 0;
 #pragma nounroll
     for (; 4 * (ks + 3) <= src.count; ks += 3) {
         load(vc, rc, ks + 2);
-        step(va, ra, ks, std::integral_constant<int, 0>{});
+        step(va, ra, ks, ic<0>{});
         load(va, ra, ks + 3);
-        step(vb, rb, ks + 1, std::integral_constant<int, 0>{});
+        step(vb, rb, ks + 1, ic<0>{});
         load(vb, rb, ks + 4);
-        step(vc, rc, ks + 2, std::integral_constant<int, 0>{});
+        step(vc, rc, ks + 2, ic<0>{});
     }
     if (ks < nks) {
         if (ks + 2 < nks) load(vc, rc, ks + 2);
-        step(va, ra, ks, std::integral_constant<int, 1>{});
-        if (ks + 1 < nks) step(vb, rb, ks + 1, std::integral_constant<int, 1>{});
-        if (ks + 2 < nks) step(vc, rc, ks + 2, std::integral_constant<int, 1>{});
+        step(va, ra, ks, ic<1>{});
+        if (ks + 1 < nks) step(vb, rb, ks + 1, ic<1>{});
+        if (ks + 2 < nks) step(vc, rc, ks + 2, ic<1>{});
     }
-    static_for_t<0, NB / 2>([&](auto gc) __attribute__((always_inline)) {
+    static_for<0, NB / 2>([&](auto gc) __attribute__((always_inline)) {
         constexpr int g = 8 * decltype(gc)::value;
         tw_settle8(acc[g], acc[g + 1], acc[g + 2], acc[g + 3], acc[g + 4], acc[g + 5], acc[g + 6], acc[g + 7]);
     });
@@ -169,7 +169,7 @@ __device__ __forceinline__ void gram64_wave_body(const tp_kargs_t& A, const tp_t
         yb[i] = (conj && cval[i]) ? ybar[gcl] : 0.0;
     }
     d4 acc[4 * NB];
-    static_for_t<0, 4 * NB>([&](auto tc) __attribute__((always_inline)) {
+    static_for<0, 4 * NB>([&](auto tc) __attribute__((always_inline)) {
         acc[decltype(tc)::value] = d4{0.0, 0.0, 0.0, 0.0};
         tw_pin1(acc[decltype(tc)::value]);
     });
@@ -269,7 +269,7 @@ __device__ __forceinline__ void gram64_wave_body(const tp_kargs_t& A, const tp_t
     // (the super-tiles of a pair are neighbours in the row-major numbering of the triangle: slot of (SI, SJ + 1) = slot + 1)
     const d2* q = shared ? (const d2*)(A.winsum + (((long long)li * A.prefix_nblk + tb0) * ntile + pair_index(SI, SJ, ws.NS)) * (SB * SB)) + lane
                          : nullptr;
-    static_for_t<0, 4>([&](auto ac) __attribute__((always_inline)) {
+    static_for<0, 4>([&](auto ac) __attribute__((always_inline)) {
         constexpr int a = decltype(ac)::value;
         d2 v2[NB][2];
         if (shared) {
@@ -279,7 +279,7 @@ __device__ __forceinline__ void gram64_wave_body(const tp_kargs_t& A, const tp_t
 #pragma unroll
                 for (int h = 0; h < 2; ++h) v2[b][h] = q[(b >> 2) * (SB * SB / 2) + a * 512 + ((b & 3) * 2 + h) * 64];
         }
-        static_for_t<0, NB>([&](auto bc) __attribute__((always_inline)) {
+        static_for<0, NB>([&](auto bc) __attribute__((always_inline)) {
             constexpr int b = decltype(bc)::value;
             d4 x = acc[NB * a + b];              // (below the diagonal of a diagonal super-tile: the zeros it started with)
             if (shared && (!DIAG || a <= b)) {
@@ -359,7 +359,7 @@ __device__ __forceinline__ void hfblock64_wave_body(const tp_kargs_t& A, const t
         yb[i] = tw_reference(A, cval[i], co[i]); cs[i] = 0.0;
     }
     d4 acc[4 * NB];
-    static_for_t<0, 4 * NB>([&](auto tc) __attribute__((always_inline)) {
+    static_for<0, 4 * NB>([&](auto tc) __attribute__((always_inline)) {
         acc[decltype(tc)::value] = d4{0.0, 0.0, 0.0, 0.0};
         tw_pin1(acc[decltype(tc)::value]);
     });
@@ -371,9 +371,9 @@ __device__ __forceinline__ void hfblock64_wave_body(const tp_kargs_t& A, const t
     typedef double d2 __attribute__((ext_vector_type(2)));
     const long long ntile = (long long)ws.NS * (ws.NS + 1) / 2;
     d2* p = (d2*)(out + (blk * ntile + tile) * (SB * SB)) + lane;
-    static_for_t<0, 4>([&](auto ac) __attribute__((always_inline)) {
+    static_for<0, 4>([&](auto ac) __attribute__((always_inline)) {
         constexpr int a = decltype(ac)::value;
-        static_for_t<0, NB>([&](auto bc) __attribute__((always_inline)) {
+        static_for<0, NB>([&](auto bc) __attribute__((always_inline)) {
             constexpr int b = decltype(bc)::value;
             const d4 x = acc[NB * a + b];                           // (below the diagonal of a diagonal super-tile: zeros)
             p[a * 512 + (b * 2 + 0) * 64] = d2{x[0], x[1]};
@@ -484,7 +484,7 @@ __device__ __forceinline__ void gram64_wave_hfs_body(const tp_kargs_t& A, const 
     pI[lane] = 0.0;
     pJ[lane] = 0.0;
     d4 acc[4 * NB];
-    static_for_t<0, 4 * NB>([&](auto tc) __attribute__((always_inline)) {
+    static_for<0, 4 * NB>([&](auto tc) __attribute__((always_inline)) {
         acc[decltype(tc)::value] = d4{0.0, 0.0, 0.0, 0.0};
         tw_pin1(acc[decltype(tc)::value]);
     });
@@ -520,7 +520,7 @@ __device__ __forceinline__ void gram64_wave_hfs_body(const tp_kargs_t& A, const 
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         const d2* q = (const d2*)(hq + pair_index(SI, SJ, NS) * (SB * SB)) + lane;
-        static_for_t<0, 4>([&](auto ac) __attribute__((always_inline)) {
+        static_for<0, 4>([&](auto ac) __attribute__((always_inline)) {
             constexpr int a = decltype(ac)::value;
             double ti[4], w0i[4], rowp[4];
 #pragma unroll
@@ -535,7 +535,7 @@ __device__ __forceinline__ void gram64_wave_hfs_body(const tp_kargs_t& A, const 
             for (int b = 0; b < NB; ++b)
 #pragma unroll
                 for (int h = 0; h < 2; ++h) v2[b][h] = q[a * 512 + (b * 2 + h) * 64];
-            static_for_t<0, NB>([&](auto bc) __attribute__((always_inline)) {
+            static_for<0, NB>([&](auto bc) __attribute__((always_inline)) {
                 constexpr int b = decltype(bc)::value;
                 if constexpr (!DIAG || a <= b) {
                     d4 x = acc[NB * a + b];
@@ -600,7 +600,7 @@ __device__ __forceinline__ void gram64_wave_hfs_body(const tp_kargs_t& A, const 
     tw_gram_pass<DIAG, EDGE, false, NB>(ds, co, yb, cval, cbord, 0.0, lane, acc, cs);
     const d2* q = shared ? (const d2*)(A.winsum + (((long long)li * A.prefix_nblk + tb0) * ntile + pair_index(SI, SJ, NS)) * (SB * SB)) + lane
                          : nullptr;
-    static_for_t<0, 4>([&](auto ac) __attribute__((always_inline)) {
+    static_for<0, 4>([&](auto ac) __attribute__((always_inline)) {
         constexpr int a = decltype(ac)::value;
         d2 v2[NB][2];
         if (shared) {
@@ -609,7 +609,7 @@ __device__ __forceinline__ void gram64_wave_hfs_body(const tp_kargs_t& A, const 
 #pragma unroll
                 for (int h = 0; h < 2; ++h) v2[b][h] = q[a * 512 + (b * 2 + h) * 64];
         }
-        static_for_t<0, NB>([&](auto bc) __attribute__((always_inline)) {
+        static_for<0, NB>([&](auto bc) __attribute__((always_inline)) {
             constexpr int b = decltype(bc)::value;
             d4 x = acc[NB * a + b];
             if (shared && (!DIAG || a <= b)) {
@@ -707,18 +707,6 @@ __global__ void __launch_bounds__(64, 1) tiled_gram_wave_pair_kernel(const tp_ka
 // columns (M_a = R_aa^-T), the tile row becomes R_aB = M_a A_aB and the trailing tiles A_IB -= R_aI' R_aB, all by MFMA with
 // operands from the accumulators.  The 64 identity columns of the block ride along as 4 more tile columns: they come out
 // as Y = R_jj^-T, whose transpose is the R_jj^-1 the TRSM and solve kernels read - no inverse pass.
-__device__ __forceinline__ double tw_readlane_d(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-// 1/sqrt(d): v_rsq_f64 seed + one third-order step (see posterior_fused_impl.h, rsqrt_cubic)
-__device__ __forceinline__ double tw_rsqrt_cubic(double d) {
-    const double y = __builtin_amdgcn_rsq(d);
-    const double e = fma(-(d * y), y, 1.0);
-    const double u = fma(e, 0.375, 0.5);
-    return fma(y * e, u, y);
-}
 constexpr int tw_ta(int a, int b) { return a * 4 - a * (a - 1) / 2 + (b - a); }       // A tile (a, b), a <= b: 0..9
 constexpr int tw_ty(int b, int a) { return 10 + b * (b + 1) / 2 + a; }                 // Y tile (b, a), a <= b: 10..19
 
@@ -758,16 +746,16 @@ __global__ void __launch_bounds__(64, TP_DIAG_OCC) tiled_diag_wave_kernel(const 
         IDT[e] = ((e >> 4) == (e & 15)) ? 1.0 : 0.0;
     }
     d4 acc[20];
-    static_for_t<0, 4>([&](auto ac) __attribute__((always_inline)) {
+    static_for<0, 4>([&](auto ac) __attribute__((always_inline)) {
         constexpr int a = decltype(ac)::value;
-        static_for_t<a, 4>([&](auto bc) __attribute__((always_inline)) {
+        static_for<a, 4>([&](auto bc) __attribute__((always_inline)) {
             constexpr int b = decltype(bc)::value;
             d4 x;
 #pragma unroll
             for (int r = 0; r < 4; ++r) x[r] = blk[(long long)(16 * a + fq + 4 * r) * KP + 16 * b + fr];
             acc[tw_ta(a, b)] = x;
         });
-        static_for_t<0, a + 1>([&](auto cc) __attribute__((always_inline)) {
+        static_for<0, a + 1>([&](auto cc) __attribute__((always_inline)) {
             constexpr int c = decltype(cc)::value;
             d4 x = d4{0.0, 0.0, 0.0, 0.0};
             if (c == a) {
@@ -786,9 +774,9 @@ __global__ void __launch_bounds__(64, TP_DIAG_OCC) tiled_diag_wave_kernel(const 
             for (int a = 0; a < 4; ++a) v[a] = p[16 * a];
         };
         auto step = [&](double (&v)[4]) __attribute__((always_inline)) {
-            static_for_t<0, 4>([&](auto ac) __attribute__((always_inline)) {
+            static_for<0, 4>([&](auto ac) __attribute__((always_inline)) {
                 constexpr int a = decltype(ac)::value;
-                static_for_t<a, 4>([&](auto bc) __attribute__((always_inline)) {
+                static_for<a, 4>([&](auto bc) __attribute__((always_inline)) {
                     constexpr int b = decltype(bc)::value;
                     tw_mfma_agpr_neg(acc[tw_ta(a, b)], v[a], v[b]);
                 });
@@ -801,11 +789,11 @@ __global__ void __launch_bounds__(64, TP_DIAG_OCC) tiled_diag_wave_kernel(const 
         constexpr int D = TP_DIAG_DEPTH;
         static_assert(16 % D == 0, "the update loop runs whole groups of D k-steps");
         double v[D][4];
-        static_for_t<0, D>([&](auto dc) __attribute__((always_inline)) { load(v[decltype(dc)::value], decltype(dc)::value); });
-        static_for_t<0, 10>([&](auto tc) __attribute__((always_inline)) { tw_pin1(acc[decltype(tc)::value]); });
+        static_for<0, D>([&](auto dc) __attribute__((always_inline)) { load(v[decltype(dc)::value], decltype(dc)::value); });
+        static_for<0, 10>([&](auto tc) __attribute__((always_inline)) { tw_pin1(acc[decltype(tc)::value]); });
 #pragma nounroll
         for (int ks = 0; ks < nks; ks += D) {
-            static_for_t<0, D>([&](auto dc) __attribute__((always_inline)) {
+            static_for<0, D>([&](auto dc) __attribute__((always_inline)) {
                 constexpr int d = decltype(dc)::value;
                 step(v[d]);
                 const int nx = ks + D + d;
@@ -816,7 +804,7 @@ __global__ void __launch_bounds__(64, TP_DIAG_OCC) tiled_diag_wave_kernel(const 
         tw_settle2(acc[8], acc[9]);
     }
     double badacc = 0.0;
-    static_for_t<0, 4>([&](auto ac) __attribute__((always_inline)) {
+    static_for<0, 4>([&](auto ac) __attribute__((always_inline)) {
         constexpr int a = decltype(ac)::value;
         const int np = npiv - 16 * a < 16 ? npiv - 16 * a : 16;      // pivots of this tile row (uniform)
         if (np > 0) {
@@ -830,8 +818,9 @@ __global__ void __launch_bounds__(64, TP_DIAG_OCC) tiled_diag_wave_kernel(const 
             const double* src = (lane < 16) ? DG : IDT;
 #pragma unroll
             for (int i = 0; i < 16; ++i) e[i] = src[i * 16 + c16];
-            // (2) the pivots (as in posterior_wave_impl.h, phase F)
-            double rinv = tw_rsqrt_cubic(tw_readlane_d(e[0], 0));
+            // (2) the pivots (as in posterior_wave_impl.h, phase F; a copy, not a shared function: moved into one the chain
+            // compiles to a worse schedule, DESIGN.md section 4f - and M_a below keeps identity rows, not zero rows)
+            double rinv = rsqrt_cubic(readlane_d(e[0], 0));
 #pragma unroll
             for (int p = 0; p < 16; ++p) {
                 if (p < np) {
@@ -839,15 +828,15 @@ __global__ void __launch_bounds__(64, TP_DIAG_OCC) tiled_diag_wave_kernel(const 
                     badacc = fma(0.0, rinv, badacc);              // a non-positive or NaN pivot: rinv is an infinity or a NaN
                     double rinv_next = 1.0;
                     if (p + 1 < 16) {
-                        const double s1 = tw_readlane_d(e[p], p + 1);
+                        const double s1 = readlane_d(e[p], p + 1);
                         e[p + 1] = fma(-s1, e[p], e[p + 1]);
-                        double dn = tw_readlane_d(e[p + 1], p + 1);
+                        double dn = readlane_d(e[p + 1], p + 1);
                         dn = (p + 1 < np) ? dn : 1.0;
-                        rinv_next = tw_rsqrt_cubic(dn);
+                        rinv_next = rsqrt_cubic(dn);
                     }
 #pragma unroll
                     for (int i = p + 2; i < 16; ++i) {
-                        const double sI = tw_readlane_d(e[p], i);
+                        const double sI = readlane_d(e[p], i);
                         e[i] = fma(-sI, e[p], e[i]);
                     }
                     rinv = rinv_next;
@@ -871,18 +860,18 @@ __global__ void __launch_bounds__(64, TP_DIAG_OCC) tiled_diag_wave_kernel(const 
                 for (int r = 0; r < 4; ++r) rj = __builtin_amdgcn_mfma_f64_16x16x4f64(mop[r], t[r], rj, 0, 0, 0);
                 t = rj;
             };
-            static_for_t<a, 4>([&](auto bc) __attribute__((always_inline)) { trsm(acc[tw_ta(a, decltype(bc)::value)]); });
-            static_for_t<0, a + 1>([&](auto cc) __attribute__((always_inline)) { trsm(acc[tw_ty(a, decltype(cc)::value)]); });
+            static_for<a, 4>([&](auto bc) __attribute__((always_inline)) { trsm(acc[tw_ta(a, decltype(bc)::value)]); });
+            static_for<0, a + 1>([&](auto cc) __attribute__((always_inline)) { trsm(acc[tw_ty(a, decltype(cc)::value)]); });
             // (4) trailing tiles: A_IB -= R_aI' R_aB, Y_IC -= R_aI' Y_aC
-            static_for_t<a + 1, 4>([&](auto Ic) __attribute__((always_inline)) {
+            static_for<a + 1, 4>([&](auto Ic) __attribute__((always_inline)) {
                 constexpr int I = decltype(Ic)::value;
-                static_for_t<I, 4>([&](auto bc) __attribute__((always_inline)) {
+                static_for<I, 4>([&](auto bc) __attribute__((always_inline)) {
                     constexpr int b = decltype(bc)::value;
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         acc[tw_ta(I, b)] = __builtin_amdgcn_mfma_f64_16x16x4f64(acc[tw_ta(a, I)][r], acc[tw_ta(a, b)][r], acc[tw_ta(I, b)], 0, 0, 1);
                 });
-                static_for_t<0, a + 1>([&](auto cc) __attribute__((always_inline)) {
+                static_for<0, a + 1>([&](auto cc) __attribute__((always_inline)) {
                     constexpr int c = decltype(cc)::value;
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -893,9 +882,9 @@ __global__ void __launch_bounds__(64, TP_DIAG_OCC) tiled_diag_wave_kernel(const 
         }
     });
     // factored rows back to the arena (upper part; the border column of the last block is y): rows past the last pivot untouched
-    static_for_t<0, 4>([&](auto ac) __attribute__((always_inline)) {
+    static_for<0, 4>([&](auto ac) __attribute__((always_inline)) {
         constexpr int a = decltype(ac)::value;
-        static_for_t<a, 4>([&](auto bc) __attribute__((always_inline)) {
+        static_for<a, 4>([&](auto bc) __attribute__((always_inline)) {
             constexpr int b = decltype(bc)::value;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -906,9 +895,9 @@ __global__ void __launch_bounds__(64, TP_DIAG_OCC) tiled_diag_wave_kernel(const 
     });
     // row-major R_jj^-1 = Y': (R^-1)[i][c] = Y[c][i]; identity in the rows / columns past the last pivot, zero below the diagonal
     double* rinvp = ws.rinv + (wl * ws.NSB + j) * (long long)(SB * SB);
-    static_for_t<0, 4>([&](auto bc) __attribute__((always_inline)) {
+    static_for<0, 4>([&](auto bc) __attribute__((always_inline)) {
         constexpr int b = decltype(bc)::value;
-        static_for_t<0, 4>([&](auto ac) __attribute__((always_inline)) {
+        static_for<0, 4>([&](auto ac) __attribute__((always_inline)) {
             constexpr int a = decltype(ac)::value;
             if constexpr (a <= b) {
 #pragma unroll

@@ -29,44 +29,8 @@
 
 namespace {
 
-// ---- ownership: tile column J belongs to wave w2_owner(J); snake over the columns from the widest (J = NT-1) down
-template <int NT, int NWV>
-constexpr int w2_owner(int J) {
-    const int p = NT - 1 - J, g = p / NWV, i = p % NWV;
-    return (g & 1) ? NWV - 1 - i : i;
-}
-template <int NT, int NWV>
-constexpr int w2_count(int WV) {
-    int n = 0;
-    for (int J = 0; J < NT; ++J)
-        if (w2_owner<NT, NWV>(J) == WV) n += J + 1;
-    return n;
-}
-template <int NT, int NWV>
-constexpr int w2_max_tiles() {
-    int m = 0;
-    for (int w = 0; w < NWV; ++w) m = w2_count<NT, NWV>(w) > m ? w2_count<NT, NWV>(w) : m;
-    return m;
-}
-// slot of tile (I, J) among its owner's tiles (row-major over the owner's tiles); -1 when I > J
-template <int NT, int NWV>
-constexpr int w2_slot(int I, int J) {
-    const int wv = w2_owner<NT, NWV>(J);
-    int n = 0;
-    for (int i = 0; i < NT; ++i)
-        for (int j = i; j < NT; ++j) {
-            if (i == I && j == J) return n;
-            if (w2_owner<NT, NWV>(j) == wv) ++n;
-        }
-    return -1;
-}
-// does wave WV own any tile column J >= I (i.e. does it need the A operand of tile row I in a trailing update)?
-template <int NT, int NWV>
-constexpr bool w2_owns_from(int WV, int I) {
-    for (int J = I; J < NT; ++J)
-        if (w2_owner<NT, NWV>(J) == WV) return true;
-    return false;
-}
+// (ownership of the tile columns - w2_owner, w2_slot, w2_count, w2_owns_from - and the Gram row loop wave_gram with its
+// pin / settle: posterior_wave_impl.h; this kernel is the case NWV = 2 or 4)
 
 // Which instantiations factorise in the data-flow form.  At 11 and 12 tiles per side (39 tiles per wave, seven of them in
 // VGPRs) its extra live values made the register allocator move an accumulator tile between the two register files INSIDE
@@ -106,164 +70,6 @@ struct W2Cfg {
     static constexpr int OFF_SUB = LDS_DOUBLES;                  // general layout: staged rows of the pass (wave_idx_rows)
 };
 constexpr int WAVE2_LDS_LIMIT = 160 * 1024;
-
-template <int T>
-__device__ __forceinline__ void w2_touch1(d4& c) {      // an ordered (volatile) "modification" of one tile, no instruction
-    if constexpr (wave_tile_in_agpr(T)) asm volatile("" : "+a"(c));
-    else asm volatile("" : "+v"(c));
-}
-template <int N>
-__device__ __forceinline__ void w2_pin(d4 (&acc)[N]) {
-    static_for<0, N>([&](auto tc) __attribute__((always_inline)) { wave_pin1<decltype(tc)::value>(acc[decltype(tc)::value]); });
-}
-// end of a pass of inline-assembly MFMAs: 24 wait states once, then every tile is "modified" behind them (asm volatile
-// statements keep their order), so that no use of an accumulator can be scheduled in front of the wait
-template <int N>
-__device__ __forceinline__ void w2_settle(d4 (&acc)[N]) {
-    wave_settle1<0>(acc[0]);
-    static_for<1, N>([&](auto tc) __attribute__((always_inline)) { w2_touch1<decltype(tc)::value>(acc[decltype(tc)::value]); });
-}
-
-// One pass over the rows of a window for wave WV: acc(I, J) += rows[:, I]' rows[:, J] for its own tile columns J.
-// Everything else as wave_gram (posterior_wave_impl.h).
-template <int NT, int NWV, int WV, bool HF, bool LEAN>
-__device__ __forceinline__ void w2_gram(const WRows& src, const long long (&coff)[NT], int k, int lane,
-                                        double (&shift)[NT], double (&w0v)[NT], bool ones, bool lazy_mask,
-                                        d4 (&acc)[w2_count<NT, NWV>(WV)], const int* lds_rows, const double* lds_sub,
-                                        double (&csum)[NT], double& usum) {
-    constexpr int NS = w2_count<NT, NWV>(WV);
-    constexpr int kI = NT - 1;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int kc = k - 16 * kI;
-    const bool cvl = fr < kc;
-    const double border = HF ? ((ones && fr == kc + 1) ? 1.0 : 0.0) : ((fr == kc) ? 1.0 : 0.0);
-    const int nks = (src.count + 3) >> 2;
-    const bool has_sub = !HF && src.sub_row != nullptr;
-
-    int row_pref = 0;
-    double sub_pref = 0.0;
-    auto prefetch = [&](int ks) __attribute__((always_inline)) {
-        int r = 4 * ks + fq;
-        r = r < src.count ? r : src.count - 1;
-        row_pref = lds_rows[r];
-        if (has_sub) sub_pref = lds_sub[r];
-    };
-    if constexpr (!LEAN) prefetch(0);
-    // 32-bit addressing: a wave-uniform 64-bit base (the window's first row; general layout: the panel) + row * (8 ld) +
-    // 8 column, ONE 24-bit multiply-add per operand (the 64-bit row * ld product cost 15 vector instructions per k-step).
-    // The contiguous layout always qualifies (tp_layout_is_lean); the general layout when the panel is below 4 GiB
-    // (tp_kargs_t::panel_off32 / hf_off32 bit 0), else it keeps 64-bit addresses.
-    const char* ub = (const char*)(LEAN ? src.base + src.first * src.ld : src.base);
-    const unsigned ld8 = (unsigned)src.ld * 8u;
-    unsigned c8[NT];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) c8[i] = 8u * (unsigned)coff[i];
-    auto load = [&](double (&v)[NT], double& sub, int ks) __attribute__((always_inline)) {
-        int r = 4 * ks + fq;
-        r = r < src.count ? r : src.count - 1;                      // rows past the end re-read the last row (masked below)
-        if (LEAN || src.off32) {
-            unsigned row;
-            if constexpr (LEAN) row = (unsigned)(r + (r >= src.count0 ? src.jump : 0));
-            else row = (unsigned)row_pref;
-            if constexpr (LEAN) {
-                // ungathered columns: group i sits 128 i bytes behind group 0 (immediate offsets); only the last group clamps
-                const unsigned r0 = __umul24(row, ld8) + c8[0];
-#pragma unroll
-                for (int i = 0; i < NT - 1; ++i) v[i] = *(const double*)(ub + (size_t)r0 + 128 * i);
-                v[NT - 1] = *(const double*)(ub + (size_t)(__umul24(row, ld8) + c8[NT - 1]));
-            } else {
-                const unsigned ro = __umul24(row, ld8);
-#pragma unroll
-                for (int i = 0; i < NT; ++i) v[i] = *(const double*)(ub + (size_t)(ro + c8[i]));
-            }
-        } else {
-            const double* p = src.base + (long long)row_pref * src.ld;
-#pragma unroll
-            for (int i = 0; i < NT; ++i) v[i] = p[coff[i]];
-        }
-        sub = 0.0;
-        if constexpr (!LEAN) {
-            if (has_sub) sub = sub_pref;
-            prefetch(ks + 1);
-        } else {
-            if (has_sub) sub = src.sub_row[r];
-        }
-    };
-    auto step = [&](double (&v)[NT], double sub, int ks, auto maskc) __attribute__((always_inline)) {
-        constexpr bool MASK = decltype(maskc)::value != 0;
-        if (HF) {
-#pragma unroll
-            for (int i = 0; i < NT; ++i) v[i] -= shift[i];
-        } else if (has_sub) {
-#pragma unroll
-            for (int i = 0; i < NT; ++i) v[i] -= sub;                // ref:57
-        }
-        v[kI] = cvl ? v[kI] : border;
-        if (MASK) {
-            const bool rv = 4 * ks + fq < src.count;
-#pragma unroll
-            for (int i = 0; i < NT; ++i) v[i] = rv ? v[i] : 0.0;
-        }
-        if (HF) {
-            double z = 0.0;
-#pragma unroll
-            for (int i = 0; i < NT; ++i) z = fma(v[i], w0v[i], z);
-            z = rowgroup_sum16(z);
-            if (!ones) {
-                // k + 1 = 0 (mod 16): no spare column for the ones of the one-pass centring - the column sums of the
-                // shifted rows (and the sum of u) are kept by vector adds instead: NT + 1 per k-step next to the MFMAs.
-                // Round 2 ran a separate pass for the column MEANS at these sizes (13.8 % of a window's time at k = 191).
-#pragma unroll
-                for (int i = 0; i < NT; ++i) csum[i] += v[i];
-                usum += z;
-            }
-            if (fr == kc) v[kI] = z;                                 // u_r = (y_r - shift).w0
-        }
-        static_for<0, NT>([&](auto Ic) __attribute__((always_inline)) {
-            constexpr int I = decltype(Ic)::value;
-            static_for<I, NT>([&](auto Jc) __attribute__((always_inline)) {
-                constexpr int J = decltype(Jc)::value;
-                if constexpr (w2_owner<NT, NWV>(J) == WV) {
-                    constexpr int t = w2_slot<NT, NWV>(I, J);
-                    wave_mfma_agpr<t>(acc[t], v[I], v[J]);
-                }
-            });
-        });
-    };
-
-    if (nks <= 0) return;
-    double va[NT], vb[NT], vc[NT];
-    double sa = 0.0, sb = 0.0, sc = 0.0;
-    load(va, sa, 0);
-    load(vb, sb, 1);
-    if (HF && lazy_mask) {
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const bool cv = 16 * i + fr < k;
-            shift[i] = cv ? shift[i] : 0.0;
-            w0v[i] = cv ? w0v[i] : 0.0;
-        }
-    }
-    w2_pin<NS>(acc);
-    int ks = 0;
-#pragma nounroll
-    for (; 4 * (ks + 3) <= src.count; ks += 3) {
-        load(vc, sc, ks + 2);
-        step(va, sa, ks, ic<0>{});
-        load(va, sa, ks + 3);
-        step(vb, sb, ks + 1, ic<0>{});
-        load(vb, sb, ks + 4);
-        step(vc, sc, ks + 2, ic<0>{});
-    }
-    if (ks < nks) {
-        if (ks + 2 < nks) load(vc, sc, ks + 2);
-        step(va, sa, ks, ic<1>{});
-        if (ks + 1 < nks) step(vb, sb, ks + 1, ic<1>{});
-        if (ks + 2 < nks) step(vc, sc, ks + 2, ic<1>{});
-    }
-    w2_settle<NS>(acc);
-}
 
 // ---- data-flow synchronisation of the factorisation (flags in LDS instead of workgroup barriers) -------------------------
 // publish: every lane's LDS writes are complete (release fence = s_waitcnt lgkmcnt(0)), then lane 0 raises the flag
@@ -344,7 +150,7 @@ __device__ __forceinline__ void w2_body(const tp_kargs_t& A, double* lds) {
     int* idx_rows_lds = LEAN ? nullptr : (int*)(lds + C::OFF_SUB + wave_idx_rows(A.n_r, A.m, A.strategy == 0));
     d4 acc[NS];
     static_for<0, NS>([&](auto tc) __attribute__((always_inline)) { acc[decltype(tc)::value] = d4{0.0, 0.0, 0.0, 0.0}; });
-    w2_pin<NS>(acc);
+    wave_pin(acc);
 
     if constexpr (WV == 0) {            // identity tile for the pivot chains (published by the barriers of phase C / E)
 #pragma unroll
@@ -373,7 +179,7 @@ __device__ __forceinline__ void w2_body(const tp_kargs_t& A, double* lds) {
         hs.count0 = 0x7fffffff; hs.jump = 0;
         hs.off32 = (A.hf_off32 & 1) != 0;
         // ---- phase A: the shift row of the one-pass centred scatter = the window's first intraday row; every wave for itself
-        const bool ones = kc < 15;        // a spare column k+1 carries ones; otherwise the sums are kept by vector adds (w2_gram)
+        const bool ones = kc < 15;        // a spare column k+1 carries ones; otherwise the sums are kept by vector adds (wave_gram)
         double shift[NT], w0v[NT], csum[NT];
         double usum = 0.0;
         {
@@ -394,7 +200,7 @@ __device__ __forceinline__ void w2_body(const tp_kargs_t& A, double* lds) {
         if (!hs.ridx) { hs.first += 1; hs.count -= 1; }
         else { hs.ridx += 1; hs.count -= 1; }
         if constexpr (!LEAN) w2_stage_rows(hs, tid, C::NTHREADS, idx_rows_lds, idx_sub_lds);
-        w2_gram<NT, NWV, WV, true, LEAN>(hs, coff, k, lane, shift, w0v, ones, true, acc, idx_rows_lds, idx_sub_lds, csum, usum);
+        wave_gram<NT, NWV, WV, true, LEAN>(hs, coff, k, lane, shift, w0v, ones, true, acc, idx_rows_lds, idx_sub_lds, csum, usum);
         hs.count = hf_rows_all;
         TP_MARK(2);
         // ---- phase C: rank-one term of the centring, q0, c, scaling (ref:333, 415-418)
@@ -514,7 +320,7 @@ __device__ __forceinline__ void w2_body(const tp_kargs_t& A, double* lds) {
         if constexpr (!LEAN) w2_stage_rows(ds, tid, C::NTHREADS, idx_rows_lds, idx_sub_lds);
         TP_MARK(32);
         double nosum = 0.0;
-        w2_gram<NT, NWV, WV, false, LEAN>(ds, coff, k, lane, none, none, false, false, acc, idx_rows_lds, idx_sub_lds, none, nosum);
+        wave_gram<NT, NWV, WV, false, LEAN>(ds, coff, k, lane, none, none, false, false, acc, idx_rows_lds, idx_sub_lds, none, nosum);
         TP_MARK(33);
         if (LEAN && shared) {
             // this wave's tiles of the table slot Q_L[b0]: [tile][2][64 lanes][2] doubles (the table numbers the tiles

@@ -20,6 +20,8 @@
 //   * no __syncthreads anywhere.
 // Same arithmetic as the multi-wave kernel per matrix element (same k-step order, same elimination), ref:LINE
 // cites /root/reference/src/portfolio_calculations.py as there.
+#include <utility>
+
 #include "posterior_fused_impl.h"
 
 namespace {
@@ -73,9 +75,64 @@ __device__ __forceinline__ void wave_post_tile(double* P, int k, int fr, int fq,
     }
 }
 
+// ---- ownership: the upper triangle is split by tile COLUMN over the NWV waves of a window.  Tile column J belongs to wave
+// w2_owner(J): snake over the columns from the widest (J = NT-1) down, so that every trailing sub-matrix of the
+// factorisation stays balanced too.  The one-wave kernel is the case NWV = 1: one owner, every tile, numbered as wtile.
+template <int NT, int NWV>
+constexpr int w2_owner(int J) {
+    const int p = NT - 1 - J, g = p / NWV, i = p % NWV;
+    return (g & 1) ? NWV - 1 - i : i;
+}
+template <int NT, int NWV>
+constexpr int w2_count(int WV) {
+    int n = 0;
+    for (int J = 0; J < NT; ++J)
+        if (w2_owner<NT, NWV>(J) == WV) n += J + 1;
+    return n;
+}
+template <int NT, int NWV>
+constexpr int w2_max_tiles() {
+    int m = 0;
+    for (int w = 0; w < NWV; ++w) m = w2_count<NT, NWV>(w) > m ? w2_count<NT, NWV>(w) : m;
+    return m;
+}
+// slot of tile (I, J) among its owner's tiles (row-major over the owner's tiles); -1 when I > J
+template <int NT, int NWV>
+constexpr int w2_slot(int I, int J) {
+    const int wv = w2_owner<NT, NWV>(J);
+    int n = 0;
+    for (int i = 0; i < NT; ++i)
+        for (int j = i; j < NT; ++j) {
+            if (i == I && j == J) return n;
+            if (w2_owner<NT, NWV>(j) == wv) ++n;
+        }
+    return -1;
+}
+// does wave WV own any tile column J >= I (i.e. does it need the A operand of tile row I in a trailing update)?
+template <int NT, int NWV>
+constexpr bool w2_owns_from(int WV, int I) {
+    for (int J = I; J < NT; ++J)
+        if (w2_owner<NT, NWV>(J) == WV) return true;
+    return false;
+}
+// NWV = 1 is the one-wave kernel's numbering, for every tile count built
+template <int NT>
+constexpr bool w2_one_wave_is_whole() {
+    for (int J = 0; J < NT; ++J) {
+        if (w2_owner<NT, 1>(J) != 0) return false;
+        for (int I = 0; I <= J; ++I)
+            if (w2_slot<NT, 1>(I, J) != wtile(NT, I, J)) return false;
+    }
+    return w2_count<NT, 1>(0) == NT * (NT + 1) / 2;
+}
+template <int... N>
+constexpr bool w2_one_wave_is_whole_all(std::integer_sequence<int, N...>) { return (w2_one_wave_is_whole<N + 1>() && ...); }
+static_assert(w2_one_wave_is_whole_all(std::make_integer_sequence<int, 15>{}),
+              "w2_owner<NT,1>(J) == 0, w2_slot<NT,1>(I,J) == wtile(NT,I,J), w2_count<NT,1>(0) == NT(NT+1)/2 for NT = 1..15");
+
 // The MFMAs of the Gram loops are inline assembly, which the compiler's hazard recogniser does not see: a
 // v_mfma_f64_16x16x4 result may be read by anything but the SrcC of the next MFMA on the same registers only 19
-// wait states after issue (what hipcc inserts behind the builtin).  Every pass over rows ends here; the asm
+// wait states after issue (what hipcc inserts behind the builtin).  Every pass over rows ends in a settle; the asm
 // "modifies" every tile, so no later use of an accumulator can be scheduled in front of the wait.
 // Where a tile lives.  The first 32 tiles fill the AGPR half of the register file (256 registers); tile counts of 8 and
 // 9 per side (36 / 45 tiles) keep the rest in VGPRs - MFMA accumulators may be either.
@@ -87,11 +144,6 @@ template <int T>
 __device__ __forceinline__ void wave_mfma_agpr(d4& c, double a, double b) {
     if constexpr (wave_tile_in_agpr(T)) asm volatile("s_nop 1\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
     else asm volatile("s_nop 1\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void wave_settle14(d4& c0, d4& c1, d4& c2, d4& c3, d4& c4, d4& c5, d4& c6, d4& c7, d4& c8, d4& c9,
-                                              d4& c10, d4& c11, d4& c12, d4& c13) {
-    asm volatile("s_nop 15\n\ts_nop 7" : "+a"(c0), "+a"(c1), "+a"(c2), "+a"(c3), "+a"(c4), "+a"(c5), "+a"(c6), "+a"(c7), "+a"(c8),
-                 "+a"(c9), "+a"(c10), "+a"(c11), "+a"(c12), "+a"(c13));
 }
 template <int T>
 __device__ __forceinline__ void wave_settle1(d4& c0) {
@@ -106,24 +158,37 @@ __device__ __forceinline__ void wave_pin1(d4& c0) {
     if constexpr (wave_tile_in_agpr(T)) asm volatile("" : "+a"(c0));
     else asm volatile("" : "+v"(c0));
 }
-template <int NT>
-__device__ __forceinline__ void wave_pin(d4 (&acc)[WCfg<NT>::NTILES]) {
-    static_for<0, WCfg<NT>::NTILES>([&](auto tc) __attribute__((always_inline)) { wave_pin1<decltype(tc)::value>(acc[decltype(tc)::value]); });
+__device__ __forceinline__ void wave_settle14(d4& c0, d4& c1, d4& c2, d4& c3, d4& c4, d4& c5, d4& c6, d4& c7, d4& c8, d4& c9,
+                                              d4& c10, d4& c11, d4& c12, d4& c13) {
+    asm volatile("s_nop 15\n\ts_nop 7" : "+a"(c0), "+a"(c1), "+a"(c2), "+a"(c3), "+a"(c4), "+a"(c5), "+a"(c6), "+a"(c7), "+a"(c8),
+                 "+a"(c9), "+a"(c10), "+a"(c11), "+a"(c12), "+a"(c13));
 }
-template <int NT>
-__device__ __forceinline__ void wave_settle(d4 (&acc)[WCfg<NT>::NTILES]) {
-    constexpr int NTL = WCfg<NT>::NTILES;
-    static_for<0, (NTL + 13) / 14>([&](auto gc) __attribute__((always_inline)) {
-        constexpr int b = 14 * decltype(gc)::value;
-        if constexpr (b + 14 <= NTL && wave_tile_in_agpr(b + 13)) {
-            wave_settle14(acc[b], acc[b + 1], acc[b + 2], acc[b + 3], acc[b + 4], acc[b + 5], acc[b + 6], acc[b + 7], acc[b + 8],
-                          acc[b + 9], acc[b + 10], acc[b + 11], acc[b + 12], acc[b + 13]);
-        } else {
-            static_for<b, (b + 14 < NTL ? b + 14 : NTL)>([&](auto tc) __attribute__((always_inline)) {
-                wave_settle1<decltype(tc)::value>(acc[decltype(tc)::value]);
-            });
-        }
-    });
+// entering a row loop: every loop-carried accumulator as an AGPR (tiles >= 32: VGPR) value - wave_pin1
+template <int N>
+__device__ __forceinline__ void wave_pin(d4 (&acc)[N]) {
+    static_for<0, N>([&](auto tc) __attribute__((always_inline)) { wave_pin1<decltype(tc)::value>(acc[decltype(tc)::value]); });
+}
+// End of a pass of inline-assembly MFMAs.  GROUPED (the one-wave kernel): one wait per group of 14 tiles.  Otherwise (the
+// two- / four-wave kernel): 24 wait states once, then every tile is "modified" behind them (asm volatile statements keep
+// their order).  The two emit different instructions; each kernel keeps the form it was tuned and hazard-checked with.
+template <bool GROUPED, int N>
+__device__ __forceinline__ void wave_settle(d4 (&acc)[N]) {
+    if constexpr (GROUPED) {
+        static_for<0, (N + 13) / 14>([&](auto gc) __attribute__((always_inline)) {
+            constexpr int b = 14 * decltype(gc)::value;
+            if constexpr (b + 14 <= N && wave_tile_in_agpr(b + 13)) {
+                wave_settle14(acc[b], acc[b + 1], acc[b + 2], acc[b + 3], acc[b + 4], acc[b + 5], acc[b + 6], acc[b + 7], acc[b + 8],
+                              acc[b + 9], acc[b + 10], acc[b + 11], acc[b + 12], acc[b + 13]);
+            } else {
+                static_for<b, (b + 14 < N ? b + 14 : N)>([&](auto tc) __attribute__((always_inline)) {
+                    wave_settle1<decltype(tc)::value>(acc[decltype(tc)::value]);
+                });
+            }
+        });
+    } else {
+        wave_settle1<0>(acc[0]);
+        static_for<1, N>([&](auto tc) __attribute__((always_inline)) { wave_pin1<decltype(tc)::value>(acc[decltype(tc)::value]); });
+    }
 }
 
 struct WRows {
@@ -138,7 +203,8 @@ struct WRows {
     bool off32 = false;     // general layout: row * 8 ld + 8 column fits 32 bits for every row of the PANEL (host-checked)
 };
 
-// One pass over the rows of a window: acc(I,J) += rows[:, I]' rows[:, J], 4 rows per k-step.
+// One pass over the rows of a window for wave WV of NWV: acc(I,J) += rows[:, I]' rows[:, J] for the tile columns J it owns,
+// 4 rows per k-step.
 //  HF:   intraday rows, shifted by `shift` (the window's first row, or its column means), column k carries
 //        u_r = (y_r - shift).w0 and - when `ones` - column k+1 carries ones (one-pass centring, phase C)
 //  !HF:  daily rows minus the per-row risk-free adjustment, column k carries ones (t = X'1, ref:222)
@@ -147,10 +213,10 @@ struct WRows {
 //  wave wait for the shift row before it could ask for the first panel rows (two memory round trips in a row, and this
 //  wave has nothing else to run meanwhile)
 //  !LEAN: lds_rows[r] / lds_sub[r] hold the panel row and the subtrahend of row r of this pass (staged by wave_stage_rows)
-template <int NT, bool HF, bool LEAN>
+template <int NT, int NWV, int WV, bool HF, bool LEAN>
 __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&coff)[NT], int k, int lane,
                                           double (&shift)[NT], double (&w0v)[NT], bool ones, bool lazy_mask,
-                                          d4 (&acc)[WCfg<NT>::NTILES], const int* lds_rows, const double* lds_sub,
+                                          d4 (&acc)[w2_count<NT, NWV>(WV)], const int* lds_rows, const double* lds_sub,
                                           double (&csum)[NT], double& usum) {
     constexpr int kI = NT - 1;
     const int fr = lane & 15, fq = lane >> 4;
@@ -160,7 +226,6 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
     const int nks = (src.count + 3) >> 2;
     const bool has_sub = !HF && src.sub_row != nullptr;
 
-    // column offsets (doubles) of this lane in the NT column groups; padding columns re-read column k-1
     // general layout: the pass's panel rows (and subtrahends) come from LDS; the values of the NEXT load are fetched right
     // behind the current load's requests, a whole k-step of MFMAs ahead of their use
     int row_pref = 0;
@@ -236,7 +301,8 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
             if (!ones) {
                 // k + 1 = 0 (mod 16): no spare column for the ones of the one-pass centring - the column sums of the
                 // shifted rows (and the sum of u) are kept by vector adds instead: NT + 1 per k-step next to the MFMAs
-                // (round 2 ran a separate pass for the column MEANS at these sizes: a second dependent trip to memory)
+                // (round 2 ran a separate pass for the column MEANS at these sizes: a second dependent trip to memory,
+                // 13.8 % of a window's time at k = 191)
 #pragma unroll
                 for (int i = 0; i < NT; ++i) csum[i] += v[i];
                 usum += z;
@@ -247,10 +313,12 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
             constexpr int I = decltype(Ic)::value;
             static_for<I, NT>([&](auto Jc) __attribute__((always_inline)) {
                 constexpr int J = decltype(Jc)::value;
-                constexpr int t = wtile(NT, I, J);
-                // accumulators pinned to the AGPR half of the register file: left to itself the allocator moved the
-                // whole accumulator set between VGPRs and AGPRs inside this loop (497 v_accvgpr moves per 84 MFMAs)
-                wave_mfma_agpr<t>(acc[t], v[I], v[J]);
+                if constexpr (w2_owner<NT, NWV>(J) == WV) {
+                    constexpr int t = w2_slot<NT, NWV>(I, J);
+                    // accumulators pinned to the AGPR half of the register file: left to itself the allocator moved the
+                    // whole accumulator set between VGPRs and AGPRs inside this loop (497 v_accvgpr moves per 84 MFMAs)
+                    wave_mfma_agpr<t>(acc[t], v[I], v[J]);
+                }
             });
         });
     };
@@ -271,7 +339,7 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
             w0v[i] = cv ? w0v[i] : 0.0;
         }
     }
-    wave_pin<NT>(acc);
+    wave_pin(acc);
     int ks = 0;
 #pragma nounroll
     for (; 4 * (ks + 3) <= src.count; ks += 3) {
@@ -288,7 +356,7 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
         if (ks + 1 < nks) step(vb, sb, ks + 1, ic<1>{});
         if (ks + 2 < nks) step(vc, sc, ks + 2, ic<1>{});
     }
-    wave_settle<NT>(acc);
+    wave_settle<NWV == 1>(acc);
 }
 
 // General layout: panel row (and subtrahend) of every row of the pass into LDS, 64 rows per instruction.
@@ -301,6 +369,9 @@ __device__ __forceinline__ void wave_stage_rows(const WRows& src, int lane, int*
     __builtin_amdgcn_wave_barrier();
 }
 
+// Phases A-E below are written out here AND in w2_body (posterior_wave2_impl.h) with its ownership filter: each of these
+// pieces, moved into a function of its own, changed the instruction stream of some kernel (DESIGN.md section 4f,
+// profiles/r07_wave_kernels_refactor_isa.txt); they keep this source form until such a change has been timed.
 // MODE 3 / 4: MODE 0 / 1 plus the store of the posterior matrix (tp_batch_keep_posterior) - instantiations of their own, so
 // that the plain modes' code is exactly what it was without the feature.
 // MODE 0: conjugate, 1: Jeffreys - the plain product paths, compiled without the read-back / custom right-hand side /
@@ -359,7 +430,7 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
     static_for<0, C::NTILES>([&](auto tc) __attribute__((always_inline)) { acc[decltype(tc)::value] = d4{0.0, 0.0, 0.0, 0.0}; });
     // AGPR values from the first definition on: where two paths of the kernel meet, the accumulators must arrive as AGPR
     // values on both, or the merge keeps all of them in VGPRs (and spills)
-    wave_pin<NT>(acc);
+    wave_pin(acc);
 
     // identity tile for the pivot chain (read after many waits on this wave's own LDS traffic)
 #pragma unroll
@@ -440,7 +511,7 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
         if (!hs.ridx) { hs.first += 1; hs.count -= 1; }
         else { hs.ridx += 1; hs.count -= 1; }
         if constexpr (!LEAN) wave_stage_rows(hs, lane, idx_rows_lds, idx_sub_lds);      // (WCfg::OFF_SUB)
-        wave_gram<NT, true, LEAN>(hs, coff, k, lane, shift, w0v, ones, true, acc, idx_rows_lds, idx_sub_lds, csum, usum);
+        wave_gram<NT, 1, 0, true, LEAN>(hs, coff, k, lane, shift, w0v, ones, true, acc, idx_rows_lds, idx_sub_lds, csum, usum);
         hs.count = hf_rows_all;
         TP_MARK(2);
         // ---- phase C: rank-one term of the centring (one-pass form); q0, c, scaling (ref:333, 415-418).  ONE pass over
@@ -582,7 +653,7 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
         // (every load of the intraday pass has completed: its staging region is free for the daily pass)
         if constexpr (!LEAN) wave_stage_rows(ds, lane, idx_rows_lds, idx_sub_lds);
         double nosum = 0.0;
-        wave_gram<NT, false, LEAN>(ds, coff, k, lane, none, none, false, false, acc, idx_rows_lds, idx_sub_lds, none, nosum);
+        wave_gram<NT, 1, 0, false, LEAN>(ds, coff, k, lane, none, none, false, false, acc, idx_rows_lds, idx_sub_lds, none, nosum);
         TP_MARK(33);
         if (LEAN && shared) {
             // (issuing the first group in front of the edge rows' loop was measured and dropped: the loop's counted
