@@ -118,7 +118,7 @@ typedef struct tp_inputs {
 const char* tp_version(void);
 /* largest portfolio_spec["size"] the built kernels cover */
 int tp_max_assets(void);
-/* largest k the solve-sweep kernel covers (tp_batch_solve_sweep); at least 143, at most tp_max_assets() */
+/* largest k the sweep kernels cover (tp_batch_solve_sweep, tp_batch_prior_sweep); at least 143, at most tp_max_assets() */
 int tp_sweep_max_assets(void);
 /* number of visible HIP devices (0 when there is none: tp_create will then fail) */
 int tp_device_count(void);
@@ -145,8 +145,9 @@ int tp_destroy(tp_handle_t h);
  *   "hf_share_min_blocks"  large-k path, conjugate: intraday windows that advance by a fixed stride share the Grams of
  *                      their whole stride-long blocks from this many whole blocks per window on (default 6; takes effect
  *                      at the next upload; "no_shared_gram" switches the scheme off)
- *   "sweep_chunk_windows"  windows per sub-range of tp_batch_solve_sweep (0 automatic: as many as 256 MiB of k x k matrices
- *                      hold); results do not depend on it
+ *   "sweep_chunk_windows"  windows per sub-range of tp_batch_solve_sweep and tp_batch_prior_sweep (0 automatic: as many as
+ *                      256 MiB of k x k matrices hold - the prior sweep keeps two per window and never exceeds that);
+ *                      results do not depend on it
  * Replaces nothing in the reference. */
 int tp_set_option(tp_handle_t h, const char* name, int value);
 const char* tp_last_error(tp_handle_t h); /* h may be NULL: last error of a failed tp_create */
@@ -243,6 +244,38 @@ int tp_batch_download_sweep(tp_batch_t b, double* x, int32_t* status);
  * sweep solved for them (tp_batch_download_rhs keeps answering for the last tp_batch_run).  Waits like
  * tp_batch_download_sweep; without a sweep before it: TP_ERR_INVALID. */
 int tp_batch_download_sweep_rhs(tp_batch_t b, double* rhs_out);
+/* Prior sweep: many conjugate priors (n0, w0) per window from ONE pair of Grams - a grid of conjugate specs over the same
+ * rebalancing dates (VIX / EPU x vw / ew x mcm_scaling, ref:247-267, 361-380) without a replica of every window per spec.
+ * With C = sum (y - ybar)(y - ybar)' the centred intraday scatter of window w, T = X'X, t = X'1, m the window's own
+ * intraday row count (hf_count[w] where given) and, for prior p, a = n0_wp m/(m-1):
+ *     S1 = a C + T ;  q0 = a w0_wp'C w0_wp ;  c = 2 n0_wp / (g + sqrt(g^2 + 4 n0_wp q0)),  g = n0_wp + k + 2   (ref:333, 358, 415-418)
+ *     w1 = S1^-1 (c a C w0_wp + t) ;  n1 = n0_wp + N ;  weights[w][p] = (n1 + k + 2) w1 / (n1 - w1'S1 w1) / gamma   (ref:489, 572-575, 836)
+ * i.e. what tp_batch_run returns for the window with (w0_wp, n0_wp) uploaded (not bit for bit: the factorisation differs).
+ * The batch's own uploaded w0 / n0 are not used, nor its tp_batch_set_rhs.  TP_ERR_INVALID: a Jeffreys batch, n_prior < 1,
+ * n0 or w0 NULL, an n0 that is not finite and > 0, a non-finite w0, a batch that was not uploaded.  TP_ERR_UNSUPPORTED:
+ * k > tp_sweep_max_assets() (also: index-layout windows of more than about 10,000 rows).  TP_ERR_HIP: an allocation failed
+ * (the message names the byte count).
+ * How it runs: the windows go through in sub-ranges that hold TWO k x k matrices per window ("sweep_chunk_windows";
+ * default and upper bound: as many as 256 MiB hold).  Per sub-range one Gram pass - one wavefront per window, every row
+ * through the MFMAs, never the shared block sums, so C, T and t depend on the window's rows alone - stores C (unscaled), T
+ * and t; then one workgroup per (window, prior) forms a C + T and C w0 in one pass, factorises in LDS and solves.  A
+ * (window, prior) result does not depend on W, n_prior, the prior's or the window's position or the sub-ranges.  Device
+ * memory: W x n_prior x (2 k + 9) doubles of priors and results, [W x k] of t and the sub-range's matrices; kept until
+ * tp_batch_destroy.
+ * The call copies n0 and w0 to the device (no host pointer is kept) and queues the kernels on the handle's stream without
+ * waiting for THEM.  Like tp_batch_solve_sweep it waits, on entry, for whatever was queued on the handle's stream before it
+ * and for its own two copies.  kernel_ms of tp_last_timing covers Gram passes and solves (one HIP-event pair); between
+ * tp_region_begin and tp_region_end a prior sweep counts as one step of tp_region_steps.  A gather requested by
+ * tp_batch_gather_async is put on its stream at the end of the call, as at the end of a tp_batch_run.  It leaves the batch
+ * alone: its set_rhs / set_shift / keep_rhs / keep_posterior settings stay, tp_batch_download / _rhs / _posterior /
+ * _sweep return what they returned before, and tp_last_launch keeps describing the last tp_batch_run. */
+int tp_batch_prior_sweep(tp_batch_t b, int32_t n_prior, const double* n0 /* [W x n_prior] */,
+                         const double* w0 /* [W x n_prior x k] */);
+/* Waits for the prior sweep and copies out weights [W x n_prior x k], status [W x n_prior] (TP_STATUS_OK, TP_STATUS_NOT_PD:
+ * a pivot <= 0 or no larger than k 2^-52 times its diagonal element of S1, i.e. lost to rounding; TP_STATUS_NONFINITE;
+ * TP_STATUS_BAD_DENOM: n1 - w1'S1 w1 <= 0) and aux [W x n_prior x TP_AUX_STRIDE] (the
+ * slots of tp_batch_download's aux); each may be NULL.  Without a prior sweep before it: TP_ERR_INVALID. */
+int tp_batch_download_prior_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux);
 int tp_batch_download(tp_batch_t b, double* weights /* [W x k] */, int32_t* status /* [W] */,
                       double* aux /* optional [W x TP_AUX_STRIDE] */); /* waits for the stream, D2H */
 int tp_batch_download_S1(tp_batch_t b, int64_t w, double* S1 /* [k x k] */); /* posterior scale matrix

@@ -45,6 +45,7 @@ EXPORTS = [
     "tp_host_alloc", "tp_host_free", "tp_batch_set_rhs", "tp_batch_set_shift", "tp_batch_keep_rhs",
     "tp_batch_download_rhs", "tp_batch_keep_posterior", "tp_batch_download_posterior", "tp_batch_run", "tp_batch_download", "tp_batch_download_S1", "tp_batch_download_matrix",
     "tp_batch_solve_sweep", "tp_batch_download_sweep", "tp_batch_download_sweep_rhs",
+    "tp_batch_prior_sweep", "tp_batch_download_prior_sweep",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
     "tp_comm_count", "tp_comm_init_all", "tp_group_gather",
@@ -112,6 +113,8 @@ def _load():
     lib.tp_batch_solve_sweep.argtypes = [c_void_p, c_int32, POINTER(c_double), c_int32, POINTER(c_double), c_int32]
     lib.tp_batch_download_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32)]
     lib.tp_batch_download_sweep_rhs.argtypes = [c_void_p, POINTER(c_double)]
+    lib.tp_batch_prior_sweep.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
+    lib.tp_batch_download_prior_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download_S1.argtypes = [c_void_p, c_int64, POINTER(c_double)]
     lib.tp_batch_download_matrix.argtypes = [c_void_p, c_int64, c_int, POINTER(c_double), POINTER(c_double)]
@@ -591,6 +594,35 @@ class Batch:
         out = np.empty((self.W, self.k), dtype=np.float64)
         self.dev._check(lib.tp_batch_download_sweep_rhs(self._b, _ptr(out if out.size else None, c_double)))
         return out
+
+    def prior_sweep(self, n0, w0, want_aux=True):
+        """`tp_batch_prior_sweep` + `tp_batch_download_prior_sweep`: the conjugate weights of every window for P priors
+        `n0` [W x P] (> 0), `w0` [W x P x k] from ONE pair of Grams per window.  Returns (weights [W, P, k], status [W, P],
+        aux [W, P, 8] or None).  The batch's own w0 / n0, results, settings and kept arrays are left alone."""
+        W, k = self.W, self.k
+        for name, a in (("n0", n0), ("w0", w0)):
+            if a is None:
+                raise ValueError(f"{name}: an array is expected")
+            if np.asarray(a).dtype.kind not in "fiu":
+                raise ValueError(f"{name}: a real floating-point array is expected, got dtype {np.asarray(a).dtype}")
+        n0 = np.ascontiguousarray(n0, dtype=np.float64)
+        w0 = np.ascontiguousarray(w0, dtype=np.float64)
+        if n0.ndim != 2 or n0.shape[0] != W or n0.shape[1] < 1:
+            raise ValueError(f"n0: expected shape ({W}, P) with P >= 1, got {tuple(n0.shape)}")
+        P = n0.shape[1]
+        if w0.shape != (W, P, k):
+            raise ValueError(f"w0: expected shape ({W}, {P}, {k}), got {tuple(w0.shape)}")
+        weights = np.empty((W, P, k), dtype=np.float64)
+        status = np.empty((W, P), dtype=np.int32)
+        aux = np.empty((W, P, AUX_STRIDE), dtype=np.float64) if want_aux else None
+        # (W = 0: the library still wants non-NULL prior arrays)
+        n0p = n0 if n0.size else np.ones(1)
+        w0p = w0 if w0.size else np.zeros(1)
+        self.dev._check(lib.tp_batch_prior_sweep(self._b, P, _ptr(n0p, c_double), _ptr(w0p, c_double)))
+        self.dev._check(lib.tp_batch_download_prior_sweep(self._b, _ptr(weights if weights.size else None, c_double),
+                                                          _ptr(status if status.size else None, c_int32),
+                                                          _ptr(aux if aux is not None and aux.size else None, c_double)))
+        return weights, status, aux
 
     def download(self, want_aux=True, out=None):
         """(weights, status, aux).  `out=(weights, status[, aux])`: write into these arrays (e.g. `pinned_empty`)."""

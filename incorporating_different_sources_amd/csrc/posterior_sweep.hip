@@ -29,14 +29,9 @@
 // Every (window, shift) is computed by its own workgroup from M_w, the two shift values and the R right-hand sides alone,
 // in an order of operations that depends on k and R only: the result does not depend on W, S, the window's position or
 // the chunking of the host loop.  Workgroup barriers only; nothing spins.
-#include "posterior_device_prims.h"
+#include "posterior_sweep_solve.h"
 
 namespace {
-
-constexpr int SWEEP_THREADS = 256;
-constexpr int SWEEP_TX = 32;            // lanes along a column
-constexpr int SWEEP_XREGS = 3;          // solution registers per lane: k <= 64 * 3
-constexpr int SWEEP_MAX_K = 143;        // 16 x 9 - 1: the one-wave kernels' range; 98.3 KiB of LDS at R = 16
 
 __global__ void __launch_bounds__(SWEEP_THREADS) posterior_sweep_kernel(const tp_sweep_kargs_t A) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -53,12 +48,12 @@ __global__ void __launch_bounds__(SWEEP_THREADS) posterior_sweep_kernel(const tp
         sh_d = A.shift[(w * A.S + s) * 2];
         sh_e = A.shift[(w * A.S + s) * 2 + 1];
     }
-    auto off = [H](int c) { return c * H - (c * (c - 1)) / 2; };
+    auto off = [H](int c) { return sweep_off(c, H); };
 
     // ---- load: column c of the lower triangle = row c of the symmetric M_w from the diagonal on (coalesced), then the
     // R right-hand sides as rows k .. k + R - 1
     const int tx = tid & (SWEEP_TX - 1), ty = tid / SWEEP_TX;
-    constexpr int TY = SWEEP_THREADS / SWEEP_TX;
+    constexpr int TY = SWEEP_TY;
     for (int c = ty; c < k; c += TY) {
         double* col = lds + off(c) - c;
         for (int i = c + tx; i < k; i += SWEEP_TX) col[i] = M[(long long)c * k + i] + sh_e + (i == c ? sh_d : 0.0);
@@ -71,20 +66,8 @@ __global__ void __launch_bounds__(SWEEP_THREADS) posterior_sweep_kernel(const tp
     }
     __syncthreads();
 
-    // ---- factorisation with the right-hand sides riding along
-    bool notpd = false;
-    for (int j = 0; j < k; ++j) {
-        const double* cj = lds + off(j) - j;          // cj[i] = A[i][j]
-        const double dj = cj[j];
-        if (dj <= 0.0) notpd = true;                   // (a NaN pivot is not "<= 0": it ends as NONFINITE)
-        const double inv = 1.0 / dj;
-        for (int c = j + 1 + ty; c < k; c += TY) {
-            const double m = cj[c] * inv;
-            double* cc = lds + off(c) - c;
-            for (int i = c + tx; i < H; i += SWEEP_TX) cc[i] -= cj[i] * m;
-        }
-        __syncthreads();
-    }
+    // ---- factorisation with the right-hand sides riding along (posterior_sweep_solve.h)
+    const bool notpd = sweep_ldl_factor(lds, k, H, tid);          // (a NaN pivot is not "<= 0": it ends as NONFINITE)
 
     // ---- back substitution, one wavefront per right-hand side
     const int lane = tid & 63, wv = tid >> 6;
@@ -93,21 +76,7 @@ __global__ void __launch_bounds__(SWEEP_THREADS) posterior_sweep_kernel(const tp
     bool bad = false;
     for (int r = wv; r < R; r += NWV) {
         double x[SWEEP_XREGS];
-#pragma unroll
-        for (int q = 0; q < SWEEP_XREGS; ++q) x[q] = 0.0;
-        for (int j = k - 1; j >= 0; --j) {
-            const double* cj = lds + off(j) - j;
-            double part = 0.0;
-#pragma unroll
-            for (int q = 0; q < SWEEP_XREGS; ++q) {
-                const int i = lane + 64 * q;
-                if (i > j && i < k) part += cj[i] * x[q];
-            }
-            const double xj = (cj[k + r] - wave_sum64(part)) / cj[j];
-#pragma unroll
-            for (int q = 0; q < SWEEP_XREGS; ++q)
-                if (lane + 64 * q == j) x[q] = xj;
-        }
+        sweep_back_substitute(lds, k, H, r, lane, x);
         double* out = A.x + (((w * A.S + s) * R + r) * (long long)k);
 #pragma unroll
         for (int q = 0; q < SWEEP_XREGS; ++q) {

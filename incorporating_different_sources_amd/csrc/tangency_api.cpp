@@ -799,6 +799,110 @@ int tp_batch_download_sweep_rhs(tp_batch_t b, double* rhs_out) {
     return download(h, {{rhs_out, b->sw_rhs0.p, sizeof(double) * (size_t)b->W * b->p.k}});
 }
 
+// Prior sweep.  Windows go through in sub-ranges of `chunk` windows: the Gram pass (posterior_gram_nt.hip) stores C and T of
+// a sub-range - two k x k matrices per window inside TP_SWEEP_WORKSPACE_BYTES - and t, then posterior_prior_sweep_kernel
+// solves the sub-range's (window, prior) pairs; never more than 2^30 pairs per launch.
+int tp_batch_prior_sweep(tp_batch_t b, int32_t n_prior, const double* n0, const double* w0) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    const int k = b->p.k;
+    const int64_t W = b->W;
+    if (b->p.strategy != TP_STRATEGY_CONJUGATE)
+        return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep applies to the conjugate strategy only");
+    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep before tp_batch_upload");
+    if (n_prior < 1) return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep: n_prior=%d < 1", n_prior);
+    if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep: %s is NULL", !n0 ? "n0" : "w0");
+    const int P = n_prior;
+    for (int64_t i = 0; i < W * P; ++i)
+        if (!(n0[i] > 0.0) || !std::isfinite(n0[i]))
+            return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep: n0[%lld] must be finite and > 0", (long long)i);
+    for (int64_t i = 0; i < W * P * k; ++i)
+        if (!std::isfinite(w0[i])) return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep: w0[%lld] must be finite", (long long)i);
+    if (k > tp_sweep_max_assets())
+        return fail(h, TP_ERR_UNSUPPORTED, "tp_batch_prior_sweep: k=%d exceeds the sweep kernel's largest universe %d", k,
+                    tp_sweep_max_assets());
+    int rc = begin_launches(b);
+    if (rc != TP_OK) return rc;
+    // like tp_batch_solve_sweep the call drains the handle's stream here: an earlier sweep may still read the buffers about
+    // to be reallocated or refilled, and the kernel span may still be waiting to be read
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    rc = harvest_kernel_time(h);
+    if (rc != TP_OK) return rc;
+    b->ps_P = 0;
+    if (W == 0) { b->ps_P = P; return TP_OK; }
+    // windows per sub-range: C and T
+    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
+    int64_t chunk = h->sweep_chunk_windows > 0 ? h->sweep_chunk_windows : (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes));
+    if (chunk > (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes))) chunk = (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes));
+    if (chunk > (1ll << 30) / P) chunk = (1ll << 30) / P;
+    if (chunk < 1) chunk = 1;
+    if (chunk > W) chunk = W;
+    const size_t WP = (size_t)W * (size_t)P;
+    rc = ensure(h, b->ps_C, mat_bytes * (size_t)chunk, "tp_batch_prior_sweep: intraday scatters of one sub-range");
+    if (rc == TP_OK) rc = ensure(h, b->ps_T, mat_bytes * (size_t)chunk, "tp_batch_prior_sweep: daily Grams of one sub-range");
+    if (rc == TP_OK) rc = ensure(h, b->ps_t, sizeof(double) * (size_t)W * k, "tp_batch_prior_sweep: daily column sums");
+    if (rc == TP_OK) rc = ensure(h, b->ps_n0, sizeof(double) * WP, "tp_batch_prior_sweep: prior strengths");
+    if (rc == TP_OK) rc = ensure(h, b->ps_w0, sizeof(double) * WP * k, "tp_batch_prior_sweep: prior weights");
+    if (rc == TP_OK) rc = ensure(h, b->ps_weights, sizeof(double) * WP * k, "tp_batch_prior_sweep: weights");
+    if (rc == TP_OK) rc = ensure(h, b->ps_status, sizeof(int32_t) * WP, "tp_batch_prior_sweep: statuses");
+    if (rc == TP_OK) rc = ensure(h, b->ps_aux, sizeof(double) * WP * TP_AUX_STRIDE, "tp_batch_prior_sweep: aux");
+    if (rc != TP_OK) return rc;
+    // the caller's arrays: copied here, no host pointer is kept
+    HIP_TRY(h, hipMemcpyAsync(b->ps_n0.p, n0, sizeof(double) * WP, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(b->ps_w0.p, w0, sizeof(double) * WP * k, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
+
+    // Gram pass: the windows' rows as a plain run reads them; no prior, no shared block sums, none of the run's outputs
+    tp_gram_kargs_t ga;
+    memset(&ga, 0, sizeof ga);
+    ga.in = make_kargs(b);
+    ga.in.w0 = nullptr; ga.in.n0 = nullptr;
+    ga.in.rhs = nullptr; ga.in.shift = nullptr;
+    ga.in.prefix = nullptr; ga.in.winsum = nullptr; ga.in.prefix_nblk = 0;
+    for (int i = 0; i < 4; ++i) ga.in.winsum_L[i] = 0;
+    ga.in.weights = nullptr; ga.in.status = nullptr; ga.in.aux = nullptr;
+    ga.in.out_rhs = nullptr; ga.in.out_post = nullptr; ga.in.post_count = 0; ga.in.stamps = nullptr;
+    ga.C = (double*)b->ps_C.p; ga.T = (double*)b->ps_T.p; ga.t = (double*)b->ps_t.p;
+    tp_prior_sweep_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.C = (const double*)b->ps_C.p; sa.T = (const double*)b->ps_T.p; sa.t = (const double*)b->ps_t.p;
+    sa.n0 = (const double*)b->ps_n0.p; sa.w0 = (const double*)b->ps_w0.p;
+    sa.hf_count = (const int*)b->hf_count.p;
+    sa.weights = (double*)b->ps_weights.p; sa.status = (int*)b->ps_status.p; sa.aux = (double*)b->ps_aux.p;
+    sa.k = k; sa.P = P; sa.N = b->p.N; sa.m = b->p.m;
+    sa.gamma = b->p.gamma;
+    // one span around all launches: a sweep is one step of tp_region_steps, kernel_ms = Gram passes + solves
+    // (tp_last_launch keeps describing tp_batch_run launches: nothing here writes it)
+    Span& span = timed_span(h);
+    HIP_TRY(h, span.begin(h->stream));
+    for (int64_t w0i = 0; w0i < W; w0i += chunk) {
+        const int64_t n = W - w0i < chunk ? W - w0i : chunk;
+        ga.in.w_first = w0i; ga.in.w_count = n;
+        hipError_t e = tp_gram_launch(ga, h->stream);
+        if (e == hipErrorNotSupported)
+            return fail(h, TP_ERR_UNSUPPORTED, "tp_batch_prior_sweep: windows of %d daily / %d intraday rows in the index layout are "
+                                               "too long for the Gram pass", b->p.n_r, b->p.m);
+        if (e != hipSuccess) return fail(h, TP_ERR_HIP, "prior sweep Gram launch failed: %s", hipGetErrorString(e));
+        sa.w_first = w0i; sa.w_count = n;
+        e = tp_prior_sweep_launch(sa, h->stream);
+        if (e != hipSuccess) return fail(h, TP_ERR_HIP, "prior sweep kernel launch failed: %s", hipGetErrorString(e));
+    }
+    rc = timed_done(h, span);
+    if (rc != TP_OK) return rc;
+    b->ps_P = P;
+    return end_launches(b);                            // (the sweep reads the batch's inputs and writes none of its results)
+}
+
+int tp_batch_download_prior_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    if (b->ps_P < 1) return fail(h, TP_ERR_INVALID, "tp_batch_download_prior_sweep: no tp_batch_prior_sweep before it");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)b->W * b->ps_P;           // (W = 0: nothing to copy)
+    return download(h, {{weights, b->ps_weights.p, sizeof(double) * n * b->p.k}, {status, b->ps_status.p, sizeof(int32_t) * n},
+                        {aux, b->ps_aux.p, sizeof(double) * n * TP_AUX_STRIDE}});
+}
+
 int tp_synchronize(tp_handle_t h) {
     if (!h) return TP_ERR_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));

@@ -12,6 +12,7 @@
 #include "../../include/tangency_posterior.h"
 #include "host_resources.h"
 #include "posterior_kernels.h"
+#include "posterior_prior_sweep.h"
 
 #define TP_MAX_LANES 4
 #define TP_REGION_MAX_STEPS 512
@@ -46,7 +47,7 @@ struct tp_handle_s {
     int tiled_arena_gib = 0;        // TP_TILED_ARENA_GIB / "tiled_arena_gib" (0: default)
     int tiled_arena_mib = 0;        // TP_TILED_ARENA_MIB / "tiled_arena_mib": a sub-GiB arena per lane (depth-first sub-batches)
     int tiled_lanes = 0;            // TP_TILED_LANES / "tiled_lanes": sub-batches in flight on streams of their own (0: default)
-    int sweep_chunk_windows = 0;    // "sweep_chunk_windows": windows per sub-range of tp_batch_solve_sweep (0: automatic)
+    int sweep_chunk_windows = 0;    // "sweep_chunk_windows": windows per sub-range of tp_batch_solve_sweep / _prior_sweep (0: automatic)
     Stream lane_stream[TP_MAX_LANES];
     Event lane_done[TP_MAX_LANES];
     Event lane_start;
@@ -75,6 +76,9 @@ struct tp_batch_s {
     // kept right-hand sides alone.  sw_post holds the matrices of ONE sub-range of windows at a time
     DevBuf sw_weights, sw_status, sw_aux, sw_rhs0, sw_post, sw_shift, sw_rhs, sw_x, sw_xstatus;
     int sw_S = 0, sw_R = 0;                                   // shape of the last sweep (0: none yet)
+    // prior sweep (tp_batch_prior_sweep): buffers of its own as well.  ps_C / ps_T hold the two Grams of ONE sub-range at a time
+    DevBuf ps_C, ps_T, ps_t, ps_n0, ps_w0, ps_weights, ps_status, ps_aux;
+    int ps_P = 0;                                             // priors per window of the last prior sweep (0: none yet)
     PriceStaging fe, fe_hf;                                   // daily and intraday (freed after a synchronous upload)
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)

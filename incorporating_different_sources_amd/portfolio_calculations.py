@@ -927,13 +927,32 @@ def _batch_family(portfolio_spec):
     return tuple(portfolio_spec.get(name) for name in ("size", "rebalancing_frequency", "rolling_window", "rolling_window_frequency"))
 
 
-def calculate_weights_for_specs(trading_dates, portfolio_specs_list, market_data):
+def _prior_sweep_weights(k, N, gamma, kw, n0, w0):
+    """One upload of the windows in `kw` and ONE prior sweep (`Batch.prior_sweep`): weights [W x P x k], status [W x P]
+    for the priors n0 [W x P], w0 [W x P x k]."""
+    dev = _native.default_device()
+    W = len(kw["n_rows"]) if kw.get("n_rows") is not None else len(kw["start"])
+    upload = {key: val for key, val in kw.items() if key not in ("n_r", "m")}
+    b = _native.Batch(dev, "conjugate", k, N, kw["n_r"], gamma, W, kw.get("m") or 0)
+    try:
+        b.upload(**upload)
+        weights, status, _ = b.prior_sweep(n0, w0, want_aux=False)
+    finally:
+        b.close()
+    return weights, status
+
+
+def calculate_weights_for_specs(trading_dates, portfolio_specs_list, market_data, share_grams=False):
     """Weights of SEVERAL conjugate specs of one grid for the same dates with ONE host pack, ONE upload of the
     panels and ONE device batch of len(specs) x len(dates) windows ("vectorised over days
     and over specs"): the specs share the windows (rows, columns, risk-free adjustment, intraday rows) and differ in
     the prior only - w0 (vw / ew, ref:361-380), n0 (VIX / EPU, mcm_scaling, ref:247-267) and gamma.  Returns one
     (weights, labels, cols, caps) per spec, bit-identical to `_weights_for_dates` spec by spec (windows are
-    independent), and remembers them for the `backtest_portfolio` calls that follow."""
+    independent), and remembers them for the `backtest_portfolio` calls that follow.
+
+    `share_grams=True`: the windows are uploaded ONCE (no replica per spec) and one prior sweep (`Batch.prior_sweep`) forms
+    every window's two Grams once and solves the len(specs) priors from them; same results within the solve's rounding,
+    same cache slots.  Sizes above `_native.sweep_max_assets()` run the replicated batch."""
     specs = list(portfolio_specs_list)
     if not specs:
         return []
@@ -947,22 +966,39 @@ def calculate_weights_for_specs(trading_dates, portfolio_specs_list, market_data
     k, N = first["size"], first["rolling_window"]
     gammas = [sp["risk_aversion"] for sp in specs]
     same_gamma = all(g == gammas[0] for g in gammas)
+    priors = [(kw["w0"], kw["n0"])] + [batch.prior_inputs(trading_dates, sp, market_data, caps) for sp in specs[1:]]
+    if share_grams and k <= _native.sweep_max_assets():
+        weights, status = _prior_sweep_weights(k, N, gammas[0] if same_gamma else 1.0, kw,
+                                               np.stack([p[1] for p in priors], axis=1), np.stack([p[0] for p in priors], axis=1))
+        _raise_on_status(status.reshape(-1))
+        weights = np.ascontiguousarray(weights.transpose(1, 0, 2)).reshape(n_specs * n_dates, k)
+    else:
+        weights = _replicated_weights(kw, priors, n_specs, k, N, gammas[0] if same_gamma else 1.0)
+    return _fill_spec_cache(specs, trading_dates, market_data, weights, n_dates, same_gamma, labels, kw["col_idx"], caps)
+
+
+def _replicated_weights(kw, priors, n_specs, k, N, gamma):
+    """Every window once per spec in ONE device batch of n_specs x n_dates windows."""
     per_window = ("row_idx", "n_rows", "col_idx", "rf_adj", "hf_row_idx", "hf_count")
     big = {key: (np.concatenate([val] * n_specs, axis=0) if key in per_window and val is not None else val)
            for key, val in kw.items()}
-    priors = [(kw["w0"], kw["n0"])] + [batch.prior_inputs(trading_dates, sp, market_data, caps) for sp in specs[1:]]
     big["w0"] = np.concatenate([p[0] for p in priors], axis=0)
     big["n0"] = np.concatenate([p[1] for p in priors], axis=0)
     # 1/gamma is the last factor of ref:836: with different risk aversions in one batch the device runs with
     # gamma = 1 and the same multiplication happens here (same rounding: (1/gamma) * x in both places)
-    weights, status, _ = _device_posterior_batch("conjugate", k, N, gammas[0] if same_gamma else 1.0, big)
+    weights, status, _ = _device_posterior_batch("conjugate", k, N, gamma, big)
     _raise_on_status(status)
+    return weights
+
+
+def _fill_spec_cache(specs, trading_dates, market_data, weights, n_dates, same_gamma, labels, cols, caps):
+    """Cut the [n_specs * n_dates x k] weights into one result per spec and remember each in its cache slot."""
     out = []
     for i, sp in enumerate(specs):
         w = weights[i * n_dates:(i + 1) * n_dates]
         if not same_gamma:
             w = 1.0 / sp["risk_aversion"] * w
-        res = (w, labels, kw["col_idx"], caps)
+        res = (w, labels, cols, caps)
         cache, key, owners = _cache_slot(sp, trading_dates, market_data)
         if len(cache) > 64:
             cache.clear()
