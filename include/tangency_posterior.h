@@ -271,10 +271,33 @@ int tp_batch_download_sweep_rhs(tp_batch_t b, double* rhs_out);
  * _sweep return what they returned before, and tp_last_launch keeps describing the last tp_batch_run. */
 int tp_batch_prior_sweep(tp_batch_t b, int32_t n_prior, const double* n0 /* [W x n_prior] */,
                          const double* w0 /* [W x n_prior x k] */);
+/* Prior sweep for k > tp_sweep_max_assets() (up to tp_max_assets()): the same definition, arguments, validation and result
+ * buffers as tp_batch_prior_sweep - download with tp_batch_download_prior_sweep - on the large-k tiled pipeline.
+ * TP_ERR_UNSUPPORTED: k <= tp_sweep_max_assets() (tp_batch_prior_sweep serves those sizes).
+ * How it runs: per sub-range of windows ("sweep_chunk_windows"; two k x k matrices per window inside 256 MiB, at least one
+ * window) the batch's own tiled Gram kernels run twice, steered by their arguments - over the daily rows for T = X'X and
+ * t = X'1, over the intraday rows for C - never with the shared block sums.  Then every (window, prior) pair takes one slot
+ * of the batch's tiled workspace ("tiled_arena_gib" / "tiled_arena_mib"), in groups of as many pairs as it holds windows: one
+ * pass forms a C + T, t and the pieces of a C w0 from the two stored matrices, a second one q0, c and the right-hand side, and
+ * the tiled factorisation and solve of tp_batch_run do the rest.  A (window, prior) result depends on the window's rows, its
+ * own prior and k only - not on W, n_prior, the positions, the sub-ranges or the size of the workspace.
+ * CENTRING: C = Y'Y - (Y'1)(Y'1)'/m is centred through the RAW moments, not through a row of the window as the scatter of
+ * tp_batch_run and tp_batch_prior_sweep is.  For returns - a mean far below the spread - the two agree to rounding; under a
+ * large common offset of the intraday panel (|mean| >> spread) the raw-moment form loses the digits the offset takes.
+ * Statuses are those of tp_batch_run on the large-k path: TP_STATUS_NOT_PD is a pivot that is not > 0 (no relative floor).
+ * Streams, timing (one step of tp_region_steps, one kernel_ms), the gather hand-over and what the call leaves alone are as
+ * for tp_batch_prior_sweep; it waits, on entry, for whatever was queued on the handle's stream.  Device memory: that of
+ * tp_batch_prior_sweep plus the batch's tiled workspace and 64 NS^2 doubles per slot of it (NS = ceil((k+1)/64)).  The call
+ * GROWS that workspace to min(W, sub-range) x n_prior slots where the arena budget allows - n_prior times what tp_batch_run
+ * alone needs for those windows (k = 500, W = 256, n_prior = 16: about 10 GB against 0.6 GB) - and it stays that large, also
+ * for later tp_batch_run calls, until tp_batch_destroy; "tiled_arena_gib" / "tiled_arena_mib" cap it. */
+int tp_batch_prior_sweep_tiled(tp_batch_t b, int32_t n_prior, const double* n0 /* [W x n_prior] */,
+                               const double* w0 /* [W x n_prior x k] */);
 /* Waits for the prior sweep and copies out weights [W x n_prior x k], status [W x n_prior] (TP_STATUS_OK, TP_STATUS_NOT_PD:
  * a pivot <= 0 or no larger than k 2^-52 times its diagonal element of S1, i.e. lost to rounding; TP_STATUS_NONFINITE;
  * TP_STATUS_BAD_DENOM: n1 - w1'S1 w1 <= 0) and aux [W x n_prior x TP_AUX_STRIDE] (the
- * slots of tp_batch_download's aux); each may be NULL.  Without a prior sweep before it: TP_ERR_INVALID. */
+ * slots of tp_batch_download's aux); each may be NULL.  Without a prior sweep (of either kind) before it:
+ * TP_ERR_INVALID. */
 int tp_batch_download_prior_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux);
 int tp_batch_download(tp_batch_t b, double* weights /* [W x k] */, int32_t* status /* [W] */,
                       double* aux /* optional [W x TP_AUX_STRIDE] */); /* waits for the stream, D2H */

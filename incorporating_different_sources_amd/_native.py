@@ -45,7 +45,7 @@ EXPORTS = [
     "tp_host_alloc", "tp_host_free", "tp_batch_set_rhs", "tp_batch_set_shift", "tp_batch_keep_rhs",
     "tp_batch_download_rhs", "tp_batch_keep_posterior", "tp_batch_download_posterior", "tp_batch_run", "tp_batch_download", "tp_batch_download_S1", "tp_batch_download_matrix",
     "tp_batch_solve_sweep", "tp_batch_download_sweep", "tp_batch_download_sweep_rhs",
-    "tp_batch_prior_sweep", "tp_batch_download_prior_sweep",
+    "tp_batch_prior_sweep", "tp_batch_prior_sweep_tiled", "tp_batch_download_prior_sweep",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
     "tp_comm_count", "tp_comm_init_all", "tp_group_gather",
@@ -114,6 +114,7 @@ def _load():
     lib.tp_batch_download_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32)]
     lib.tp_batch_download_sweep_rhs.argtypes = [c_void_p, POINTER(c_double)]
     lib.tp_batch_prior_sweep.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
+    lib.tp_batch_prior_sweep_tiled.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     lib.tp_batch_download_prior_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download_S1.argtypes = [c_void_p, c_int64, POINTER(c_double)]
@@ -599,6 +600,15 @@ class Batch:
         """`tp_batch_prior_sweep` + `tp_batch_download_prior_sweep`: the conjugate weights of every window for P priors
         `n0` [W x P] (> 0), `w0` [W x P x k] from ONE pair of Grams per window.  Returns (weights [W, P, k], status [W, P],
         aux [W, P, 8] or None).  The batch's own w0 / n0, results, settings and kept arrays are left alone."""
+        return self._prior_sweep(lib.tp_batch_prior_sweep, n0, w0, want_aux)
+
+    def prior_sweep_tiled(self, n0, w0, want_aux=True):
+        """`tp_batch_prior_sweep_tiled` + `tp_batch_download_prior_sweep`: `prior_sweep` for k above `sweep_max_assets()`,
+        factorised by the large-k tiled pipeline (smaller k: TP_ERR_UNSUPPORTED).  The intraday scatter is centred through
+        the raw moments: meant for returns, not for panels with a large common offset."""
+        return self._prior_sweep(lib.tp_batch_prior_sweep_tiled, n0, w0, want_aux)
+
+    def _prior_sweep(self, call, n0, w0, want_aux):
         W, k = self.W, self.k
         for name, a in (("n0", n0), ("w0", w0)):
             if a is None:
@@ -618,7 +628,7 @@ class Batch:
         # (W = 0: the library still wants non-NULL prior arrays)
         n0p = n0 if n0.size else np.ones(1)
         w0p = w0 if w0.size else np.zeros(1)
-        self.dev._check(lib.tp_batch_prior_sweep(self._b, P, _ptr(n0p, c_double), _ptr(w0p, c_double)))
+        self.dev._check(call(self._b, P, _ptr(n0p, c_double), _ptr(w0p, c_double)))
         self.dev._check(lib.tp_batch_download_prior_sweep(self._b, _ptr(weights if weights.size else None, c_double),
                                                           _ptr(status if status.size else None, c_int32),
                                                           _ptr(aux if aux is not None and aux.size else None, c_double)))

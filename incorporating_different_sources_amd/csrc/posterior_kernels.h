@@ -161,6 +161,10 @@ int tp_tiled_max_assets(void);
 void tp_tiled_geometry(int k, int* KP, int* NS, int* NSB);
 hipError_t tp_tiled_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream, bool build_prefix);
 hipError_t tp_tiled_prefix_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream);
+// the two halves of tp_tiled_launch: the Gram stage leaves the bordered matrices in the arena (and stores out_rhs / out_post);
+// the factor stage factorises and solves whatever a.w_count matrices the arena holds (entry e -> output slot a.w_first + e)
+hipError_t tp_tiled_gram_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream, bool build_prefix);
+hipError_t tp_tiled_factor_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream);
 // bytes of the shared block Grams + n_L block-window tables of the daily panel in the tiled layout (16-row blocks)
 size_t tp_tiled_prefix_bytes(int k, long long panel_rows, int n_L, int* nblk_out);
 size_t tp_tiled_slot_doubles(int k);

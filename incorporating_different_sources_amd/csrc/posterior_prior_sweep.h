@@ -35,3 +35,21 @@ struct tp_prior_sweep_kargs_t {
 };
 size_t tp_prior_sweep_lds_bytes(int k);
 hipError_t tp_prior_sweep_launch(const tp_prior_sweep_kargs_t& a, hipStream_t stream);
+
+// prior sweep on the large-k tiled path (posterior_prior_sweep_tiled.hip, tp_batch_prior_sweep_tiled): fills e_count arena
+// entries - entry e is the (window, prior) pair with the flat index e_first + e = w P + p - with a C + T, the border column
+// c a C w0 + t, ws.scal and ws.flags, as tiled_clear_kernel leaves a conjugate window; tp_tiled_factor_launch takes it from
+// there.  C and T are those of the windows [wc_first, ..) of the sub-range (symmetric, full storage); t, n0, w0 and hf_count
+// are indexed by the numbers in the batch.  Uses ws.arena, ws.part [e_count][NS][NS][64], ws.ybar (scratch), ws.scal, ws.flags.
+struct tp_prior_sweep_tiled_kargs_t {
+    const double* C;            // [windows of the sub-range x k x k]
+    const double* T;            // [windows of the sub-range x k x k]
+    const double* t;            // [W x k]
+    const double* n0;           // [W x P]
+    const double* w0;           // [W x P x k]
+    const int* hf_count;        // optional [W]: intraday rows of the window (else m)
+    long long e_first, e_count; // e_count <= the workspace's capacity
+    long long wc_first;         // first window of the sub-range
+    int k, P, m;
+};
+hipError_t tp_prior_sweep_tiled_launch(const tp_prior_sweep_tiled_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream);

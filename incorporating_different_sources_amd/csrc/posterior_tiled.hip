@@ -937,7 +937,6 @@ __global__ void __launch_bounds__(NTHREADS) tile64_syrk_trsm_kernel(const tp_kar
 
 #include "posterior_tiled_wave.h"
 
-// Whole pipeline for windows [a.w_first, a.w_first + a.w_count) (a.w_count <= ws capacity), on `stream`.
 size_t tp_tiled_slot_doubles(int k) {
     int KP, NS, NSB;
     tp_tiled_geometry(k, &KP, &NS, &NSB);
@@ -964,11 +963,14 @@ hipError_t tp_tiled_prefix_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, 
                                  stream, a.prefix_blk0);
 }
 
-hipError_t tp_tiled_launch(const tp_kargs_t& a_in, const tp_tiled_ws_t& ws, hipStream_t stream, bool build_prefix) {
+// Gram stage: everything up to the point where the arena holds the bordered matrix of every window of the sub-batch (border
+// rows cleared, flags zeroed, kept right-hand sides and matrices stored).  A run goes on with tp_tiled_factor_launch; the
+// large-k prior sweep (posterior_prior_sweep_tiled.hip) stops here and takes T, t and C from the kept arrays.
+hipError_t tp_tiled_gram_launch(const tp_kargs_t& a_in, const tp_tiled_ws_t& ws, hipStream_t stream, bool build_prefix) {
     tp_kargs_t a = a_in;
     const int G = (int)a.w_count;
     if (G <= 0) return hipSuccess;
-    const int NS = ws.NS, NSB = ws.NSB;
+    const int NS = ws.NS;
     const bool conj = a.strategy == 0;
     // 32-bit offsets for both panels in the layout they come in (explicit rows: bit 0, contiguous: bit 1)?
     const bool lean = (a.panel_off32 & (a.row_idx ? 1 : 2)) && (!conj || (a.hf_off32 & (a.hf_row_idx ? 1 : 2)));
@@ -1010,6 +1012,18 @@ hipError_t tp_tiled_launch(const tp_kargs_t& a_in, const tp_tiled_ws_t& ws, hipS
     hipLaunchKernelGGL(tiled_clear_kernel, dim3(G), dim3(NTHREADS), 0, stream, a, ws);
     if (a.out_post != nullptr && a.w_first < a.post_w0 + a.post_count && a.w_first + G > a.post_w0)
         hipLaunchKernelGGL(tiled_post_kernel, xcd_grid(NS * (NS + 1) / 2, G), dim3(NTHREADS), 0, stream, a, ws);
+    return hipGetLastError();
+}
+
+// Factorisation and solve of the a.w_count bordered matrices in the arena (entry e is window a.w_first + e of the output
+// arrays), whoever filled it.  Of the arguments the block steps read k, w_count and (on the host) opts; tile64_kernel also
+// forms addresses from w_first, col_idx and m that only its Gram mode dereferences.  tiled_solve_kernel reads strategy, N,
+// gamma, w_first, weights, status, aux, ws.scal[8 e + 2..4] = (c, q0, n0) and ws.flags.
+hipError_t tp_tiled_factor_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream) {
+    const int G = (int)a.w_count;
+    if (G <= 0) return hipSuccess;
+    const int NS = ws.NS, NSB = ws.NSB;
+    const bool use_wave = a.opts.tiled_wave != 0;
     // Left-looking blocked Cholesky: block row j first receives the updates of ALL earlier block rows in one
     // pass (every arena tile is read and written once per factorisation, not once per block step), then its
     // diagonal block is factorised and the rest of the row is solved.
@@ -1037,4 +1051,11 @@ hipError_t tp_tiled_launch(const tp_kargs_t& a_in, const tp_tiled_ws_t& ws, hipS
     const size_t smem = sizeof(double) * (size_t)(ws.KP + SB);
     hipLaunchKernelGGL(tiled_solve_kernel, dim3(G), dim3(NTHREADS), smem, stream, a, ws);
     return hipGetLastError();
+}
+
+// Whole pipeline for windows [a.w_first, a.w_first + a.w_count) (a.w_count <= ws capacity), on `stream`.
+hipError_t tp_tiled_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream, bool build_prefix) {
+    if (a.w_count <= 0) return hipSuccess;
+    const hipError_t e = tp_tiled_gram_launch(a, ws, stream, build_prefix);
+    return e != hipSuccess ? e : tp_tiled_factor_launch(a, ws, stream);
 }

@@ -799,6 +799,64 @@ int tp_batch_download_sweep_rhs(tp_batch_t b, double* rhs_out) {
     return download(h, {{rhs_out, b->sw_rhs0.p, sizeof(double) * (size_t)b->W * b->p.k}});
 }
 
+// What the two prior sweeps share - tp_batch_prior_sweep (`tiled` = false, k <= tp_sweep_max_assets()) and
+// tp_batch_prior_sweep_tiled (above it): the argument checks, the drain of the handle's stream, the windows per sub-range (C and
+// T: two k x k matrices per window inside TP_SWEEP_WORKSPACE_BYTES, never more than 2^30 (window, prior) pairs), the sweep's
+// buffers and the copies of the caller's arrays.  *chunk_out = 0: W = 0, nothing to launch (ps_P is set).
+static int prior_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_prior, const double* n0, const double* w0,
+                               int64_t* chunk_out) {
+    tp_handle_t h = b->h;
+    const int k = b->p.k;
+    const int64_t W = b->W;
+    *chunk_out = 0;
+    if (b->p.strategy != TP_STRATEGY_CONJUGATE) return fail(h, TP_ERR_INVALID, "%s applies to the conjugate strategy only", name);
+    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
+    if (n_prior < 1) return fail(h, TP_ERR_INVALID, "%s: n_prior=%d < 1", name, n_prior);
+    if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "%s: %s is NULL", name, !n0 ? "n0" : "w0");
+    const int P = n_prior;
+    for (int64_t i = 0; i < W * P; ++i)
+        if (!(n0[i] > 0.0) || !std::isfinite(n0[i]))
+            return fail(h, TP_ERR_INVALID, "%s: n0[%lld] must be finite and > 0", name, (long long)i);
+    for (int64_t i = 0; i < W * P * k; ++i)
+        if (!std::isfinite(w0[i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)i);
+    if (!tiled && k > tp_sweep_max_assets())
+        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d exceeds the sweep kernel's largest universe %d", name, k, tp_sweep_max_assets());
+    if (tiled && k <= tp_sweep_max_assets())
+        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d is served by tp_batch_prior_sweep (k <= %d)", name, k, tp_sweep_max_assets());
+    int rc = begin_launches(b);
+    if (rc != TP_OK) return rc;
+    // like tp_batch_solve_sweep the call drains the handle's stream here: an earlier launch may still use the buffers (and the
+    // tiled workspace) about to be reallocated or refilled, and the kernel span may still be waiting to be read
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    rc = harvest_kernel_time(h);
+    if (rc != TP_OK) return rc;
+    b->ps_P = 0;
+    if (W == 0) { b->ps_P = P; return TP_OK; }
+    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
+    int64_t chunk = h->sweep_chunk_windows > 0 ? h->sweep_chunk_windows : (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes));
+    if (chunk > (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes))) chunk = (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes));
+    if (chunk > (1ll << 30) / P) chunk = (1ll << 30) / P;
+    if (chunk < 1) chunk = 1;
+    if (chunk > W) chunk = W;
+    const size_t WP = (size_t)W * (size_t)P;
+    const std::string what = std::string(name) + ": ";
+    rc = ensure(h, b->ps_C, mat_bytes * (size_t)chunk, (what + "intraday scatters of one sub-range").c_str());
+    if (rc == TP_OK) rc = ensure(h, b->ps_T, mat_bytes * (size_t)chunk, (what + "daily Grams of one sub-range").c_str());
+    if (rc == TP_OK) rc = ensure(h, b->ps_t, sizeof(double) * (size_t)W * k, (what + "daily column sums").c_str());
+    if (rc == TP_OK) rc = ensure(h, b->ps_n0, sizeof(double) * WP, (what + "prior strengths").c_str());
+    if (rc == TP_OK) rc = ensure(h, b->ps_w0, sizeof(double) * WP * k, (what + "prior weights").c_str());
+    if (rc == TP_OK) rc = ensure(h, b->ps_weights, sizeof(double) * WP * k, (what + "weights").c_str());
+    if (rc == TP_OK) rc = ensure(h, b->ps_status, sizeof(int32_t) * WP, (what + "statuses").c_str());
+    if (rc == TP_OK) rc = ensure(h, b->ps_aux, sizeof(double) * WP * TP_AUX_STRIDE, (what + "aux").c_str());
+    if (rc != TP_OK) return rc;
+    // the caller's arrays: copied here, no host pointer is kept
+    HIP_TRY(h, hipMemcpyAsync(b->ps_n0.p, n0, sizeof(double) * WP, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(b->ps_w0.p, w0, sizeof(double) * WP * k, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
+    *chunk_out = chunk;
+    return TP_OK;
+}
+
 // Prior sweep.  Windows go through in sub-ranges of `chunk` windows: the Gram pass (posterior_gram_nt.hip) stores C and T of
 // a sub-range - two k x k matrices per window inside TP_SWEEP_WORKSPACE_BYTES - and t, then posterior_prior_sweep_kernel
 // solves the sub-range's (window, prior) pairs; never more than 2^30 pairs per launch.
@@ -807,50 +865,10 @@ int tp_batch_prior_sweep(tp_batch_t b, int32_t n_prior, const double* n0, const 
     tp_handle_t h = b->h;
     const int k = b->p.k;
     const int64_t W = b->W;
-    if (b->p.strategy != TP_STRATEGY_CONJUGATE)
-        return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep applies to the conjugate strategy only");
-    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep before tp_batch_upload");
-    if (n_prior < 1) return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep: n_prior=%d < 1", n_prior);
-    if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep: %s is NULL", !n0 ? "n0" : "w0");
     const int P = n_prior;
-    for (int64_t i = 0; i < W * P; ++i)
-        if (!(n0[i] > 0.0) || !std::isfinite(n0[i]))
-            return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep: n0[%lld] must be finite and > 0", (long long)i);
-    for (int64_t i = 0; i < W * P * k; ++i)
-        if (!std::isfinite(w0[i])) return fail(h, TP_ERR_INVALID, "tp_batch_prior_sweep: w0[%lld] must be finite", (long long)i);
-    if (k > tp_sweep_max_assets())
-        return fail(h, TP_ERR_UNSUPPORTED, "tp_batch_prior_sweep: k=%d exceeds the sweep kernel's largest universe %d", k,
-                    tp_sweep_max_assets());
-    int rc = begin_launches(b);
-    if (rc != TP_OK) return rc;
-    // like tp_batch_solve_sweep the call drains the handle's stream here: an earlier sweep may still read the buffers about
-    // to be reallocated or refilled, and the kernel span may still be waiting to be read
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    rc = harvest_kernel_time(h);
-    if (rc != TP_OK) return rc;
-    b->ps_P = 0;
-    if (W == 0) { b->ps_P = P; return TP_OK; }
-    // windows per sub-range: C and T
-    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
-    int64_t chunk = h->sweep_chunk_windows > 0 ? h->sweep_chunk_windows : (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes));
-    if (chunk > (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes))) chunk = (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes));
-    if (chunk > (1ll << 30) / P) chunk = (1ll << 30) / P;
-    if (chunk < 1) chunk = 1;
-    if (chunk > W) chunk = W;
-    const size_t WP = (size_t)W * (size_t)P;
-    rc = ensure(h, b->ps_C, mat_bytes * (size_t)chunk, "tp_batch_prior_sweep: intraday scatters of one sub-range");
-    if (rc == TP_OK) rc = ensure(h, b->ps_T, mat_bytes * (size_t)chunk, "tp_batch_prior_sweep: daily Grams of one sub-range");
-    if (rc == TP_OK) rc = ensure(h, b->ps_t, sizeof(double) * (size_t)W * k, "tp_batch_prior_sweep: daily column sums");
-    if (rc == TP_OK) rc = ensure(h, b->ps_n0, sizeof(double) * WP, "tp_batch_prior_sweep: prior strengths");
-    if (rc == TP_OK) rc = ensure(h, b->ps_w0, sizeof(double) * WP * k, "tp_batch_prior_sweep: prior weights");
-    if (rc == TP_OK) rc = ensure(h, b->ps_weights, sizeof(double) * WP * k, "tp_batch_prior_sweep: weights");
-    if (rc == TP_OK) rc = ensure(h, b->ps_status, sizeof(int32_t) * WP, "tp_batch_prior_sweep: statuses");
-    if (rc == TP_OK) rc = ensure(h, b->ps_aux, sizeof(double) * WP * TP_AUX_STRIDE, "tp_batch_prior_sweep: aux");
-    if (rc != TP_OK) return rc;
-    // the caller's arrays: copied here, no host pointer is kept
-    HIP_TRY(h, hipMemcpyAsync(b->ps_n0.p, n0, sizeof(double) * WP, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(b->ps_w0.p, w0, sizeof(double) * WP * k, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
+    int64_t chunk = 0;
+    int rc = prior_sweep_prepare(b, "tp_batch_prior_sweep", false, n_prior, n0, w0, &chunk);
+    if (rc != TP_OK || chunk == 0) return rc;
 
     // Gram pass: the windows' rows as a plain run reads them; no prior, no shared block sums, none of the run's outputs
     tp_gram_kargs_t ga;
@@ -886,6 +904,99 @@ int tp_batch_prior_sweep(tp_batch_t b, int32_t n_prior, const double* n0, const 
         sa.w_first = w0i; sa.w_count = n;
         e = tp_prior_sweep_launch(sa, h->stream);
         if (e != hipSuccess) return fail(h, TP_ERR_HIP, "prior sweep kernel launch failed: %s", hipGetErrorString(e));
+    }
+    rc = timed_done(h, span);
+    if (rc != TP_OK) return rc;
+    b->ps_P = P;
+    return end_launches(b);                            // (the sweep reads the batch's inputs and writes none of its results)
+}
+
+// Prior sweep above tp_sweep_max_assets(), on the large-k tiled pipeline.  Per sub-range of windows (two k x k matrices per
+// window inside TP_SWEEP_WORKSPACE_BYTES, at least one window) the batch's own tiled Gram stage runs twice, steered by its
+// arguments - as a Jeffreys batch without centring over the daily rows (T into ps_T through the kept-matrix store, t into ps_t
+// through the kept-right-hand-side store) and as a Jeffreys batch centred by the window's row count over the INTRADAY rows,
+// the daily-panel fields pointed at the intraday panel (C = Y'Y - (Y'1)(Y'1)'/m into ps_C).  Then the sub-range's (window,
+// prior) pairs go through the arena in groups of at most tiled_capacity entries: posterior_prior_sweep_tiled.hip fills them,
+// tp_tiled_factor_launch factorises and solves them into the sweep's buffers.
+int tp_batch_prior_sweep_tiled(tp_batch_t b, int32_t n_prior, const double* n0, const double* w0) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    const int k = b->p.k;
+    const int64_t W = b->W;
+    const int P = n_prior;
+    int64_t chunk = 0;
+    int rc = prior_sweep_prepare(b, "tp_batch_prior_sweep_tiled", true, n_prior, n0, w0, &chunk);
+    if (rc != TP_OK || chunk == 0) return rc;
+    // the batch's own tiled workspace (lane 0) and the pieces of a C w0 per arena entry
+    tp_tiled_ws_t wsl[TP_MAX_LANES];
+    int lanes = 1;
+    rc = ensure_tiled_ws(b, wsl, &lanes, chunk * P);
+    if (rc != TP_OK) return rc;
+    const int64_t cap = b->tiled_capacity;
+    rc = ensure(h, b->t_part[0], sizeof(double) * (size_t)cap * wsl[0].NS * wsl[0].NS * 64, "tp_batch_prior_sweep_tiled: prior products");
+    if (rc != TP_OK) return rc;
+    tp_tiled_ws_t ws = wsl[0];
+    ws.part = (double*)b->t_part[0].p;
+
+    // T and t: the daily rows as a plain run reads them, uncentred; no prior, no shared block sums, no custom right-hand side
+    tp_kargs_t ta = make_kargs(b);
+    ta.strategy = TP_STRATEGY_JEFFREYS;
+    ta.center_rows = 2;
+    ta.w0 = nullptr; ta.n0 = nullptr;
+    ta.rhs = nullptr; ta.shift = nullptr;
+    ta.prefix = nullptr; ta.winsum = nullptr; ta.prefix_nblk = 0; ta.prefix_blk0 = 0;
+    for (int i = 0; i < 4; ++i) ta.winsum_L[i] = 0;
+    ta.weights = nullptr; ta.status = nullptr; ta.aux = nullptr; ta.stamps = nullptr;
+    ta.out_rhs = (double*)b->ps_t.p;
+    ta.out_post = (double*)b->ps_T.p;
+    // C: the same stage over the intraday rows - the daily-panel fields name the intraday panel (its own 32-bit offset flags:
+    // make_kargs formed hf_off32 from that panel's bytes, leading dimension and m), centred by the window's row count
+    tp_kargs_t ca = ta;
+    ca.panel = ta.hf_panel; ca.start = ta.hf_start; ca.row_idx = ta.hf_row_idx; ca.n_rows = ta.hf_count;
+    ca.n_r = b->p.m; ca.rf_adj = nullptr;
+    ca.panel_ld = ta.hf_ld; ca.panel_off32 = ta.hf_off32;
+    ca.center_rows = 1;
+    ca.out_rhs = nullptr;
+    ca.out_post = (double*)b->ps_C.p;
+    for (tp_kargs_t* g : {&ta, &ca}) { g->hf_panel = nullptr; g->hf_start = nullptr; g->hf_row_idx = nullptr; g->hf_count = nullptr; g->hf_off32 = 0; }
+    tp_prior_sweep_tiled_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.C = (const double*)b->ps_C.p; sa.T = (const double*)b->ps_T.p; sa.t = (const double*)b->ps_t.p;
+    sa.n0 = (const double*)b->ps_n0.p; sa.w0 = (const double*)b->ps_w0.p;
+    sa.hf_count = (const int*)b->hf_count.p;
+    sa.k = k; sa.P = P; sa.m = b->p.m;
+    // factorisation and solve of the arena entries: a conjugate "batch" of (window, prior) pairs writing the sweep's buffers
+    tp_kargs_t fa;
+    memset(&fa, 0, sizeof fa);
+    fa.strategy = TP_STRATEGY_CONJUGATE;
+    fa.k = k; fa.N = b->p.N; fa.n_r = b->p.n_r; fa.m = b->p.m; fa.gamma = b->p.gamma;
+    fa.opts = h->opts;
+    fa.weights = (double*)b->ps_weights.p; fa.status = (int*)b->ps_status.p; fa.aux = (double*)b->ps_aux.p;
+    fa.dbg_w = -1;
+    // one span around all launches: a sweep is one step of tp_region_steps, kernel_ms = Gram passes + fills + solves
+    // (tp_last_launch keeps describing tp_batch_run launches: nothing here writes it)
+    Span& span = timed_span(h);
+    HIP_TRY(h, span.begin(h->stream));
+    for (int64_t w0i = 0; w0i < W; w0i += chunk) {
+        const int64_t n = W - w0i < chunk ? W - w0i : chunk;
+        for (int64_t g0 = 0; g0 < n; g0 += cap) {
+            for (tp_kargs_t* g : {&ta, &ca}) {
+                g->w_first = w0i + g0; g->w_count = n - g0 < cap ? n - g0 : cap;
+                g->post_w0 = w0i; g->post_count = n;
+                const hipError_t e = tp_tiled_gram_launch(*g, ws, h->stream, false);
+                if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled prior sweep Gram launch failed: %s", hipGetErrorString(e));
+            }
+        }
+        const int64_t E = n * P;
+        for (int64_t e0 = 0; e0 < E; e0 += cap) {
+            sa.wc_first = w0i;
+            sa.e_first = w0i * P + e0; sa.e_count = E - e0 < cap ? E - e0 : cap;
+            hipError_t e = tp_prior_sweep_tiled_launch(sa, ws, h->stream);
+            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled prior sweep fill launch failed: %s", hipGetErrorString(e));
+            fa.w_first = sa.e_first; fa.w_count = sa.e_count;
+            e = tp_tiled_factor_launch(fa, ws, h->stream);
+            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled prior sweep factor launch failed: %s", hipGetErrorString(e));
+        }
     }
     rc = timed_done(h, span);
     if (rc != TP_OK) return rc;

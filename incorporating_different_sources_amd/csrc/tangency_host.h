@@ -144,7 +144,9 @@ int download(tp_handle_t h, std::initializer_list<Copy> copies);
 // tangency_plan.cpp: input validation, upload planning, large-k launch planning
 int validate_pairs(tp_handle_t h, const char* what, const int32_t* num, const int32_t* den, int64_t n, int64_t price_rows);
 int validate_inputs(tp_handle_t h, const tp_params_t& p, int64_t W, const tp_inputs_t* in_raw);
-int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int* lanes_out);
+// `entries`: arena slots a caller other than a run could fill at once (the tiled prior sweep: (window, prior) pairs); the
+// workspace holds up to max(W, entries) of them where the arena budget allows
+int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int* lanes_out, int64_t entries = 0);
 int plan_daily_tables(tp_batch_t b, tp_kargs_t& sub, bool whole);
 int plan_hf_tables(tp_batch_t b, tp_kargs_t& sub);
 int plan_shared_gram(tp_batch_t b, const tp_inputs_t* in);

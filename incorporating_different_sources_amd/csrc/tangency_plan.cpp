@@ -86,7 +86,7 @@ int validate_inputs(tp_handle_t h, const tp_params_t& p, int64_t W, const tp_inp
 // larger launches).  Depth-first alternative (options tiled_lanes / tiled_arena_mib): several small sub-batches in flight,
 // each on a stream and a workspace of its own, sized so that all arenas together stay inside the 256 MiB Infinity Cache
 // - the left-looking update then re-reads a window's block rows from cache instead of streaming them from HBM.
-int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int* lanes_out) {
+int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int* lanes_out, int64_t entries) {
     tp_handle_t h = b->h;
     int KP, NS, NSB;
     tp_tiled_geometry(b->p.k, &KP, &NS, &NSB);
@@ -102,7 +102,7 @@ int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int* lanes_out) {
     if (h->tiled_arena_mib >= 1 && h->tiled_arena_mib <= 200 * 1024) arena_bytes = (unsigned long long)h->tiled_arena_mib << 20;
     int64_t G = (int64_t)(arena_bytes / per_window);
     if (G < 1) G = 1;
-    if (G > b->W) G = b->W;
+    if (G > (entries > b->W ? entries : b->W)) G = entries > b->W ? entries : b->W;
     if (G > 65535) G = 65535;
     if ((int64_t)lanes * G > b->W) lanes = (int)((b->W + G - 1) / G);
     if (b->tiled_capacity < G || b->tiled_lanes < lanes) {

@@ -927,16 +927,16 @@ def _batch_family(portfolio_spec):
     return tuple(portfolio_spec.get(name) for name in ("size", "rebalancing_frequency", "rolling_window", "rolling_window_frequency"))
 
 
-def _prior_sweep_weights(k, N, gamma, kw, n0, w0):
-    """One upload of the windows in `kw` and ONE prior sweep (`Batch.prior_sweep`): weights [W x P x k], status [W x P]
-    for the priors n0 [W x P], w0 [W x P x k]."""
+def _prior_sweep_weights(k, N, gamma, kw, n0, w0, tiled=False):
+    """One upload of the windows in `kw` and ONE prior sweep (`Batch.prior_sweep`; `tiled`: `Batch.prior_sweep_tiled`):
+    weights [W x P x k], status [W x P] for the priors n0 [W x P], w0 [W x P x k]."""
     dev = _native.default_device()
     W = len(kw["n_rows"]) if kw.get("n_rows") is not None else len(kw["start"])
     upload = {key: val for key, val in kw.items() if key not in ("n_r", "m")}
     b = _native.Batch(dev, "conjugate", k, N, kw["n_r"], gamma, W, kw.get("m") or 0)
     try:
         b.upload(**upload)
-        weights, status, _ = b.prior_sweep(n0, w0, want_aux=False)
+        weights, status, _ = (b.prior_sweep_tiled if tiled else b.prior_sweep)(n0, w0, want_aux=False)
     finally:
         b.close()
     return weights, status
@@ -952,7 +952,11 @@ def calculate_weights_for_specs(trading_dates, portfolio_specs_list, market_data
 
     `share_grams=True`: the windows are uploaded ONCE (no replica per spec) and one prior sweep (`Batch.prior_sweep`) forms
     every window's two Grams once and solves the len(specs) priors from them; same results within the solve's rounding,
-    same cache slots.  Sizes above `_native.sweep_max_assets()` run the replicated batch."""
+    same cache slots.  Sizes above `_native.sweep_max_assets()` run the replicated batch.
+
+    `share_grams="any"`: as `True`, and sizes above `_native.sweep_max_assets()` take the large-k form of the sweep
+    (`Batch.prior_sweep_tiled`) instead of the replicated batch.  Its intraday scatter is centred through the raw moments
+    (DESIGN.md section 4h): for return panels the results agree with the replicated batch within the solve's rounding."""
     specs = list(portfolio_specs_list)
     if not specs:
         return []
@@ -967,9 +971,11 @@ def calculate_weights_for_specs(trading_dates, portfolio_specs_list, market_data
     gammas = [sp["risk_aversion"] for sp in specs]
     same_gamma = all(g == gammas[0] for g in gammas)
     priors = [(kw["w0"], kw["n0"])] + [batch.prior_inputs(trading_dates, sp, market_data, caps) for sp in specs[1:]]
-    if share_grams and k <= _native.sweep_max_assets():
+    small = bool(share_grams) and k <= _native.sweep_max_assets()
+    if small or share_grams == "any":
         weights, status = _prior_sweep_weights(k, N, gammas[0] if same_gamma else 1.0, kw,
-                                               np.stack([p[1] for p in priors], axis=1), np.stack([p[0] for p in priors], axis=1))
+                                               np.stack([p[1] for p in priors], axis=1), np.stack([p[0] for p in priors], axis=1),
+                                               tiled=not small)
         _raise_on_status(status.reshape(-1))
         weights = np.ascontiguousarray(weights.transpose(1, 0, 2)).reshape(n_specs * n_dates, k)
     else:
