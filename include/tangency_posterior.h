@@ -236,8 +236,35 @@ int tp_batch_download_posterior(tp_batch_t b, double* M /* [w_count x k x k], sy
 #define TP_SWEEP_MAX_RHS 16
 int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift /* [W x n_shift x 2] or NULL */,
                          int32_t n_rhs, const double* rhs /* [W x n_rhs x k] or NULL */, int32_t default_rhs);
-/* Waits for the sweep and copies out x [W x S x R x k] and status [W x S] (TP_STATUS_OK, TP_STATUS_NOT_PD: a pivot <= 0,
- * TP_STATUS_NONFINITE: NaN / Inf in any of the R solutions); either may be NULL.  Without a sweep before it:
+/* Solve sweep for k > tp_sweep_max_assets(): the same definition of M_w, arguments, validation and result buffers as
+ * tp_batch_solve_sweep - download with tp_batch_download_sweep / tp_batch_download_sweep_rhs - on the large-k tiled pipeline.
+ * TP_ERR_UNSUPPORTED: k <= tp_sweep_max_assets() (tp_batch_solve_sweep serves those sizes and keeps refusing the larger
+ * ones), or k + R > tp_max_assets() + 1 (the arena side would exceed 2048).
+ * How it runs: per sub-range of windows ("sweep_chunk_windows"; one k x k matrix per window inside 256 MiB, at least one
+ * window) the batch's own tiled Gram kernels - its real strategy, without its set_rhs / set_shift and never with the shared
+ * daily or intraday block sums, so M_w depends on the window's rows alone - store M_w and the default right-hand side.  Then
+ * every (window, shift) pair takes one entry of a tiled workspace the SWEEP owns, whose arena side is
+ * KP = 64 ceil((k + R)/64): a fill pass writes M_w + d I + e 1 1' into the k x k corner, the R right-hand sides into columns
+ * k .. k+R-1 and zeros elsewhere; the block steps of tp_batch_run's tiled factorisation, which take their geometry from the
+ * workspace and carry every column >= k of a pivot block row along, factorise the entry ONCE and forward-substitute all R
+ * columns; a back substitution of the sweep's own solves them in groups of up to four columns.  Entries go through in groups
+ * of the workspace's capacity.  A (window, shift) result depends on the window's rows, its own shift and right-hand sides, k
+ * and R only - not on W, S, the positions, the sub-ranges or the size of the workspace.
+ * Statuses: TP_STATUS_NOT_PD is the tiled run's rule, a pivot that is not > 0 (no relative floor; a NaN in the window's rows
+ * ends here, for every shift of that window); TP_STATUS_NONFINITE: NaN / Inf in any of the R solutions.
+ * Streams, timing (one HIP-event pair: one step of tp_region_steps, one kernel_ms over Gram passes, fills, factorisations and
+ * solves), the gather hand-over and what the call leaves alone are as for tp_batch_solve_sweep, tp_last_launch included; it
+ * waits, on entry, for whatever was queued on the handle's stream.
+ * Device memory: that of tp_batch_solve_sweep without its three Gram-pass outputs, plus the batch's tiled run workspace as
+ * tp_batch_run sizes it (NOT grown or re-shaped: it stays what later runs need) and the sweep's workspace of
+ * 8 (KP^2 + 4096 ceil(k/64)) + 4 bytes per entry.  The entry count follows the run workspace's budget rule - 32 GiB, never
+ * more than a third of the free memory, "tiled_arena_gib" / "tiled_arena_mib" override it - capped at the (window, shift)
+ * pairs of one sub-range and at 65,535 (k = 500, R = 2: 2.4 MB per entry, 32 dates x 1000 shifts go through about 14,500 entries
+ * at a time).  It is kept, like the other sweep buffers, until tp_batch_destroy. */
+int tp_batch_solve_sweep_tiled(tp_batch_t b, int32_t n_shift, const double* shift /* [W x n_shift x 2] or NULL */,
+                               int32_t n_rhs, const double* rhs /* [W x n_rhs x k] or NULL */, int32_t default_rhs);
+/* Waits for the sweep (of either kind) and copies out x [W x S x R x k] and status [W x S] (TP_STATUS_OK, TP_STATUS_NOT_PD:
+ * a pivot <= 0, TP_STATUS_NONFINITE: NaN / Inf in any of the R solutions); either may be NULL.  Without a sweep before it:
  * TP_ERR_INVALID. */
 int tp_batch_download_sweep(tp_batch_t b, double* x, int32_t* status);
 /* The default right-hand sides [W x k] (t, or c S0 w0 + t) the Gram pass of the last sweep formed, whether or not the

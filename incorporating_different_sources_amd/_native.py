@@ -44,7 +44,7 @@ EXPORTS = [
     "tp_batch_shared_intraday_blocks",
     "tp_host_alloc", "tp_host_free", "tp_batch_set_rhs", "tp_batch_set_shift", "tp_batch_keep_rhs",
     "tp_batch_download_rhs", "tp_batch_keep_posterior", "tp_batch_download_posterior", "tp_batch_run", "tp_batch_download", "tp_batch_download_S1", "tp_batch_download_matrix",
-    "tp_batch_solve_sweep", "tp_batch_download_sweep", "tp_batch_download_sweep_rhs",
+    "tp_batch_solve_sweep", "tp_batch_solve_sweep_tiled", "tp_batch_download_sweep", "tp_batch_download_sweep_rhs",
     "tp_batch_prior_sweep", "tp_batch_prior_sweep_tiled", "tp_batch_download_prior_sweep",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
@@ -111,6 +111,7 @@ def _load():
     lib.tp_batch_download_posterior.argtypes = [c_void_p, POINTER(c_double)]
     lib.tp_batch_run.argtypes = [c_void_p]
     lib.tp_batch_solve_sweep.argtypes = [c_void_p, c_int32, POINTER(c_double), c_int32, POINTER(c_double), c_int32]
+    lib.tp_batch_solve_sweep_tiled.argtypes = [c_void_p, c_int32, POINTER(c_double), c_int32, POINTER(c_double), c_int32]
     lib.tp_batch_download_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32)]
     lib.tp_batch_download_sweep_rhs.argtypes = [c_void_p, POINTER(c_double)]
     lib.tp_batch_prior_sweep.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
@@ -554,6 +555,16 @@ class Batch:
         right-hand sides `rhs` [W x n x k] (a [W x k] array is one column), behind the window's own right-hand side when
         `default_rhs`.  Returns (x [W, S, R, k], status [W, S]).  `out=(x, status)`: write into these arrays (e.g.
         `pinned_empty`).  The batch's results, settings and kept arrays are left alone."""
+        return self._solve_sweep(lib.tp_batch_solve_sweep, shift, rhs, default_rhs, out)
+
+    def solve_sweep_tiled(self, shift=None, rhs=None, default_rhs=True, out=None):
+        """`tp_batch_solve_sweep_tiled` + `tp_batch_download_sweep`: `solve_sweep` for k above `sweep_max_assets()`, every
+        (window, shift) pair factorised once by the large-k tiled pipeline with the R right-hand sides riding along as
+        columns k .. k+R-1 of the arena (smaller k, or k + R > max_assets() + 1: TP_ERR_UNSUPPORTED).  Same arguments,
+        shape checks and return values; `download_sweep_rhs` serves both calls."""
+        return self._solve_sweep(lib.tp_batch_solve_sweep_tiled, shift, rhs, default_rhs, out)
+
+    def _solve_sweep(self, call, shift, rhs, default_rhs, out):
         W, k = self.W, self.k
         sh = None
         S = 1
@@ -584,14 +595,15 @@ class Batch:
         else:
             x = np.empty((W, S, R, k), dtype=np.float64)
             status = np.empty((W, S), dtype=np.int32)
-        self.dev._check(lib.tp_batch_solve_sweep(self._b, S if sh is not None else 0, _ptr(sh, c_double), n_rhs,
-                                                 _ptr(r if n_rhs else None, c_double), 1 if default_rhs else 0))
+        self.dev._check(call(self._b, S if sh is not None else 0, _ptr(sh, c_double), n_rhs,
+                             _ptr(r if n_rhs else None, c_double), 1 if default_rhs else 0))
         self.dev._check(lib.tp_batch_download_sweep(self._b, _ptr(x if x.size else None, c_double),
                                                     _ptr(status if status.size else None, c_int32)))
         return x, status
 
     def download_sweep_rhs(self) -> np.ndarray:
-        """[W x k] default right-hand sides (t = X'1, or c S0 w0 + t) the Gram pass of the last `solve_sweep` formed."""
+        """[W x k] default right-hand sides (t = X'1, or c S0 w0 + t) the Gram pass of the last `solve_sweep` /
+        `solve_sweep_tiled` formed."""
         out = np.empty((self.W, self.k), dtype=np.float64)
         self.dev._check(lib.tp_batch_download_sweep_rhs(self._b, _ptr(out if out.size else None, c_double)))
         return out

@@ -165,6 +165,9 @@ hipError_t tp_tiled_prefix_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, 
 // the factor stage factorises and solves whatever a.w_count matrices the arena holds (entry e -> output slot a.w_first + e)
 hipError_t tp_tiled_gram_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream, bool build_prefix);
 hipError_t tp_tiled_factor_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream);
+// the factor stage without its solve: the block steps alone, on a workspace of any geometry (KP, NS, NSB come from `ws`) -
+// columns >= k of the pivot block rows come out forward-substituted (the tiled solve sweep back-substitutes them itself)
+hipError_t tp_tiled_block_steps_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream);
 // bytes of the shared block Grams + n_L block-window tables of the daily panel in the tiled layout (16-row blocks)
 size_t tp_tiled_prefix_bytes(int k, long long panel_rows, int n_L, int* nblk_out);
 size_t tp_tiled_slot_doubles(int k);

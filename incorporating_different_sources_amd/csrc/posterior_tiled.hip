@@ -1015,11 +1015,12 @@ hipError_t tp_tiled_gram_launch(const tp_kargs_t& a_in, const tp_tiled_ws_t& ws,
     return hipGetLastError();
 }
 
-// Factorisation and solve of the a.w_count bordered matrices in the arena (entry e is window a.w_first + e of the output
-// arrays), whoever filled it.  Of the arguments the block steps read k, w_count and (on the host) opts; tile64_kernel also
-// forms addresses from w_first, col_idx and m that only its Gram mode dereferences.  tiled_solve_kernel reads strategy, N,
-// gamma, w_first, weights, status, aux, ws.scal[8 e + 2..4] = (c, q0, n0) and ws.flags.
-hipError_t tp_tiled_factor_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream) {
+// The block steps of the factorisation of the a.w_count matrices in the arena, whoever filled it and whatever the workspace's
+// geometry: every kernel here takes KP, NS and NSB from `ws` and the pivot count from k.  Of the arguments they read k,
+// w_count and (on the host) opts; tile64_kernel also forms addresses from w_first, col_idx and m that only its Gram mode
+// dereferences.  Every column >= k of a pivot block row rides along and comes out forward-substituted: the one border column
+// of a run (NS = ceil((k+1)/64)) or the R right-hand sides of the tiled solve sweep (NS = ceil((k+R)/64)).
+hipError_t tp_tiled_block_steps_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream) {
     const int G = (int)a.w_count;
     if (G <= 0) return hipSuccess;
     const int NS = ws.NS, NSB = ws.NSB;
@@ -1048,6 +1049,17 @@ hipError_t tp_tiled_factor_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, 
             else hipLaunchKernelGGL(tile64_kernel<MODE_TRSM>, xcd_grid(T, G), dim3(NTHREADS), 0, stream, a, ws, j);
         }
     }
+    return hipGetLastError();
+}
+
+// Factorisation and solve of the a.w_count bordered matrices in the arena (entry e is window a.w_first + e of the output
+// arrays), whoever filled it: the block steps, then tiled_solve_kernel, which reads strategy, N, gamma, w_first, weights,
+// status, aux, ws.scal[8 e + 2..4] = (c, q0, n0) and ws.flags.
+hipError_t tp_tiled_factor_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream) {
+    const int G = (int)a.w_count;
+    if (G <= 0) return hipSuccess;
+    const hipError_t e = tp_tiled_block_steps_launch(a, ws, stream);
+    if (e != hipSuccess) return e;
     const size_t smem = sizeof(double) * (size_t)(ws.KP + SB);
     hipLaunchKernelGGL(tiled_solve_kernel, dim3(G), dim3(NTHREADS), smem, stream, a, ws);
     return hipGetLastError();

@@ -680,31 +680,37 @@ int tp_batch_run(tp_batch_t b) {
 // windows as TP_SWEEP_WORKSPACE_BYTES of matrices hold (256 MiB, the size of the Infinity Cache: the solve kernel reads
 // what the Gram pass has just written), never more than 2^30 (window, shift) pairs per launch.
 #define TP_SWEEP_WORKSPACE_BYTES (256ull << 20)
-int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift, int32_t n_rhs, const double* rhs,
-                         int32_t default_rhs) {
-    if (!b) return TP_ERR_INVALID;
+// What the two solve sweeps share - tp_batch_solve_sweep (`tiled` = false, k <= tp_sweep_max_assets()) and
+// tp_batch_solve_sweep_tiled (above it): the argument checks, the drain of the handle's stream, the windows per sub-range, the
+// sweep's buffers and the copies of the caller's arrays.  *chunk_out = 0: W = 0, nothing to launch (sw_S / sw_R are set).
+static int solve_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_shift, const double* shift, int32_t n_rhs,
+                               const double* rhs, int32_t default_rhs, int* S_out, int* R_out, int64_t* chunk_out) {
     tp_handle_t h = b->h;
     const int k = b->p.k;
     const int64_t W = b->W;
-    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep before tp_batch_upload");
-    if (n_shift < 0) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: n_shift=%d < 0", n_shift);
-    if (n_rhs < 0) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: n_rhs=%d < 0", n_rhs);
+    *chunk_out = 0;
+    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
+    if (n_shift < 0) return fail(h, TP_ERR_INVALID, "%s: n_shift=%d < 0", name, n_shift);
+    if (n_rhs < 0) return fail(h, TP_ERR_INVALID, "%s: n_rhs=%d < 0", name, n_rhs);
     if (shift && b->p.strategy != TP_STRATEGY_JEFFREYS)
-        return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: a shift applies to the Jeffreys strategy only");
-    if (shift && n_shift < 1) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: shift given with n_shift=0");
-    if (!shift && n_shift > 1) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: n_shift=%d without shift", n_shift);
+        return fail(h, TP_ERR_INVALID, "%s: a shift applies to the Jeffreys strategy only", name);
+    if (shift && n_shift < 1) return fail(h, TP_ERR_INVALID, "%s: shift given with n_shift=0", name);
+    if (!shift && n_shift > 1) return fail(h, TP_ERR_INVALID, "%s: n_shift=%d without shift", name, n_shift);
     const int S = n_shift > 1 ? n_shift : 1;
     const long long R = (default_rhs ? 1 : 0) + (long long)n_rhs;
     if (R < 1 || R > TP_SWEEP_MAX_RHS)
-        return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: %lld right-hand sides per window outside [1, %d]", R, TP_SWEEP_MAX_RHS);
-    if (n_rhs > 0 && !rhs) return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: n_rhs=%d without rhs", n_rhs);
+        return fail(h, TP_ERR_INVALID, "%s: %lld right-hand sides per window outside [1, %d]", name, R, TP_SWEEP_MAX_RHS);
+    if (n_rhs > 0 && !rhs) return fail(h, TP_ERR_INVALID, "%s: n_rhs=%d without rhs", name, n_rhs);
     if (shift)
         for (int64_t i = 0; i < 2 * W * S; ++i)
             if (!(shift[i] >= 0.0) || !std::isfinite(shift[i]))
-                return fail(h, TP_ERR_INVALID, "tp_batch_solve_sweep: shift[%lld] must be finite and >= 0", (long long)i);
-    if (k > tp_sweep_max_assets())
-        return fail(h, TP_ERR_UNSUPPORTED, "tp_batch_solve_sweep: k=%d exceeds the sweep kernel's largest universe %d", k,
-                    tp_sweep_max_assets());
+                return fail(h, TP_ERR_INVALID, "%s: shift[%lld] must be finite and >= 0", name, (long long)i);
+    if (!tiled && k > tp_sweep_max_assets())
+        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d exceeds the sweep kernel's largest universe %d", name, k, tp_sweep_max_assets());
+    if (tiled && k <= tp_sweep_max_assets())
+        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d is served by tp_batch_solve_sweep (k <= %d)", name, k, tp_sweep_max_assets());
+    if (tiled && k + R > tp_max_assets() + 1)
+        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d with %lld right-hand sides exceeds the arena side %d", name, k, R, tp_max_assets() + 1);
     int rc = begin_launches(b);
     if (rc != TP_OK) return rc;
     // Unlike tp_batch_run the call drains the handle's stream here (documented in the header): an earlier sweep may still
@@ -713,30 +719,39 @@ int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift, int
     rc = harvest_kernel_time(h);
     if (rc != TP_OK) return rc;
     b->sw_S = 0; b->sw_R = 0;
+    *S_out = S; *R_out = (int)R;
     if (W == 0) { b->sw_S = S; b->sw_R = (int)R; return TP_OK; }
     // windows per sub-range
     const size_t mat_bytes = sizeof(double) * (size_t)k * k;
     int64_t chunk = h->sweep_chunk_windows > 0 ? h->sweep_chunk_windows : (int64_t)(TP_SWEEP_WORKSPACE_BYTES / mat_bytes);
+    if (tiled && chunk > (int64_t)(TP_SWEEP_WORKSPACE_BYTES / mat_bytes)) chunk = (int64_t)(TP_SWEEP_WORKSPACE_BYTES / mat_bytes);
     if (chunk > (1ll << 30) / S) chunk = (1ll << 30) / S;
     if (chunk < 1) chunk = 1;
     if (chunk > W) chunk = W;
-    rc = ensure(h, b->sw_post, mat_bytes * (size_t)chunk, "tp_batch_solve_sweep: kept matrices of one sub-range");
-    if (rc == TP_OK) rc = ensure(h, b->sw_weights, sizeof(double) * (size_t)W * k, "tp_batch_solve_sweep: weights of the Gram pass");
-    if (rc == TP_OK) rc = ensure(h, b->sw_status, sizeof(int32_t) * (size_t)W, "tp_batch_solve_sweep: statuses of the Gram pass");
-    if (rc == TP_OK) rc = ensure(h, b->sw_aux, sizeof(double) * (size_t)W * TP_AUX_STRIDE, "tp_batch_solve_sweep: aux of the Gram pass");
-    if (rc == TP_OK) rc = ensure(h, b->sw_rhs0, sizeof(double) * (size_t)W * k, "tp_batch_solve_sweep: default right-hand sides");
-    if (rc == TP_OK) rc = ensure(h, b->sw_x, sizeof(double) * (size_t)W * S * (size_t)R * k, "tp_batch_solve_sweep: solutions");
-    if (rc == TP_OK) rc = ensure(h, b->sw_xstatus, sizeof(int32_t) * (size_t)W * S, "tp_batch_solve_sweep: solution statuses");
-    if (rc == TP_OK && shift) rc = ensure(h, b->sw_shift, sizeof(double) * 2 * (size_t)W * S, "tp_batch_solve_sweep: shifts");
-    if (rc == TP_OK && n_rhs > 0) rc = ensure(h, b->sw_rhs, sizeof(double) * (size_t)W * n_rhs * k, "tp_batch_solve_sweep: right-hand sides");
+    const std::string what = std::string(name) + ": ";
+    rc = ensure(h, b->sw_post, mat_bytes * (size_t)chunk, (what + "kept matrices of one sub-range").c_str());
+    if (!tiled) {                                      // outputs of the run kernel that serves as the Gram pass
+        if (rc == TP_OK) rc = ensure(h, b->sw_weights, sizeof(double) * (size_t)W * k, (what + "weights of the Gram pass").c_str());
+        if (rc == TP_OK) rc = ensure(h, b->sw_status, sizeof(int32_t) * (size_t)W, (what + "statuses of the Gram pass").c_str());
+        if (rc == TP_OK) rc = ensure(h, b->sw_aux, sizeof(double) * (size_t)W * TP_AUX_STRIDE, (what + "aux of the Gram pass").c_str());
+    }
+    if (rc == TP_OK) rc = ensure(h, b->sw_rhs0, sizeof(double) * (size_t)W * k, (what + "default right-hand sides").c_str());
+    if (rc == TP_OK) rc = ensure(h, b->sw_x, sizeof(double) * (size_t)W * S * (size_t)R * k, (what + "solutions").c_str());
+    if (rc == TP_OK) rc = ensure(h, b->sw_xstatus, sizeof(int32_t) * (size_t)W * S, (what + "solution statuses").c_str());
+    if (rc == TP_OK && shift) rc = ensure(h, b->sw_shift, sizeof(double) * 2 * (size_t)W * S, (what + "shifts").c_str());
+    if (rc == TP_OK && n_rhs > 0) rc = ensure(h, b->sw_rhs, sizeof(double) * (size_t)W * n_rhs * k, (what + "right-hand sides").c_str());
     if (rc != TP_OK) return rc;
     // the caller's arrays: copied here, no host pointer is kept
     if (shift) HIP_TRY(h, hipMemcpyAsync(b->sw_shift.p, shift, sizeof(double) * 2 * (size_t)W * S, hipMemcpyHostToDevice, h->stream));
     if (n_rhs > 0) HIP_TRY(h, hipMemcpyAsync(b->sw_rhs.p, rhs, sizeof(double) * (size_t)W * n_rhs * k, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
+    *chunk_out = chunk;
+    return TP_OK;
+}
 
-    // Gram pass: the batch as a plain run would see it - no custom right-hand side, no shift - writing into the sweep's
-    // buffers, and without the shared block sums (whether those are used depends on W: M_w must not)
+// the Gram pass of a solve sweep: the batch as a plain run would see it - no custom right-hand side, no shift - writing into
+// the sweep's buffers, and without the shared block sums (whether those are used depends on W: M_w must not)
+static tp_kargs_t solve_sweep_gram_kargs(tp_batch_t b) {
     tp_kargs_t a = make_kargs(b);
     a.rhs = nullptr;
     a.shift = nullptr;
@@ -748,6 +763,20 @@ int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift, int
     a.out_rhs = (double*)b->sw_rhs0.p;
     a.out_post = (double*)b->sw_post.p;
     a.stamps = nullptr;
+    return a;
+}
+
+int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift, int32_t n_rhs, const double* rhs,
+                         int32_t default_rhs) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    const int k = b->p.k;
+    const int64_t W = b->W;
+    int S = 0, R = 0;
+    int64_t chunk = 0;
+    int rc = solve_sweep_prepare(b, "tp_batch_solve_sweep", false, n_shift, shift, n_rhs, rhs, default_rhs, &S, &R, &chunk);
+    if (rc != TP_OK || chunk == 0) return rc;
+    tp_kargs_t a = solve_sweep_gram_kargs(b);
     tp_sweep_kargs_t sa;
     memset(&sa, 0, sizeof sa);
     sa.post = (const double*)b->sw_post.p;
@@ -756,7 +785,7 @@ int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift, int
     sa.shift = shift ? (const double*)b->sw_shift.p : nullptr;
     sa.x = (double*)b->sw_x.p;
     sa.status = (int*)b->sw_xstatus.p;
-    sa.k = k; sa.S = S; sa.R = (int)R; sa.n_rhs = n_rhs;
+    sa.k = k; sa.S = S; sa.R = R; sa.n_rhs = n_rhs;
     sa.gamma = b->p.gamma;
     const tp_launch_info_t keep_launch = h->last_launch;      // tp_last_launch describes tp_batch_run launches
     // one span around all launches: a sweep is one step of tp_region_steps, kernel_ms = Gram passes + solves
@@ -775,7 +804,104 @@ int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift, int
     h->last_launch = keep_launch;
     rc = timed_done(h, span);
     if (rc != TP_OK) return rc;
-    b->sw_S = S; b->sw_R = (int)R;
+    b->sw_S = S; b->sw_R = R;
+    return end_launches(b);                            // (the sweep reads the batch's inputs and writes none of its results)
+}
+
+// The sweep's own tiled workspace (arena, inverse diagonal blocks, flags) at the sweep's geometry, KP from k + R: as many
+// (window, shift) entries as the large-k arena budget allows (tiled_arena_entries, the rule ensure_tiled_ws sizes by; what this
+// workspace already holds counts as free), at most `entries`.  The batch's run workspace is left as it is.
+static int ensure_sweep_tiled_ws(tp_batch_t b, int R, int64_t entries, tp_tiled_ws_t* ws, int64_t* cap_out) {
+    tp_handle_t h = b->h;
+    int KP, NS, NSB;
+    tp_solve_sweep_tiled_geometry(b->p.k, R, &KP, &NS, &NSB);
+    const size_t per_entry = sizeof(double) * ((size_t)KP * KP + (size_t)NSB * 64 * 64) + sizeof(int);
+    int64_t G = tiled_arena_entries(h, per_entry, 1, b->swt_arena.bytes + b->swt_rinv.bytes + b->swt_flags.bytes);
+    if (G > entries) G = entries;
+    int rc = ensure(h, b->swt_arena, sizeof(double) * (size_t)G * KP * KP, "tp_batch_solve_sweep_tiled: arena");
+    if (rc == TP_OK) rc = ensure(h, b->swt_rinv, sizeof(double) * (size_t)G * NSB * 64 * 64, "tp_batch_solve_sweep_tiled: inverse diagonal blocks");
+    if (rc == TP_OK) rc = ensure(h, b->swt_flags, sizeof(int) * (size_t)G, "tp_batch_solve_sweep_tiled: flags");
+    if (rc != TP_OK) return rc;
+    memset(ws, 0, sizeof *ws);
+    ws->arena = (double*)b->swt_arena.p; ws->rinv = (double*)b->swt_rinv.p; ws->flags = (int*)b->swt_flags.p;
+    ws->KP = KP; ws->NS = NS; ws->NSB = NSB;
+    *cap_out = G;
+    return TP_OK;
+}
+
+// Solve sweep above tp_sweep_max_assets(), on the large-k tiled pipeline.  Per sub-range of windows (one k x k matrix per
+// window inside TP_SWEEP_WORKSPACE_BYTES, at least one window) the batch's own tiled Gram stage - its real strategy, no custom
+// right-hand side, no shift, no shared sums - leaves M_w in sw_post (the kept-matrix store) and the default right-hand side in
+// sw_rhs0 (the kept-right-hand-side store), in groups of as many windows as the batch's run workspace holds.  Then the
+// sub-range's (window, shift) pairs go through the SWEEP's workspace in groups of its capacity: posterior_solve_sweep_tiled.hip
+// fills them, the block steps of the tiled factorisation factorise them and forward-substitute the R columns, and the sweep's
+// own kernel back-substitutes.
+int tp_batch_solve_sweep_tiled(tp_batch_t b, int32_t n_shift, const double* shift, int32_t n_rhs, const double* rhs,
+                               int32_t default_rhs) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    const int k = b->p.k;
+    const int64_t W = b->W;
+    int S = 0, R = 0;
+    int64_t chunk = 0;
+    int rc = solve_sweep_prepare(b, "tp_batch_solve_sweep_tiled", true, n_shift, shift, n_rhs, rhs, default_rhs, &S, &R, &chunk);
+    if (rc != TP_OK || chunk == 0) return rc;
+    // the batch's run workspace (lane 0) as a run would size it, for the Gram stage; the sweep's own for the entries
+    tp_tiled_ws_t wsl[TP_MAX_LANES];
+    int lanes = 1;
+    rc = ensure_tiled_ws(b, wsl, &lanes);
+    if (rc != TP_OK) return rc;
+    const int64_t gcap = b->tiled_capacity;
+    tp_tiled_ws_t ws;
+    int64_t cap = 0;
+    rc = ensure_sweep_tiled_ws(b, R, chunk * S, &ws, &cap);
+    if (rc != TP_OK) return rc;
+    tp_kargs_t a = solve_sweep_gram_kargs(b);
+    a.weights = nullptr; a.status = nullptr; a.aux = nullptr;          // (the Gram stage writes none of them)
+    a.hf_prefix = nullptr; a.hf_winsum = nullptr;                      // no shared intraday sums either
+    tp_solve_sweep_tiled_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.post = (const double*)b->sw_post.p;
+    sa.default_rhs = default_rhs ? (const double*)b->sw_rhs0.p : nullptr;
+    sa.rhs = n_rhs > 0 ? (const double*)b->sw_rhs.p : nullptr;
+    sa.shift = shift ? (const double*)b->sw_shift.p : nullptr;
+    sa.x = (double*)b->sw_x.p;
+    sa.status = (int*)b->sw_xstatus.p;
+    sa.k = k; sa.S = S; sa.R = R; sa.n_rhs = n_rhs;
+    sa.gamma = b->p.gamma;
+    // the block steps read k, w_count (set per group below) and the kernel choices; everything else stays zero
+    tp_kargs_t fa;
+    memset(&fa, 0, sizeof fa);
+    fa.k = k;
+    fa.opts = h->opts;
+    // one span around all launches: a sweep is one step of tp_region_steps, kernel_ms = Gram passes + fills + factorisations
+    // + solves (tp_last_launch keeps describing tp_batch_run launches: nothing here writes it)
+    Span& span = timed_span(h);
+    HIP_TRY(h, span.begin(h->stream));
+    for (int64_t w0 = 0; w0 < W; w0 += chunk) {
+        const int64_t n = W - w0 < chunk ? W - w0 : chunk;
+        for (int64_t g0 = 0; g0 < n; g0 += gcap) {
+            a.w_first = w0 + g0; a.w_count = n - g0 < gcap ? n - g0 : gcap;
+            a.post_w0 = w0; a.post_count = n;
+            const hipError_t e = tp_tiled_gram_launch(a, wsl[0], h->stream, false);
+            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled solve sweep Gram launch failed: %s", hipGetErrorString(e));
+        }
+        const int64_t E = n * S;
+        for (int64_t e0 = 0; e0 < E; e0 += cap) {
+            sa.wc_first = w0;
+            sa.e_first = w0 * S + e0; sa.e_count = E - e0 < cap ? E - e0 : cap;
+            hipError_t e = tp_solve_sweep_tiled_fill_launch(sa, ws, h->stream);
+            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled solve sweep fill launch failed: %s", hipGetErrorString(e));
+            fa.w_count = sa.e_count;
+            e = tp_tiled_block_steps_launch(fa, ws, h->stream);
+            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled solve sweep factor launch failed: %s", hipGetErrorString(e));
+            e = tp_solve_sweep_tiled_solve_launch(sa, ws, h->stream);
+            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled solve sweep solve launch failed: %s", hipGetErrorString(e));
+        }
+    }
+    rc = timed_done(h, span);
+    if (rc != TP_OK) return rc;
+    b->sw_S = S; b->sw_R = R;
     return end_launches(b);                            // (the sweep reads the batch's inputs and writes none of its results)
 }
 

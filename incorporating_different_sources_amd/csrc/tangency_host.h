@@ -13,6 +13,7 @@
 #include "host_resources.h"
 #include "posterior_kernels.h"
 #include "posterior_prior_sweep.h"
+#include "posterior_solve_sweep_tiled.h"
 
 #define TP_MAX_LANES 4
 #define TP_REGION_MAX_STEPS 512
@@ -76,6 +77,9 @@ struct tp_batch_s {
     // kept right-hand sides alone.  sw_post holds the matrices of ONE sub-range of windows at a time
     DevBuf sw_weights, sw_status, sw_aux, sw_rhs0, sw_post, sw_shift, sw_rhs, sw_x, sw_xstatus;
     int sw_S = 0, sw_R = 0;                                   // shape of the last sweep (0: none yet)
+    // tiled solve sweep (tp_batch_solve_sweep_tiled): its own workspace of (window, shift) entries at the sweep's geometry
+    // (KP from k + R) - the run workspace below keeps the size and shape tp_batch_run gives it
+    DevBuf swt_arena, swt_rinv, swt_flags;
     // prior sweep (tp_batch_prior_sweep): buffers of its own as well.  ps_C / ps_T hold the two Grams of ONE sub-range at a time
     DevBuf ps_C, ps_T, ps_t, ps_n0, ps_w0, ps_weights, ps_status, ps_aux;
     int ps_P = 0;                                             // priors per window of the last prior sweep (0: none yet)
@@ -144,6 +148,9 @@ int download(tp_handle_t h, std::initializer_list<Copy> copies);
 // tangency_plan.cpp: input validation, upload planning, large-k launch planning
 int validate_pairs(tp_handle_t h, const char* what, const int32_t* num, const int32_t* den, int64_t n, int64_t price_rows);
 int validate_inputs(tp_handle_t h, const tp_params_t& p, int64_t W, const tp_inputs_t* in_raw);
+// entries a tiled arena of `per_entry` bytes each may hold: the budget is 32 GiB (shared among `lanes`), never more than a third
+// of what is free (`held` bytes, about to be reallocated, count as free), tiled_arena_gib / _mib override it; 1 .. 65,535
+int64_t tiled_arena_entries(tp_handle_t h, size_t per_entry, int lanes = 1, size_t held = 0);
 // `entries`: arena slots a caller other than a run could fill at once (the tiled prior sweep: (window, prior) pairs); the
 // workspace holds up to max(W, entries) of them where the arena budget allows
 int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int* lanes_out, int64_t entries = 0);

@@ -82,6 +82,25 @@ int validate_inputs(tp_handle_t h, const tp_params_t& p, int64_t W, const tp_inp
     return TP_OK;
 }
 
+// The arena budget of the large-k path, in entries of `per_entry` bytes: 32 GiB of the 288 (fewer, larger launches: measured
+// +2-4 % over 6 GiB at k = 500) shared among `lanes`, never more than a third of what is free (`held`: bytes the caller is
+// about to reallocate, counted as free); tiled_arena_gib overrides it, tiled_arena_mib sets a lane's own arena.
+int64_t tiled_arena_entries(tp_handle_t h, size_t per_entry, int lanes, size_t held) {
+    unsigned long long gib = 32;
+    { size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+          free_b += held;
+          if ((free_b >> 30) / 3 < gib) gib = (free_b >> 30) / 3 > 1 ? (free_b >> 30) / 3 : 1;
+      } }
+    if (h->tiled_arena_gib >= 1 && h->tiled_arena_gib <= 200) gib = (unsigned long long)h->tiled_arena_gib;
+    unsigned long long arena_bytes = (gib << 30) / (unsigned long long)lanes;
+    if (h->tiled_arena_mib >= 1 && h->tiled_arena_mib <= 200 * 1024) arena_bytes = (unsigned long long)h->tiled_arena_mib << 20;
+    int64_t G = (int64_t)(arena_bytes / per_entry);
+    if (G < 1) G = 1;
+    if (G > 65535) G = 65535;
+    return G;
+}
+
 // Workspace of the large-k path.  Default: ONE lane whose arena holds as many in-flight windows as 32 GiB allow (fewer,
 // larger launches).  Depth-first alternative (options tiled_lanes / tiled_arena_mib): several small sub-batches in flight,
 // each on a stream and a workspace of its own, sized so that all arenas together stay inside the 256 MiB Infinity Cache
@@ -92,18 +111,8 @@ int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int* lanes_out, int64_t ent
     tp_tiled_geometry(b->p.k, &KP, &NS, &NSB);
     const size_t per_window = sizeof(double) * ((size_t)KP * KP + (size_t)NSB * 64 * 64 + KP + (size_t)b->p.m + 8) + 4;
     int lanes = h->tiled_lanes >= 1 ? (h->tiled_lanes > TP_MAX_LANES ? TP_MAX_LANES : h->tiled_lanes) : 1;
-    // in-flight windows of one sub-batch: an arena budget of 32 GiB of the 288 (fewer, larger launches: measured
-    // +2-4 % over 6 GiB at k = 500), never more than a third of what is free; tiled_arena_gib / _mib override it
-    unsigned long long gib = 32;
-    { size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (free_b >> 30) / 3 < gib) gib = (free_b >> 30) / 3 > 1 ? (free_b >> 30) / 3 : 1; }
-    if (h->tiled_arena_gib >= 1 && h->tiled_arena_gib <= 200) gib = (unsigned long long)h->tiled_arena_gib;
-    unsigned long long arena_bytes = (gib << 30) / (unsigned long long)lanes;
-    if (h->tiled_arena_mib >= 1 && h->tiled_arena_mib <= 200 * 1024) arena_bytes = (unsigned long long)h->tiled_arena_mib << 20;
-    int64_t G = (int64_t)(arena_bytes / per_window);
-    if (G < 1) G = 1;
+    int64_t G = tiled_arena_entries(h, per_window, lanes);
     if (G > (entries > b->W ? entries : b->W)) G = entries > b->W ? entries : b->W;
-    if (G > 65535) G = 65535;
     if ((int64_t)lanes * G > b->W) lanes = (int)((b->W + G - 1) / G);
     if (b->tiled_capacity < G || b->tiled_lanes < lanes) {
         if (b->tiled_capacity > G) G = b->tiled_capacity;

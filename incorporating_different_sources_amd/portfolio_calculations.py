@@ -644,6 +644,10 @@ def _greyserman_from_solves(u_t, u_one, t, n, xi, eta, k, gamma):
 
 
 _GREYSERMAN_SWEEP_BYTES = 1 << 30   # solutions of one sweep (dates x draws x 2 x k doubles, on the device and on the host)
+# Sizes above `_native.sweep_max_assets()`: True takes one window per date and one tiled solve sweep
+# (`Batch.solve_sweep_tiled`, S = draws, R = 2) instead of the replicated batch.  Off until the two have been timed
+# against each other on the device.
+GREYSERMAN_TILED_SWEEP = False
 
 
 def _greyserman_batch(kw, gamma, k, N, draws=None):
@@ -652,11 +656,12 @@ def _greyserman_batch(kw, gamma, k, N, draws=None):
     per date.  A sweep holds dates x draws x 2 x k solutions on the device and on the host, so the dates go through in
     groups of at most _GREYSERMAN_SWEEP_BYTES of solutions (1,342 dates at k = 50, 469 at k = 143, with 1000 draws); a
     date's result does not depend on the grouping.  Above `sweep_max_assets()`: GREYSERMAN_DRAWS repeated windows per
-    date, two launches per 32 dates."""
+    date, two launches per 32 dates - or, with GREYSERMAN_TILED_SWEEP set, the same loop with `Batch.solve_sweep_tiled`."""
     n_rows = np.asarray(kw["n_rows"])
     W = len(n_rows)
     xi, eta = _greyserman_hyper(W, draws)
-    if k > _native.sweep_max_assets():
+    tiled = k > _native.sweep_max_assets()
+    if tiled and not GREYSERMAN_TILED_SWEEP:
         return _greyserman_batch_repeated(kw, gamma, k, N, xi, eta)
     dev = _native.default_device()
     B = eta.shape[1]
@@ -672,7 +677,8 @@ def _greyserman_batch(kw, gamma, k, N, draws=None):
         b = _native.Batch(dev, "jeffreys", k, N, kw["n_r"], 1.0, hi - lo, 0, flags=_native.FLAG_NO_CENTER)
         try:
             b.upload(**sub)
-            u, status = b.solve_sweep(shift=shift, rhs=np.ones((hi - lo, 1, k)), default_rhs=True)
+            u, status = (b.solve_sweep_tiled if tiled else b.solve_sweep)(shift=shift, rhs=np.ones((hi - lo, 1, k)),
+                                                                          default_rhs=True)
             _raise_on_status(status.reshape(-1))
             t = b.download_sweep_rhs()                     # the Gram pass also leaves t = X'1 (ref:222)
         finally:

@@ -1,0 +1,439 @@
+"""Solve sweeps above sweep_max_assets() (tp_batch_solve_sweep_tiled / Batch.solve_sweep_tiled): S shifts x R right-hand sides
+per window from one Gram pass, every (window, shift) pair factorised ONCE by the large-k tiled pipeline with the R right-hand
+sides as columns k .. k+R-1 of an arena of side KP = 64 ceil((k + R)/64),
+    x[w, s, r] = (M_w + d_ws I + e_ws 1 1')^-1 rhs_wr / gamma.
+Checked against the oracle (Jeffreys: oracle.posterior_batch once per (s, r); conjugate: numpy.linalg.solve on the oracle's S1),
+against the set_rhs + set_shift + run path, for independence of W / S / the window's position / the sub-ranges / the size of
+the sweep's workspace, statuses, that the batch is left alone, timing, the contract, and the Greyserman switch.  -m gpu.
+
+Shapes (k, N, R): 144 is the first size above the LDS solve core; (190, 3): k + 1 needs 3 super-tiles per side and k + R needs 4,
+so the sweep's geometry differs from the run's; (192, 1): k a multiple of 64, NSB = 3, NS = 4, default right-hand side only;
+(255, 16): default + 15 columns, four column groups and a last pivot block of 63; (256, 5): column groups 4 + 1 and the
+right-hand sides in a super-tile column of their own; (300, 3): a general mid-size case."""
+import numpy as np
+import pytest
+
+from incorporating_different_sources_amd import _native, synthetic
+from oracle import oracle
+
+pytestmark = pytest.mark.gpu
+
+GAMMA = 5.0
+# the bound the project holds shifted solves to (tests/test_gpu_solve_sweep.py): atol = 1e-10 max(1, |ref|.max()), rtol = 0
+TOL = 1e-10
+SHAPES = [(144, 200, 3), (190, 250, 3), (192, 250, 1), (255, 300, 16), (256, 320, 5), (300, 360, 3)]
+W, S = 3, 4
+
+
+@pytest.fixture(scope="module")
+def dev():
+    d = _native.Device(0)
+    yield d
+    d.close()
+
+
+def assert_close(x, ref, tol=TOL, what=""):
+    bound = tol * max(1.0, float(np.abs(ref).max()))
+    err = float(np.abs(x - ref).max())
+    print(f"{what}: max|sweep - ref| = {err:.3e} (bound {bound:.3e}, |ref|.max() = {np.abs(ref).max():.3e})")
+    assert np.isfinite(x).all()
+    assert err <= bound, f"{what}: {err:.3e} > {bound:.3e}"
+
+
+def make_shift(rng, W, S):
+    """[W x S x 2]: shift 0 all-zero, d ~ Gamma(1, 10)/2, e ~ U(0, 50)."""
+    sh = np.stack([rng.gamma(1.0, 10.0, size=(W, S)) / 2, rng.uniform(0.0, 50.0, size=(W, S))], axis=2)
+    sh[:, 0, :] = 0.0
+    return sh
+
+
+def layouts(inp, seed):
+    """(name, panel, upload kwargs, oracle kwargs) of the contiguous layout and of one with row_idx / n_rows / col_idx /
+    rf_adj over a panel with 8 more columns to choose from (tests/test_gpu_solve_sweep.py::layouts)."""
+    k, W, n_r = inp["k"], inp["W"], inp["n_r"]
+    cont = dict(start=inp["start"], hf_panel=inp["hf_panel"], hf_start=inp["hf_start"], w0=inp["w0"], n0=inp["n0"])
+    yield "contiguous", inp["panel"], cont, dict(cont, n_r=n_r, m=inp["m"])
+    rng = np.random.default_rng(seed)
+    P = np.concatenate([inp["panel"], rng.normal(0.0, 0.01, size=(inp["panel"].shape[0], 8))], axis=1)
+    H = np.concatenate([inp["hf_panel"], rng.normal(0.0, 0.001, size=(inp["hf_panel"].shape[0], 8))], axis=1)
+    col_idx = np.stack([rng.permutation(P.shape[1])[:k] for _ in range(W)]).astype(np.int32)
+    row_idx = np.stack([inp["start"][w] + np.sort(rng.choice(n_r, n_r, replace=False)) for w in range(W)]).astype(np.int32)
+    n_rows = rng.integers(max(k, n_r - 5), n_r + 1, size=W).astype(np.int32)
+    rf_adj = rng.normal(0, 1e-4, size=(W, n_r))
+    idx = dict(row_idx=row_idx, n_rows=n_rows, col_idx=col_idx, rf_adj=rf_adj, hf_panel=H, hf_start=inp["hf_start"],
+               w0=inp["w0"], n0=inp["n0"])
+    yield "index", P, idx, dict(idx, start=None, n_r=n_r, m=inp["m"])
+
+
+def window_rows(panel, okw, k, w):
+    """X of window w, sliced the way oracle.posterior_batch slices it."""
+    nr = int(okw["n_rows"][w]) if okw.get("n_rows") is not None else okw["n_r"]
+    rows = (np.asarray(okw["row_idx"][w][:nr], dtype=np.int64) if okw.get("row_idx") is not None
+            else np.arange(okw["start"][w], okw["start"][w] + nr))
+    cols = np.asarray(okw["col_idx"][w], dtype=np.int64) if okw.get("col_idx") is not None else np.arange(k)
+    X = panel[np.ix_(rows, cols)]
+    if okw.get("rf_adj") is not None:
+        X = X - np.asarray(okw["rf_adj"][w][:nr])[:, None]
+    return X, cols
+
+
+def jeffreys_upload_kw(ukw):
+    return {key: val for key, val in ukw.items() if key not in ("hf_panel", "hf_start", "w0", "n0")}
+
+
+def jeffreys_reference(k, N, panel, okw, shift, rhs, no_center, default_rhs=True):
+    """oracle.posterior_batch once per (s, r)."""
+    W, S = shift.shape[:2]
+    cols_rhs = ([None] if default_rhs else []) + [rhs[:, j, :] for j in range(rhs.shape[1])]
+    ref = np.empty((W, S, len(cols_rhs), k))
+    jkw = {key: val for key, val in okw.items() if key not in ("hf_panel", "hf_start", "w0", "n0", "m")}
+    for s in range(S):
+        for r, col in enumerate(cols_rhs):
+            wts, status, _ = oracle.posterior_batch("jeffreys", k, N, GAMMA, panel, rhs=col, shift=shift[:, s, :],
+                                                    no_center=no_center, **jkw)
+            assert (status == 0).all()
+            ref[:, s, r, :] = wts
+    return ref
+
+
+def jeffreys_batch(dev, inp, k, N, windows=None, flags=_native.FLAG_NO_CENTER):
+    ws = np.arange(inp["W"]) if windows is None else np.asarray(windows)
+    b = dev.batch("jeffreys", k, N, inp["n_r"], GAMMA, len(ws), 0, flags)
+    b.upload(inp["panel"], start=inp["start"][ws])
+    return b
+
+
+# ---- 1. Jeffreys against the oracle ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("k,N,R", SHAPES)
+@pytest.mark.parametrize("no_center", [True, False])
+def test_jeffreys_tiled_sweep_matches_oracle(dev, k, N, R, no_center):
+    inp = synthetic.make_kernel_inputs(k, N, W, seed=910000 + k)
+    rng = np.random.default_rng(910000 + k)
+    shift = make_shift(rng, W, S)
+    rhs = rng.normal(size=(W, R - 1, k))
+    for name, panel, ukw, okw in layouts(inp, 910000 + k):
+        b = dev.batch("jeffreys", k, N, inp["n_r"], GAMMA, W, 0, _native.FLAG_NO_CENTER if no_center else 0)
+        b.upload(panel, **jeffreys_upload_kw(ukw))
+        x, status = b.solve_sweep_tiled(shift=shift, rhs=rhs if R > 1 else None)
+        b.close()
+        assert x.shape == (W, S, R, k) and status.shape == (W, S)
+        assert (status == _native.STATUS_OK).all()
+        assert_close(x, jeffreys_reference(k, N, panel, okw, shift, rhs, no_center), what=f"jeffreys k={k} R={R} {name}")
+
+
+# ---- 2. conjugate against the oracle --------------------------------------------------------------------------------
+@pytest.mark.parametrize("k,N,R", SHAPES)
+def test_conjugate_tiled_sweep_matches_numpy_solve_of_oracle_S1(dev, k, N, R):
+    inp = synthetic.make_kernel_inputs(k, N, W, seed=911000 + k)
+    rng = np.random.default_rng(911000 + k)
+    rhs = rng.normal(size=(W, R - 1, k))
+    for name, panel, ukw, okw in layouts(inp, 911000 + k):
+        b = dev.batch("conjugate", k, N, inp["n_r"], GAMMA, W, inp["m"])
+        b.upload(panel, **ukw)
+        x, status = b.solve_sweep_tiled(rhs=rhs if R > 1 else None)
+        rhs0 = b.download_sweep_rhs()
+        b.close()
+        assert x.shape == (W, 1, R, k) and (status == _native.STATUS_OK).all()
+        ref = np.empty_like(x)
+        for w in range(W):
+            X, cols = window_rows(panel, okw, k, w)
+            Y = okw["hf_panel"][np.ix_(np.arange(okw["hf_start"][w], okw["hf_start"][w] + inp["m"]), cols)]
+            a = oracle.conjugate_window(X, Y, inp["w0"][w], float(inp["n0"][w]), N, k, GAMMA, return_aux=True)[1]
+            b0 = a["c"] * (a["S0"] @ inp["w0"][w]) + a["t"]
+            assert np.abs(rhs0[w] - b0).max() <= 1e-12 * max(1.0, np.abs(b0).max())
+            for r, col in enumerate([b0] + [rhs[w, j] for j in range(R - 1)]):
+                ref[w, 0, r] = np.linalg.solve(a["S1"], col) / GAMMA
+        assert_close(x, ref, what=f"conjugate k={k} R={R} {name}")
+
+
+# ---- 3. against the existing device path ----------------------------------------------------------------------------
+@pytest.mark.parametrize("k,N", [(190, 250), (256, 320)])
+def test_single_tiled_solve_agrees_with_set_rhs_set_shift_run(dev, k, N):
+    """Not bit for bit: the sweep's arena geometry (KP from k + R) may differ from the run's (KP from k + 1)."""
+    inp = synthetic.make_kernel_inputs(k, N, W, seed=912000 + k)
+    rng = np.random.default_rng(912000 + k)
+    shift = make_shift(rng, W, 2)[:, 1:, :]
+    rhs = rng.normal(size=(W, 1, k))
+    b = jeffreys_batch(dev, inp, k, N)
+    x, status = b.solve_sweep_tiled(shift=shift, rhs=rhs, default_rhs=False)
+    b.set_rhs(rhs[:, 0, :]).set_shift(shift[:, 0, :])
+    wts, wstatus, _ = b.run().download(want_aux=False)
+    b.close()
+    assert x.shape == (W, 1, 1, k)
+    assert (status[:, 0] == wstatus).all() and (wstatus == _native.STATUS_OK).all()
+    assert_close(x[:, 0, 0, :], wts, what=f"sweep vs run k={k}")
+
+
+# ---- 3b. every form of the block steps carries the right-hand-side columns ------------------------------------------
+@pytest.mark.parametrize("k,N,R", [(256, 320, 5), (300, 360, 3)])
+@pytest.mark.parametrize("options", [{"tiled_wave": 0}, {"tiled_fuse": 0}, {"tiled_wave": 0, "tiled_fuse": 0}],
+                         ids=["wave0", "fuse0", "wave0-fuse0"])
+def test_block_step_variants_carry_every_rhs_column(dev, k, N, R, options):
+    """tiled_wave = 0: tiled_diag_kernel, and MODE_SYRK_DIAG in front of it while fused; tiled_fuse = 0: MODE_SYRK over the whole
+    block row + MODE_TRSM.  (256, 5): the right-hand sides are a super-tile column of their own, which only the off-diagonal
+    kernels touch; (300, 3): they share the last pivot block's tile, which the diagonal kernels solve.  Same oracle, same bound
+    as the default options."""
+    inp = synthetic.make_kernel_inputs(k, N, W, seed=912500 + k)
+    rng = np.random.default_rng(912500 + k)
+    shift = make_shift(rng, W, S)
+    rhs = rng.normal(size=(W, R - 1, k))
+    b = jeffreys_batch(dev, inp, k, N)
+    for name, value in options.items():
+        dev.set_option(name, value)
+    try:
+        x, status = b.solve_sweep_tiled(shift=shift, rhs=rhs)
+    finally:
+        for name in options:
+            dev.set_option(name, -1)
+        b.close()
+    assert (status == _native.STATUS_OK).all()
+    okw = dict(start=inp["start"], n_r=inp["n_r"])
+    assert_close(x, jeffreys_reference(k, N, inp["panel"], okw, shift, rhs, True), what=f"k={k} R={R} {options}")
+
+
+# ---- 4. bit-identical results ---------------------------------------------------------------------------------------
+def test_tiled_sweep_is_independent_of_W_S_position_chunking_and_arena(dev):
+    k, N, R, W5 = 190, 250, 3, 5
+    inp = synthetic.make_kernel_inputs(k, N, W5, seed=913000)
+    rng = np.random.default_rng(913000)
+    shift = make_shift(rng, W5, S)
+    rhs = rng.normal(size=(W5, R - 1, k))
+
+    def sweep(windows, sh, chunk=0, arena_mib=0):
+        dev.set_option("sweep_chunk_windows", chunk)
+        dev.set_option("tiled_arena_mib", arena_mib)
+        try:
+            ws = np.asarray(windows)
+            b = jeffreys_batch(dev, inp, k, N, ws)
+            out = b.solve_sweep_tiled(shift=sh[ws], rhs=rhs[ws])
+            b.close()
+            return out
+        finally:
+            dev.set_option("sweep_chunk_windows", 0)
+            dev.set_option("tiled_arena_mib", 0)
+
+    every = np.arange(W5)
+    x5, s5 = sweep(every, shift)
+    assert (s5 == _native.STATUS_OK).all()
+    for w in (0, 3):                                       # W = 1 against 5
+        x1, s1 = sweep([w], shift)
+        assert np.array_equal(x1[0], x5[w]) and np.array_equal(s1[0], s5[w])
+    for s in (0, 2):                                       # S = 1 against 4
+        xs, ss = sweep(every, shift[:, s:s + 1, :])
+        assert np.array_equal(xs[:, 0], x5[:, s]) and np.array_equal(ss[:, 0], s5[:, s])
+    xr, sr = sweep(every[::-1], shift)                     # every window but the middle one at another position
+    assert np.array_equal(xr[::-1], x5) and np.array_equal(sr[::-1], s5)
+    xc, sc = sweep(every, shift, chunk=1)                  # sub-ranges of 1 window against automatic
+    assert np.array_equal(xc, x5) and np.array_equal(sc, s5)
+    # an entry is 8 (256^2 + 3 x 4096) + 4 bytes = 0.6 MB: 2 MiB hold 3 of the 20 entries, 1 MiB one
+    for mib in (1, 2):
+        xa, sa = sweep(every, shift, arena_mib=mib)
+        assert np.array_equal(xa, x5) and np.array_equal(sa, s5)
+
+
+# ---- 5. statuses ----------------------------------------------------------------------------------------------------
+def test_tiled_nan_row_flags_every_shift_of_its_window_only(dev):
+    """A NaN in the window's rows makes its first pivot a NaN, which is "not > 0": the tiled run's TP_STATUS_NOT_PD."""
+    k, N, R = 150, 200, 2
+    inp = synthetic.make_kernel_inputs(k, N, W, seed=914000)
+    rng = np.random.default_rng(914000)
+    shift = make_shift(rng, W, S)
+    rhs = rng.normal(size=(W, R - 1, k))
+    row_idx = (inp["start"][:, None] + np.arange(inp["n_r"])[None, :]).astype(np.int32)
+
+    def sweep(panel, ridx):
+        b = dev.batch("jeffreys", k, N, inp["n_r"], GAMMA, W, 0, _native.FLAG_NO_CENTER)
+        b.upload(panel, row_idx=ridx)
+        out = b.solve_sweep_tiled(shift=shift, rhs=rhs)
+        b.close()
+        return out
+
+    x_clean, s_clean = sweep(inp["panel"], row_idx)
+    assert (s_clean == _native.STATUS_OK).all()
+    bad_idx = row_idx.copy()
+    bad_idx[1, 7] = inp["panel"].shape[0]                  # window 1 alone reads the extra row
+    x, status = sweep(np.concatenate([inp["panel"], np.full((1, k), np.nan)], axis=0), bad_idx)
+    assert (status[1] == _native.STATUS_NOT_PD).all(), status
+    assert np.array_equal(status[[0, 2]], s_clean[[0, 2]]) and np.array_equal(x[[0, 2]], x_clean[[0, 2]])
+
+
+def test_tiled_duplicate_column_is_not_pd_unshifted_and_solved_when_shifted(dev):
+    k, N, R = 150, 200, 2
+    inp = synthetic.make_kernel_inputs(k, N, W, seed=914100)
+    rng = np.random.default_rng(914100)
+    col_idx = np.tile(np.arange(k, dtype=np.int32), (W, 1))
+    col_idx[1, 70] = col_idx[1, 4]                         # window 1: two identical columns -> T is singular
+    row_idx = (inp["start"][:, None] + np.arange(inp["n_r"])[None, :]).astype(np.int32)
+    shift = np.tile(np.array([[0.0, 0.0], [0.5, 0.0], [2.0, 3.0]]), (W, 1, 1))
+    rhs = rng.normal(size=(W, R - 1, k))
+    b = dev.batch("jeffreys", k, N, inp["n_r"], GAMMA, W, 0, _native.FLAG_NO_CENTER)
+    b.upload(inp["panel"], row_idx=row_idx, col_idx=col_idx)
+    x, status = b.solve_sweep_tiled(shift=shift, rhs=rhs)
+    b.close()
+    assert status[1, 0] == _native.STATUS_NOT_PD, status
+    assert (np.delete(status.reshape(-1), 3) == _native.STATUS_OK).all(), status
+    X = inp["panel"][np.ix_(row_idx[1], col_idx[1])]
+    T, t = X.T @ X, X.sum(axis=0)
+    ref = np.empty((2, R, k))
+    for s in (1, 2):
+        M = T + shift[1, s, 0] * np.eye(k) + shift[1, s, 1] * np.ones((k, k))
+        ref[s - 1, 0] = np.linalg.solve(M, t) / GAMMA
+        ref[s - 1, 1] = np.linalg.solve(M, rhs[1, 0]) / GAMMA
+    assert_close(x[1, 1:], ref, what="duplicate column, shifted")
+
+
+# ---- 6. the batch is left alone -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("strategy", ["conjugate", "jeffreys"])
+def test_tiled_sweep_leaves_the_batch_alone(dev, strategy):
+    k, N = 150, 200
+    inp = synthetic.make_kernel_inputs(k, N, W, seed=915000)
+    rng = np.random.default_rng(915000)
+    b = dev.batch(strategy, k, N, inp["n_r"], GAMMA, W, inp["m"])
+    b.upload(inp["panel"], start=inp["start"], hf_panel=inp["hf_panel"], hf_start=inp["hf_start"], w0=inp["w0"], n0=inp["n0"])
+    b.set_rhs(rng.normal(size=(W, k)))
+    if strategy == "jeffreys":
+        b.set_shift(make_shift(rng, W, 2)[:, 1, :])
+    b.keep_posterior(1, 2).keep_rhs().run()
+    before = (*b.download(), b.download_posterior(), b.download_rhs())
+    launch = dev.last_launch()
+    sh = make_shift(rng, W, 3) if strategy == "jeffreys" else None
+    rhs = rng.normal(size=(W, 2, k))
+    swept = b.solve_sweep_tiled(shift=sh, rhs=rhs)
+    assert (swept[1] == _native.STATUS_OK).all()
+    assert dev.last_launch() == launch
+    after = (*b.download(), b.download_posterior(), b.download_rhs())
+    for x, y in zip(before, after):
+        assert np.array_equal(x, y, equal_nan=True)
+    b.run()
+    assert dev.last_launch() == launch
+    again = (*b.download(), b.download_posterior(), b.download_rhs())
+    for x, y in zip(before, again):
+        assert np.array_equal(x, y, equal_nan=True)
+    resweep = b.solve_sweep_tiled(shift=sh, rhs=rhs)
+    b.close()
+    for x, y in zip(swept, resweep):
+        assert np.array_equal(x, y)
+
+
+# ---- 7. timing ------------------------------------------------------------------------------------------------------
+def test_tiled_sweep_is_one_timed_step(dev):
+    k, N, R = 150, 200, 2
+    inp = synthetic.make_kernel_inputs(k, N, W, seed=916000)
+    rng = np.random.default_rng(916000)
+    b = jeffreys_batch(dev, inp, k, N)
+    dev.set_option("sweep_chunk_windows", 2)               # two sub-ranges, still one step
+    try:
+        dev.region_begin()
+        b.solve_sweep_tiled(shift=make_shift(rng, W, S), rhs=rng.normal(size=(W, R - 1, k)))
+        dev.region_end()
+    finally:
+        dev.set_option("sweep_chunk_windows", 0)
+    steps = dev.region_steps()
+    b.close()
+    assert len(steps) == 1 and steps[0] > 0 and dev.last_timing()["kernel_ms"] > 0
+
+
+# ---- 8. the contract ------------------------------------------------------------------------------------------------
+def test_tiled_sweep_contract(dev):
+    k, N = 144, 200
+    inp = synthetic.make_kernel_inputs(k, N, W, seed=917000)
+    rng = np.random.default_rng(917000)
+    lib, c_double, c_int32, ptr = _native.lib, _native.c_double, _native.c_int32, _native._ptr
+
+    def code(fn):
+        with pytest.raises(_native.TangencyError) as e:
+            fn()
+        return e.value.code
+
+    b = dev.batch("jeffreys", k, N, inp["n_r"], GAMMA, W)
+    x_buf, s_buf = np.empty((W, 1, 1, k)), np.empty((W, 1), dtype=np.int32)
+    assert code(lambda: b.solve_sweep_tiled()) == _native.TP_ERR_INVALID                     # not uploaded
+    b.upload(inp["panel"], start=inp["start"])
+    assert lib.tp_batch_download_sweep(b._b, ptr(x_buf, c_double), ptr(s_buf, c_int32)) == _native.TP_ERR_INVALID   # no sweep yet
+    assert code(lambda: b.download_sweep_rhs()) == _native.TP_ERR_INVALID
+    for bad in (-1e-3, np.nan, np.inf):                                                      # d, e finite and >= 0
+        sh = make_shift(rng, W, 3)
+        sh[2, 1, 1] = bad
+        assert code(lambda: b.solve_sweep_tiled(shift=sh)) == _native.TP_ERR_INVALID
+    sh = make_shift(rng, W, 3)
+    assert lib.tp_batch_solve_sweep_tiled(b._b, -1, ptr(sh, c_double), 0, None, 1) == _native.TP_ERR_INVALID
+    assert lib.tp_batch_solve_sweep_tiled(b._b, 0, ptr(sh, c_double), 0, None, 1) == _native.TP_ERR_INVALID    # shift with n_shift = 0
+    assert lib.tp_batch_solve_sweep_tiled(b._b, 3, None, 0, None, 1) == _native.TP_ERR_INVALID                 # n_shift > 1 without shift
+    assert lib.tp_batch_solve_sweep_tiled(b._b, 0, None, 0, None, 0) == _native.TP_ERR_INVALID                 # R = 0
+    r17 = rng.normal(size=(W, 17, k))
+    assert lib.tp_batch_solve_sweep_tiled(b._b, 0, None, 17, ptr(r17, c_double), 0) == _native.TP_ERR_INVALID
+    assert lib.tp_batch_solve_sweep_tiled(b._b, 0, None, 16, ptr(r17, c_double), 1) == _native.TP_ERR_INVALID
+    assert lib.tp_batch_solve_sweep_tiled(b._b, 0, None, -1, None, 1) == _native.TP_ERR_INVALID
+    assert lib.tp_batch_solve_sweep_tiled(b._b, 0, None, 2, None, 1) == _native.TP_ERR_INVALID                 # n_rhs without rhs
+    assert lib.tp_batch_solve_sweep_tiled(None, 0, None, 0, None, 1) == _native.TP_ERR_INVALID
+    assert lib.tp_batch_download_sweep(b._b, ptr(x_buf, c_double), ptr(s_buf, c_int32)) == _native.TP_ERR_INVALID   # still none that ran
+    assert code(lambda: b.solve_sweep()) == _native.TP_ERR_UNSUPPORTED                       # k = 144: the LDS sweep keeps refusing
+    # it works, into pinned arrays, and R = 16 without the default equals the 15 columns behind it
+    out = (_native.pinned_empty((W, 3, 16, k)), _native.pinned_empty((W, 3), np.int32))
+    x, status = b.solve_sweep_tiled(shift=sh, rhs=r17[:, :15], out=out)
+    assert x is out[0] and status is out[1] and (status == 0).all()
+    x2, _ = b.solve_sweep_tiled(shift=sh, rhs=r17[:, :16], default_rhs=False)
+    assert np.array_equal(x2[:, :, :15], x[:, :, 1:])
+    X = inp["panel"][inp["start"][1]:inp["start"][1] + inp["n_r"]]
+    assert np.abs(b.download_sweep_rhs()[1] - X.sum(axis=0)).max() <= 1e-13
+    b.close()
+    # a shift on a conjugate batch
+    c = dev.batch("conjugate", k, N, inp["n_r"], GAMMA, W, inp["m"])
+    c.upload(inp["panel"], start=inp["start"], hf_panel=inp["hf_panel"], hf_start=inp["hf_start"], w0=inp["w0"], n0=inp["n0"])
+    with pytest.raises(_native.TangencyError) as e:
+        c.solve_sweep_tiled(shift=np.zeros((W, 1, 2)))
+    assert e.value.code == _native.TP_ERR_INVALID and "Jeffreys strategy only" in str(e.value)
+    c.close()
+    # k = 143: tp_batch_solve_sweep's range
+    ks = _native.sweep_max_assets()
+    assert ks == 143
+    small = synthetic.make_kernel_inputs(ks, 200, 1, seed=917001)
+    g = dev.batch("jeffreys", ks, 200, small["n_r"], GAMMA, 1)
+    g.upload(small["panel"], start=small["start"])
+    assert code(lambda: g.solve_sweep_tiled()) == _native.TP_ERR_UNSUPPORTED
+    assert (g.solve_sweep()[1] == 0).all()
+    g.close()
+    # k + R > max_assets() + 1: the arena side would exceed 2048 (refused before anything is allocated or launched)
+    kb = _native.max_assets() - 1                                                             # 2046: R = 2 fits, R = 3 does not
+    rowsb = kb + 10
+    big = np.random.default_rng(917002).normal(0.0, 0.01, size=(rowsb, kb))
+    h = dev.batch("jeffreys", kb, rowsb, rowsb, GAMMA, 1)
+    h.upload(big, start=np.zeros(1, np.int64))
+    assert code(lambda: h.solve_sweep_tiled(rhs=np.ones((1, 2, kb)))) == _native.TP_ERR_UNSUPPORTED
+    assert code(lambda: h.solve_sweep_tiled(rhs=np.ones((1, 3, kb)), default_rhs=False)) == _native.TP_ERR_UNSUPPORTED
+    h.close()
+
+
+# ---- 9. Greyserman --------------------------------------------------------------------------------------------------
+def _spec(strat, size, N):
+    return {"weighting_strategy": strat, "size": size, "risk_aversion": 5, "turnover_cost": 15,
+            "rebalancing_frequency": "daily", "rolling_window": N, "rolling_window_frequency": "daily",
+            "mcm_scaling": None, "display_name": strat}
+
+
+def test_greyserman_switch_takes_the_tiled_sweep(monkeypatch):
+    from incorporating_different_sources_amd import batch, portfolio_calculations as pc
+    size, N, dates_n, draws_n = 150, 180, 3, 16
+    assert size > _native.sweep_max_assets()
+    md, _ = synthetic.make_market_data(n_tickers=size + 4, n_days=N + 40, seed=20240091)
+    days = md["stock_prices_df"].index
+    dates = list(days[N + 5::7])[:dates_n]
+    assert len(dates) == dates_n
+    kw, _ = batch.pack_windows(dates, _spec("jeffreys", size, N), md, members_of=pc._members_provider(md))
+    rng = np.random.default_rng(918000)
+    draws = (rng.uniform(-1000, 1000, size=(dates_n, draws_n)), rng.gamma(1.0, 10.0, size=(dates_n, draws_n)))
+    calls = []
+    real = _native.Batch.solve_sweep_tiled
+    monkeypatch.setattr(_native.Batch, "solve_sweep_tiled",
+                        lambda self, **kws: (calls.append(kws["shift"].shape), real(self, **kws))[1])
+    assert pc.GREYSERMAN_TILED_SWEEP is False
+    off = pc._greyserman_batch(kw, 5.0, size, N, draws=draws)
+    assert calls == []                                     # switch off: the replicated batch, never the tiled sweep
+    monkeypatch.setattr(pc, "GREYSERMAN_TILED_SWEEP", True)
+    on = pc._greyserman_batch(kw, 5.0, size, N, draws=draws)
+    assert calls == [(dates_n, draws_n, 2)]                # ONE tiled sweep: S = draws (R = 2: t and 1)
+    assert off.shape == (dates_n, size) and np.isfinite(off).all()
+    bound = 1e-6 * float(np.abs(off).max())                # the project's Greyserman bound (tests/test_gpu_boundary.py)
+    err = float(np.abs(on - off).max())
+    print(f"greyserman k={size}: max|tiled sweep - replicated| = {err:.3e} (bound {bound:.3e})")
+    assert err <= bound
