@@ -326,6 +326,45 @@ int tp_batch_prior_sweep_tiled(tp_batch_t b, int32_t n_prior, const double* n0 /
  * slots of tp_batch_download's aux); each may be NULL.  Without a prior sweep (of either kind) before it:
  * TP_ERR_INVALID. */
 int tp_batch_download_prior_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux);
+/* Size sweep: n_size nested universes per window - the first sizes[0] < sizes[1] < ... <= k columns of the batch's universe -
+ * from ONE pair of Grams and ONE factorisation per (window, prior): the `sizes` axis of a spec grid (ref:247-267) without a
+ * pack, an upload and a batch per size.  It rests on the columns being ordered so that the smaller universe IS a prefix of the
+ * larger one (select_universe returns the largest caps in descending order); the caller vouches for that - and for the
+ * windows' rows being those the smaller universe would have had (batch.pack_windows_nested checks both).
+ * Conjugate batch, prior p, size s with k_s = sizes[s]; C, T, t, m and a = n0_wp m/(m-1) as in tp_batch_prior_sweep:
+ *     S1 = (a C + T)[:k_s,:k_s] ;  v = C[:k_s,:k_s] w0_wps[:k_s] ;  q0 = a w0_wps'v
+ *     c = 2 n0_wp / (g + sqrt(g^2 + 4 n0_wp q0)),  g = n0_wp + k_s + 2 ;  w1 = S1^-1 (c a v + t[:k_s]) ;  n1 = n0_wp + N
+ *     weights[w][p][s][:k_s] = (n1 + k_s + 2) w1 / (n1 - w1'S1 w1) / gamma ,   weights[w][p][s][k_s:] = 0
+ * i.e. what tp_batch_run returns for a batch of size k_s over the prefix columns with (w0_wps, n0_wp) uploaded (not bit for
+ * bit: the factorisation differs).  Only the first k_s entries of a w0 vector are read; the rest may hold anything.
+ * Jeffreys batch: n_prior = 0, n0 = w0 = NULL, the outputs have P = 1: weights[w][0][s][:k_s] = M[:k_s,:k_s]^-1 t[:k_s] / gamma
+ * with M = T - t t'/N or the form TP_FLAG_CENTER_BY_ROWS / TP_FLAG_NO_CENTER selects.
+ * The batch's own uploaded w0 / n0 are not used, nor its tp_batch_set_rhs / tp_batch_set_shift.
+ * TP_ERR_INVALID: a batch that was not uploaded; n_size outside [1, TP_SWEEP_MAX_RHS]; sizes NULL or not strictly increasing
+ * within [1, k]; conjugate: n_prior < 1, n0 or w0 NULL, an n0 that is not finite and > 0, a non-finite w0 inside a prefix;
+ * Jeffreys: n_prior != 0 or a non-NULL n0 / w0.  TP_ERR_UNSUPPORTED: k > tp_sweep_max_assets() (also, conjugate: index-layout
+ * windows of more than about 10,000 rows).  TP_ERR_HIP: an allocation failed (the message names the byte count).
+ * How it runs: sub-ranges of windows as in tp_batch_prior_sweep ("sweep_chunk_windows").  Per sub-range the Gram pass of the
+ * prior sweep stores C, T and t (Jeffreys: the batch's own run kernel keeps M and t - it reads the daily inputs only); then one
+ * workgroup per (window, prior) forms the lower triangle at k with one extra row per size, factorises it once in LDS and
+ * back-substitutes every size over its own prefix.  The leading block of the factor is the factor of the leading block: a
+ * size's result depends on the window's rows, its prior, k_s and k only - not on the other sizes, W, n_prior, the positions or
+ * the sub-ranges.  A column at or beyond k_s - a duplicate, a zero column, a NaN - does not reach size s.
+ * Device memory: W x P x n_size x (2 k + 9) doubles of priors and results, [W x k] of t and the sub-range's matrices; kept
+ * until tp_batch_destroy.  Streams, the entry drain, timing (kernel_ms covers Gram passes and solves; one step of
+ * tp_region_steps), the gather hand-over and what the call leaves alone are as for tp_batch_prior_sweep; in addition
+ * tp_batch_download_prior_sweep returns what it returned before. */
+int tp_batch_size_sweep(tp_batch_t b, int32_t n_size, const int32_t* sizes /* [n_size] */,
+                        int32_t n_prior, const double* n0 /* [W x n_prior] */,
+                        const double* w0 /* [W x n_prior x n_size x k] */);
+/* Waits for the size sweep and copies out weights [W x P x n_size x k] (P = n_prior, 1 for a Jeffreys batch), status
+ * [W x P x n_size] - per size: TP_STATUS_NOT_PD when a pivot j < k_s is <= 0 or no larger than k_s 2^-52 times its diagonal
+ * element of S1 (of M); TP_STATUS_NONFINITE; TP_STATUS_BAD_DENOM (conjugate): n1 - w1'S1 w1 <= 0 - and aux
+ * [W x P x n_size x TP_AUX_STRIDE] (the slots of tp_batch_download's aux: for a Jeffreys batch 0 except slot 4, t'M^-1 t over
+ * the prefix); each may be NULL.  Without a size sweep before it: TP_ERR_INVALID. */
+int tp_batch_download_size_sweep(tp_batch_t b, double* weights /* [W x P x n_size x k] */,
+                                 int32_t* status /* [W x P x n_size] */,
+                                 double* aux /* [W x P x n_size x TP_AUX_STRIDE] */);
 int tp_batch_download(tp_batch_t b, double* weights /* [W x k] */, int32_t* status /* [W] */,
                       double* aux /* optional [W x TP_AUX_STRIDE] */); /* waits for the stream, D2H */
 int tp_batch_download_S1(tp_batch_t b, int64_t w, double* S1 /* [k x k] */); /* posterior scale matrix

@@ -384,6 +384,69 @@ def pack_windows(trading_dates, portfolio_spec, market_data, members_of=None, re
     return kw, labels
 
 
+def pack_windows_nested(trading_dates, portfolio_spec, sizes, market_data, members_of=None):
+    """`pack_windows` at max(sizes) for a size sweep (`_native.Batch.size_sweep`): (kw, labels, caps [W x k], mask [W x S]).
+    mask[w, s] says whether the universe of size sizes[s] at date w can be served from the pack as its first sizes[s] columns:
+      * the prefix IS that universe - `select_universe` at that size returns the same columns in the same order (verified, not
+        assumed), and its prices are complete over the window as pack_windows demands;
+      * the daily and intraday rows the reference's dropna leaves the smaller universe are those of the pack, i.e. no row was
+        dropped because of a NaN in a column beyond the prefix alone.
+    `portfolio_spec["size"]` is not read.  Raises what `pack_windows` raises at the largest size (fewer eligible stocks than
+    that at a date: ValueError)."""
+    sizes = [int(s) for s in sizes]
+    if not sizes or any(b <= a for a, b in zip(sizes, sizes[1:])) or sizes[0] < 1:
+        raise ValueError(f"sizes: a strictly increasing list of positive sizes expected, got {sizes}")
+    spec = dict(portfolio_spec, size=sizes[-1])
+    kw, labels, caps = pack_windows(trading_dates, spec, market_data, members_of=members_of, return_caps=True)
+    freq = spec["rolling_window_frequency"]
+    N = spec["rolling_window"]
+    conj = spec["weighting_strategy"].startswith("conjugate")
+    mp = panels_for(market_data, freq)
+    window_days = N * _TRADING_DAYS[freq]
+    all_members = np.ones(len(mp.tickers), dtype=bool)
+    mask = np.ones((len(trading_dates), len(sizes)), dtype=bool)
+
+    def only_beyond(nan_block, ks):
+        """some row has a NaN beyond column ks and none before it"""
+        return bool((nan_block[:, ks:].any(axis=1) & ~nan_block[:, :ks].any(axis=1)).any())
+
+    for w, ts in enumerate(trading_dates):
+        d = pd.Timestamp(ts).value
+        pos, members = _date_position_and_members(mp, ts, members_of, all_members)
+        cols = kw["col_idx"][w]
+        # candidate rows of the window before dropna, as pack_windows forms them, and where they are NaN per selected column
+        if freq == "daily":
+            first_price = max(0, pos - N + 1)
+            lab0, lab1 = first_price, pos
+            if (mp.L_nan_cum[pos + 1, cols] != mp.L_nan_cum[first_price + 1, cols]).any():
+                daily_nan = mp.L_nan[np.arange(first_price + 1, pos + 1, dtype=np.int64)][:, cols]
+            else:                                        # no NaN return of a selected asset in the window: nothing to gather
+                daily_nan = np.zeros((lab1 - lab0, len(cols)), dtype=bool)
+        else:
+            b = int(mp.bin_of[pos])
+            first_bin = max(0, b - N + 1)
+            daily_nan = mp.L_nan[np.arange(first_bin + 1, b, dtype=np.int64)][:, cols]
+            if b > first_bin:
+                daily_nan = np.vstack([daily_nan, _return_is_nan(mp.P[pos], mp.R[b - 1])[cols][None, :]])
+            lab0, lab1 = first_bin, b
+        daily_nan = daily_nan[~np.isnan(mp.rf_at_label[lab0 + 1:lab1 + 1])]      # a NaN risk-free day drops the row at any size
+        hf_nan = None
+        if conj:
+            span = _CALENDAR_DAYS[freq]
+            a = int(np.searchsorted(mp.hf_ns, d - span * _NS_PER_DAY + _NS_PER_DAY, side="right"))
+            end_of_day = pd.Timestamp(ts).replace(hour=23, minute=59, second=59).value
+            e = int(np.searchsorted(mp.hf_ns, min(d + _NS_PER_DAY, end_of_day), side="right"))
+            if e > a + 1 and mp.H_rownan_cum[e] != mp.H_rownan_cum[a + 1]:      # some bar of the span has a NaN somewhere
+                hf_nan = mp.H_nan[np.arange(a + 1, e, dtype=np.int64)][:, cols]
+            else:
+                hf_nan = np.zeros((0, len(cols)), dtype=bool)
+        for s, ks in enumerate(sizes[:-1]):
+            sub, _ = select_universe(mp, pos, ks, window_days, spec["rebalancing_frequency"], members)
+            mask[w, s] = (len(sub) == ks and np.array_equal(sub, cols[:ks]) and not only_beyond(daily_nan, ks)
+                          and not (conj and only_beyond(hf_nan, ks)))
+    return kw, labels, caps, mask
+
+
 def _prior_strength(mp, mcm, d, ts, N, scaling):
     """n0 = N * max(cur/avg, avg/cur) * mcm_scaling (ref:90-114, 247-267) from the cached MCM arrays."""
     pos = int(np.searchsorted(mcm["ns"], d, side="right")) - 1

@@ -1,6 +1,7 @@
 #pragma once
-// posterior_sweep_solve.h - the LDS factorisation and back substitution the two sweep kernels share (posterior_sweep.hip:
-// many shifts and right-hand sides; posterior_prior_sweep.hip: many conjugate priors).  One 256-thread workgroup owns one
+// posterior_sweep_solve.h - the LDS factorisation and back substitution the sweep kernels share (posterior_sweep.hip: many
+// shifts and right-hand sides; posterior_prior_sweep.hip: many conjugate priors; posterior_size_sweep.hip: nested universes,
+// solved over prefixes of one factorisation).  One 256-thread workgroup owns one
 // matrix: its lower triangle in PACKED storage, column by column, with R right-hand sides riding along as R extra rows,
 //
 //     column c holds rows i = c .. k + R - 1 at  off(c) + (i - c),   off(c) = c (k + R) - c (c - 1) / 2 .
@@ -56,6 +57,29 @@ __device__ __forceinline__ void sweep_back_substitute(const double* lds, int k, 
         for (int q = 0; q < SWEEP_XREGS; ++q) {
             const int i = lane + 64 * q;
             if (i > j && i < k) part += cj[i] * x[q];
+        }
+        const double xj = (cj[k + r] - wave_sum64(part)) / cj[j];
+#pragma unroll
+        for (int q = 0; q < SWEEP_XREGS; ++q)
+            if (lane + 64 * q == j) x[q] = xj;
+    }
+}
+
+// The same back substitution over the leading kp x kp block (posterior_size_sweep.hip): step j = kp-1 .. 0, the dot product
+// over j < i < kp, the right-hand side still in row k + r.  The leading block of the factor is the factor of the leading
+// block, and entry j of a forward-substituted row depends on columns <= j only, so this solves the first kp columns' own
+// system.  With kp = k it is sweep_back_substitute, operation for operation.
+__device__ __forceinline__ void sweep_back_substitute_prefix(const double* lds, int k, int H, int kp, int r, int lane,
+                                                             double (&x)[SWEEP_XREGS]) {
+#pragma unroll
+    for (int q = 0; q < SWEEP_XREGS; ++q) x[q] = 0.0;
+    for (int j = kp - 1; j >= 0; --j) {
+        const double* cj = lds + sweep_off(j, H) - j;
+        double part = 0.0;
+#pragma unroll
+        for (int q = 0; q < SWEEP_XREGS; ++q) {
+            const int i = lane + 64 * q;
+            if (i > j && i < kp) part += cj[i] * x[q];
         }
         const double xj = (cj[k + r] - wave_sum64(part)) / cj[j];
 #pragma unroll

@@ -925,26 +925,45 @@ int tp_batch_download_sweep_rhs(tp_batch_t b, double* rhs_out) {
     return download(h, {{rhs_out, b->sw_rhs0.p, sizeof(double) * (size_t)b->W * b->p.k}});
 }
 
-// What the two prior sweeps share - tp_batch_prior_sweep (`tiled` = false, k <= tp_sweep_max_assets()) and
-// tp_batch_prior_sweep_tiled (above it): the argument checks, the drain of the handle's stream, the windows per sub-range (C and
-// T: two k x k matrices per window inside TP_SWEEP_WORKSPACE_BYTES, never more than 2^30 (window, prior) pairs), the sweep's
-// buffers and the copies of the caller's arrays.  *chunk_out = 0: W = 0, nothing to launch (ps_P is set).
+// What the prior sweeps and the size sweep share - tp_batch_prior_sweep (`tiled` = false, k <= tp_sweep_max_assets()),
+// tp_batch_prior_sweep_tiled (above it) and tp_batch_size_sweep (`sz` given: n_size universes per (window, prior), buffers of its
+// own, a Jeffreys batch allowed - without priors): the argument checks, the drain of the handle's stream, the windows per
+// sub-range (C and T: two k x k matrices per window inside TP_SWEEP_WORKSPACE_BYTES, never more than 2^30 (window, prior) pairs),
+// the sweep's buffers and the copies of the caller's arrays.  *chunk_out = 0: W = 0, nothing to launch (the sweep's shape is set).
+struct SizeAxis { int32_t n_size; const int32_t* sizes; };
 static int prior_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_prior, const double* n0, const double* w0,
-                               int64_t* chunk_out) {
+                               int64_t* chunk_out, const SizeAxis* sz = nullptr) {
     tp_handle_t h = b->h;
     const int k = b->p.k;
     const int64_t W = b->W;
     *chunk_out = 0;
-    if (b->p.strategy != TP_STRATEGY_CONJUGATE) return fail(h, TP_ERR_INVALID, "%s applies to the conjugate strategy only", name);
+    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
+    if (!sz && !conj) return fail(h, TP_ERR_INVALID, "%s applies to the conjugate strategy only", name);
     if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
-    if (n_prior < 1) return fail(h, TP_ERR_INVALID, "%s: n_prior=%d < 1", name, n_prior);
-    if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "%s: %s is NULL", name, !n0 ? "n0" : "w0");
-    const int P = n_prior;
-    for (int64_t i = 0; i < W * P; ++i)
-        if (!(n0[i] > 0.0) || !std::isfinite(n0[i]))
-            return fail(h, TP_ERR_INVALID, "%s: n0[%lld] must be finite and > 0", name, (long long)i);
-    for (int64_t i = 0; i < W * P * k; ++i)
-        if (!std::isfinite(w0[i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)i);
+    if (sz) {
+        if (sz->n_size < 1 || sz->n_size > TP_SWEEP_MAX_RHS)
+            return fail(h, TP_ERR_INVALID, "%s: n_size=%d outside [1, %d]", name, sz->n_size, TP_SWEEP_MAX_RHS);
+        if (!sz->sizes) return fail(h, TP_ERR_INVALID, "%s: sizes is NULL", name);
+        for (int s = 0; s < sz->n_size; ++s)
+            if (sz->sizes[s] < 1 || sz->sizes[s] > k || (s > 0 && sz->sizes[s] <= sz->sizes[s - 1]))
+                return fail(h, TP_ERR_INVALID, "%s: sizes[%d]=%d: strictly increasing sizes within [1, %d] expected", name, s, sz->sizes[s], k);
+    }
+    if (sz && !conj && (n_prior != 0 || n0 || w0))
+        return fail(h, TP_ERR_INVALID, "%s: a Jeffreys batch takes no priors (n_prior = 0, n0 = w0 = NULL)", name);
+    const int P = conj ? n_prior : 1;
+    const int S = sz ? sz->n_size : 1;
+    if (conj) {
+        if (n_prior < 1) return fail(h, TP_ERR_INVALID, "%s: n_prior=%d < 1", name, n_prior);
+        if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "%s: %s is NULL", name, !n0 ? "n0" : "w0");
+        for (int64_t i = 0; i < W * P; ++i)
+            if (!(n0[i] > 0.0) || !std::isfinite(n0[i]))
+                return fail(h, TP_ERR_INVALID, "%s: n0[%lld] must be finite and > 0", name, (long long)i);
+        for (int64_t e = 0; e < W * P * S; ++e) {          // (a size sweep reads the first sizes[s] entries of a vector only)
+            const int ke = sz ? sz->sizes[e % S] : k;
+            for (int i = 0; i < ke; ++i)
+                if (!std::isfinite(w0[e * k + i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)(e * k + i));
+        }
+    }
     if (!tiled && k > tp_sweep_max_assets())
         return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d exceeds the sweep kernel's largest universe %d", name, k, tp_sweep_max_assets());
     if (tiled && k <= tp_sweep_max_assets())
@@ -956,8 +975,8 @@ static int prior_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     rc = harvest_kernel_time(h);
     if (rc != TP_OK) return rc;
-    b->ps_P = 0;
-    if (W == 0) { b->ps_P = P; return TP_OK; }
+    if (sz) { b->zs_P = 0; b->zs_S = 0; } else b->ps_P = 0;
+    if (W == 0) { if (sz) { b->zs_P = P; b->zs_S = S; } else b->ps_P = P; return TP_OK; }
     const size_t mat_bytes = sizeof(double) * (size_t)k * k;
     int64_t chunk = h->sweep_chunk_windows > 0 ? h->sweep_chunk_windows : (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes));
     if (chunk > (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes))) chunk = (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes));
@@ -965,22 +984,52 @@ static int prior_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32
     if (chunk < 1) chunk = 1;
     if (chunk > W) chunk = W;
     const size_t WP = (size_t)W * (size_t)P;
+    const size_t WPS = WP * (size_t)S;
     const std::string what = std::string(name) + ": ";
-    rc = ensure(h, b->ps_C, mat_bytes * (size_t)chunk, (what + "intraday scatters of one sub-range").c_str());
-    if (rc == TP_OK) rc = ensure(h, b->ps_T, mat_bytes * (size_t)chunk, (what + "daily Grams of one sub-range").c_str());
-    if (rc == TP_OK) rc = ensure(h, b->ps_t, sizeof(double) * (size_t)W * k, (what + "daily column sums").c_str());
-    if (rc == TP_OK) rc = ensure(h, b->ps_n0, sizeof(double) * WP, (what + "prior strengths").c_str());
-    if (rc == TP_OK) rc = ensure(h, b->ps_w0, sizeof(double) * WP * k, (what + "prior weights").c_str());
-    if (rc == TP_OK) rc = ensure(h, b->ps_weights, sizeof(double) * WP * k, (what + "weights").c_str());
-    if (rc == TP_OK) rc = ensure(h, b->ps_status, sizeof(int32_t) * WP, (what + "statuses").c_str());
-    if (rc == TP_OK) rc = ensure(h, b->ps_aux, sizeof(double) * WP * TP_AUX_STRIDE, (what + "aux").c_str());
+    DevBuf& dC = sz ? b->zs_C : b->ps_C;  DevBuf& dT = sz ? b->zs_T : b->ps_T;  DevBuf& dt = sz ? b->zs_t : b->ps_t;
+    DevBuf& dn0 = sz ? b->zs_n0 : b->ps_n0;  DevBuf& dw0 = sz ? b->zs_w0 : b->ps_w0;
+    DevBuf& dwts = sz ? b->zs_weights : b->ps_weights;  DevBuf& dst = sz ? b->zs_status : b->ps_status;  DevBuf& daux = sz ? b->zs_aux : b->ps_aux;
+    rc = TP_OK;
+    if (conj) rc = ensure(h, dC, mat_bytes * (size_t)chunk, (what + "intraday scatters of one sub-range").c_str());
+    if (rc == TP_OK) rc = ensure(h, dT, mat_bytes * (size_t)chunk, (what + (conj ? "daily Grams of one sub-range" : "matrices of one sub-range")).c_str());
+    if (rc == TP_OK) rc = ensure(h, dt, sizeof(double) * (size_t)W * k, (what + "daily column sums").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, dn0, sizeof(double) * WP, (what + "prior strengths").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, dw0, sizeof(double) * WPS * k, (what + "prior weights").c_str());
+    if (rc == TP_OK) rc = ensure(h, dwts, sizeof(double) * WPS * k, (what + "weights").c_str());
+    if (rc == TP_OK) rc = ensure(h, dst, sizeof(int32_t) * WPS, (what + "statuses").c_str());
+    if (rc == TP_OK) rc = ensure(h, daux, sizeof(double) * WPS * TP_AUX_STRIDE, (what + "aux").c_str());
+    if (rc == TP_OK && sz) rc = ensure(h, b->zs_sizes, sizeof(int32_t) * (size_t)S, (what + "sizes").c_str());
+    if (rc == TP_OK && sz && !conj) {                      // outputs of the run kernel that serves as the Gram pass
+        rc = ensure(h, b->zs_gw, sizeof(double) * (size_t)W * k, (what + "weights of the Gram pass").c_str());
+        if (rc == TP_OK) rc = ensure(h, b->zs_gs, sizeof(int32_t) * (size_t)W, (what + "statuses of the Gram pass").c_str());
+        if (rc == TP_OK) rc = ensure(h, b->zs_ga, sizeof(double) * (size_t)W * TP_AUX_STRIDE, (what + "aux of the Gram pass").c_str());
+    }
     if (rc != TP_OK) return rc;
     // the caller's arrays: copied here, no host pointer is kept
-    HIP_TRY(h, hipMemcpyAsync(b->ps_n0.p, n0, sizeof(double) * WP, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(b->ps_w0.p, w0, sizeof(double) * WP * k, hipMemcpyHostToDevice, h->stream));
+    if (conj) {
+        HIP_TRY(h, hipMemcpyAsync(dn0.p, n0, sizeof(double) * WP, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(dw0.p, w0, sizeof(double) * WPS * k, hipMemcpyHostToDevice, h->stream));
+    }
+    if (sz) HIP_TRY(h, hipMemcpyAsync(b->zs_sizes.p, sz->sizes, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
     *chunk_out = chunk;
     return TP_OK;
+}
+
+// Gram pass of a prior sweep or a conjugate size sweep: the windows' rows as a plain run reads them; no prior, no shared block
+// sums, none of the run's outputs
+static tp_gram_kargs_t prior_sweep_gram_kargs(tp_batch_t b, const DevBuf& C, const DevBuf& T, const DevBuf& t) {
+    tp_gram_kargs_t ga;
+    memset(&ga, 0, sizeof ga);
+    ga.in = make_kargs(b);
+    ga.in.w0 = nullptr; ga.in.n0 = nullptr;
+    ga.in.rhs = nullptr; ga.in.shift = nullptr;
+    ga.in.prefix = nullptr; ga.in.winsum = nullptr; ga.in.prefix_nblk = 0;
+    for (int i = 0; i < 4; ++i) ga.in.winsum_L[i] = 0;
+    ga.in.weights = nullptr; ga.in.status = nullptr; ga.in.aux = nullptr;
+    ga.in.out_rhs = nullptr; ga.in.out_post = nullptr; ga.in.post_count = 0; ga.in.stamps = nullptr;
+    ga.C = (double*)C.p; ga.T = (double*)T.p; ga.t = (double*)t.p;
+    return ga;
 }
 
 // Prior sweep.  Windows go through in sub-ranges of `chunk` windows: the Gram pass (posterior_gram_nt.hip) stores C and T of
@@ -996,17 +1045,7 @@ int tp_batch_prior_sweep(tp_batch_t b, int32_t n_prior, const double* n0, const 
     int rc = prior_sweep_prepare(b, "tp_batch_prior_sweep", false, n_prior, n0, w0, &chunk);
     if (rc != TP_OK || chunk == 0) return rc;
 
-    // Gram pass: the windows' rows as a plain run reads them; no prior, no shared block sums, none of the run's outputs
-    tp_gram_kargs_t ga;
-    memset(&ga, 0, sizeof ga);
-    ga.in = make_kargs(b);
-    ga.in.w0 = nullptr; ga.in.n0 = nullptr;
-    ga.in.rhs = nullptr; ga.in.shift = nullptr;
-    ga.in.prefix = nullptr; ga.in.winsum = nullptr; ga.in.prefix_nblk = 0;
-    for (int i = 0; i < 4; ++i) ga.in.winsum_L[i] = 0;
-    ga.in.weights = nullptr; ga.in.status = nullptr; ga.in.aux = nullptr;
-    ga.in.out_rhs = nullptr; ga.in.out_post = nullptr; ga.in.post_count = 0; ga.in.stamps = nullptr;
-    ga.C = (double*)b->ps_C.p; ga.T = (double*)b->ps_T.p; ga.t = (double*)b->ps_t.p;
+    tp_gram_kargs_t ga = prior_sweep_gram_kargs(b, b->ps_C, b->ps_T, b->ps_t);
     tp_prior_sweep_kargs_t sa;
     memset(&sa, 0, sizeof sa);
     sa.C = (const double*)b->ps_C.p; sa.T = (const double*)b->ps_T.p; sa.t = (const double*)b->ps_t.p;
@@ -1138,6 +1177,79 @@ int tp_batch_download_prior_sweep(tp_batch_t b, double* weights, int32_t* status
     const size_t n = (size_t)b->W * b->ps_P;           // (W = 0: nothing to copy)
     return download(h, {{weights, b->ps_weights.p, sizeof(double) * n * b->p.k}, {status, b->ps_status.p, sizeof(int32_t) * n},
                         {aux, b->ps_aux.p, sizeof(double) * n * TP_AUX_STRIDE}});
+}
+
+// Size sweep.  Sub-ranges as in tp_batch_prior_sweep.  Conjugate: the same Gram pass stores C, T and t.  Jeffreys: the batch's
+// own run kernel - as the solve sweep steers it: no custom right-hand side, no shift, no shared block sums, outputs into the
+// sweep's buffers - keeps M (its centring flag applied) and t; it reads the daily inputs only.  Then posterior_size_sweep_kernel
+// factorises every (window, prior) once at k and solves every size over its prefix.
+int tp_batch_size_sweep(tp_batch_t b, int32_t n_size, const int32_t* sizes, int32_t n_prior, const double* n0, const double* w0) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    const int k = b->p.k;
+    const int64_t W = b->W;
+    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
+    const int P = conj ? n_prior : 1;
+    const SizeAxis sz{n_size, sizes};
+    int64_t chunk = 0;
+    int rc = prior_sweep_prepare(b, "tp_batch_size_sweep", false, n_prior, n0, w0, &chunk, &sz);
+    if (rc != TP_OK || chunk == 0) return rc;
+    tp_gram_kargs_t ga = prior_sweep_gram_kargs(b, b->zs_C, b->zs_T, b->zs_t);
+    tp_kargs_t ja;
+    memset(&ja, 0, sizeof ja);
+    if (!conj) {
+        ja = solve_sweep_gram_kargs(b);
+        ja.weights = (double*)b->zs_gw.p; ja.status = (int*)b->zs_gs.p; ja.aux = (double*)b->zs_ga.p;
+        ja.out_rhs = (double*)b->zs_t.p; ja.out_post = (double*)b->zs_T.p;
+    }
+    tp_size_sweep_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.C = conj ? (const double*)b->zs_C.p : nullptr;
+    sa.T = (const double*)b->zs_T.p; sa.t = (const double*)b->zs_t.p;
+    sa.n0 = conj ? (const double*)b->zs_n0.p : nullptr; sa.w0 = conj ? (const double*)b->zs_w0.p : nullptr;
+    sa.hf_count = (const int*)b->hf_count.p;
+    sa.sizes = (const int*)b->zs_sizes.p;
+    sa.weights = (double*)b->zs_weights.p; sa.status = (int*)b->zs_status.p; sa.aux = (double*)b->zs_aux.p;
+    sa.k = k; sa.P = P; sa.S = n_size; sa.N = b->p.N; sa.m = b->p.m;
+    sa.gamma = b->p.gamma;
+    const tp_launch_info_t keep_launch = h->last_launch;      // tp_last_launch describes tp_batch_run launches
+    // one span around all launches: a sweep is one step of tp_region_steps, kernel_ms = Gram passes + solves
+    Span& span = timed_span(h);
+    HIP_TRY(h, span.begin(h->stream));
+    for (int64_t w0i = 0; w0i < W; w0i += chunk) {
+        const int64_t n = W - w0i < chunk ? W - w0i : chunk;
+        if (conj) {
+            ga.in.w_first = w0i; ga.in.w_count = n;
+            const hipError_t e = tp_gram_launch(ga, h->stream);
+            if (e == hipErrorNotSupported)
+                return fail(h, TP_ERR_UNSUPPORTED, "tp_batch_size_sweep: windows of %d daily / %d intraday rows in the index layout are "
+                                                   "too long for the Gram pass", b->p.n_r, b->p.m);
+            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "size sweep Gram launch failed: %s", hipGetErrorString(e));
+        } else {
+            ja.w_first = w0i; ja.w_count = n;
+            ja.post_w0 = w0i; ja.post_count = n;
+            rc = launch(b, ja, n, false);
+            h->last_launch = keep_launch;
+            if (rc != TP_OK) return rc;
+        }
+        sa.w_first = w0i; sa.w_count = n;
+        const hipError_t e = tp_size_sweep_launch(sa, h->stream);
+        if (e != hipSuccess) return fail(h, TP_ERR_HIP, "size sweep kernel launch failed: %s", hipGetErrorString(e));
+    }
+    rc = timed_done(h, span);
+    if (rc != TP_OK) return rc;
+    b->zs_P = P; b->zs_S = n_size;
+    return end_launches(b);                            // (the sweep reads the batch's inputs and writes none of its results)
+}
+
+int tp_batch_download_size_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    if (b->zs_P < 1 || b->zs_S < 1) return fail(h, TP_ERR_INVALID, "tp_batch_download_size_sweep: no tp_batch_size_sweep before it");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)b->W * b->zs_P * b->zs_S;  // (W = 0: nothing to copy)
+    return download(h, {{weights, b->zs_weights.p, sizeof(double) * n * b->p.k}, {status, b->zs_status.p, sizeof(int32_t) * n},
+                        {aux, b->zs_aux.p, sizeof(double) * n * TP_AUX_STRIDE}});
 }
 
 int tp_synchronize(tp_handle_t h) {

@@ -13,6 +13,7 @@
 #include "host_resources.h"
 #include "posterior_kernels.h"
 #include "posterior_prior_sweep.h"
+#include "posterior_size_sweep.h"
 #include "posterior_solve_sweep_tiled.h"
 
 #define TP_MAX_LANES 4
@@ -48,7 +49,7 @@ struct tp_handle_s {
     int tiled_arena_gib = 0;        // TP_TILED_ARENA_GIB / "tiled_arena_gib" (0: default)
     int tiled_arena_mib = 0;        // TP_TILED_ARENA_MIB / "tiled_arena_mib": a sub-GiB arena per lane (depth-first sub-batches)
     int tiled_lanes = 0;            // TP_TILED_LANES / "tiled_lanes": sub-batches in flight on streams of their own (0: default)
-    int sweep_chunk_windows = 0;    // "sweep_chunk_windows": windows per sub-range of tp_batch_solve_sweep / _prior_sweep (0: automatic)
+    int sweep_chunk_windows = 0;    // "sweep_chunk_windows": windows per sub-range of tp_batch_solve_sweep / _prior_sweep / _size_sweep (0: automatic)
     Stream lane_stream[TP_MAX_LANES];
     Event lane_done[TP_MAX_LANES];
     Event lane_start;
@@ -83,6 +84,10 @@ struct tp_batch_s {
     // prior sweep (tp_batch_prior_sweep): buffers of its own as well.  ps_C / ps_T hold the two Grams of ONE sub-range at a time
     DevBuf ps_C, ps_T, ps_t, ps_n0, ps_w0, ps_weights, ps_status, ps_aux;
     int ps_P = 0;                                             // priors per window of the last prior sweep (0: none yet)
+    // size sweep (tp_batch_size_sweep): buffers of its own again.  zs_C / zs_T hold the matrices of ONE sub-range at a time (a
+    // Jeffreys batch: M in zs_T, no zs_C); zs_gw / zs_gs / zs_ga take the outputs of the run kernel that serves as its Gram pass
+    DevBuf zs_C, zs_T, zs_t, zs_n0, zs_w0, zs_sizes, zs_weights, zs_status, zs_aux, zs_gw, zs_gs, zs_ga;
+    int zs_P = 0, zs_S = 0;                                   // shape of the last size sweep (0: none yet)
     PriceStaging fe, fe_hf;                                   // daily and intraday (freed after a synchronous upload)
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)

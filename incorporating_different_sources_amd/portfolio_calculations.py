@@ -989,6 +989,98 @@ def calculate_weights_for_specs(trading_dates, portfolio_specs_list, market_data
     return _fill_spec_cache(specs, trading_dates, market_data, weights, n_dates, same_gamma, labels, kw["col_idx"], caps)
 
 
+def _size_family(portfolio_spec):
+    """Specs with equal (window, frequencies) see the same dates' rows; `size` picks a prefix of the cap-ordered universe."""
+    return tuple(portfolio_spec.get(name) for name in ("rebalancing_frequency", "rolling_window", "rolling_window_frequency"))
+
+
+def calculate_weights_for_sizes(trading_dates, portfolio_specs_list, market_data):
+    """Weights of specs that differ in `size` (conjugate specs: also in the prior - vw / ew, VIX / EPU, mcm_scaling) for the
+    same dates with ONE host pack at the largest size (`batch.pack_windows_nested`), ONE upload and ONE size sweep
+    (`Batch.size_sweep`): every (window, prior) is factorised once and each size solved over its prefix of the cap-ordered
+    universe.  Conjugate specs only, or Jeffreys specs only, of one (window, frequencies) family.  (date, size) pairs the pack
+    cannot serve (its mask) and sizes above `_native.sweep_max_assets()` go through `_weights_for_dates` for that spec.
+    Returns one (weights, labels, cols, caps) per spec, each at its own size - equal to `_weights_for_dates` spec by spec
+    within the solve's rounding - and remembers the conjugate ones in the cache slots `calculate_weights_for_specs` fills.
+    When the pack at the largest swept size raises a ValueError - a date with fewer eligible stocks than that size, incomplete
+    prices of one of its stocks - nothing is swept: every spec runs `_weights_for_dates` on its own, so the smaller sizes are
+    still served and the reference's exception surfaces for the specs the reference would raise it for.
+    Opt-in: nothing calls it by default."""
+    specs = list(portfolio_specs_list)
+    if not specs:
+        return []
+    conj = specs[0]["weighting_strategy"] in _CONJUGATE
+    if (any((sp["weighting_strategy"] in _CONJUGATE) != conj or (not conj and sp["weighting_strategy"] != "jeffreys") for sp in specs)
+            or len({_size_family(sp) for sp in specs}) != 1):
+        raise ValueError("calculate_weights_for_sizes: conjugate specs, or Jeffreys specs, of equal window and frequencies expected")
+    trading_dates = list(trading_dates)
+    n_dates = len(trading_dates)
+    members_of = _members_provider(market_data)
+    N = specs[0]["rolling_window"]
+    gammas = [sp["risk_aversion"] for sp in specs]
+    same_gamma = all(g == gammas[0] for g in gammas)
+    sizes = sorted({int(sp["size"]) for sp in specs if sp["size"] <= _native.sweep_max_assets()})
+    swept = None
+    packed = None
+    if sizes:
+        try:
+            packed = batch.pack_windows_nested(trading_dates, specs[0], sizes, market_data, members_of=members_of)
+        except ValueError as exc:                        # see the docstring: the specs decide one by one what the caller sees
+            logger.warning(f"size sweep dropped ({exc}); solving the {len(specs)} specs one by one")
+    if packed is not None:
+        k = sizes[-1]
+        kw, labels, caps, mask = packed
+        n0 = w0 = None
+        prior_keys = []
+        if conj:
+            prior_of = lambda sp: (sp["weighting_strategy"], sp["mcm_scaling"])
+            prior_keys = list(dict.fromkeys(prior_of(sp) for sp in specs if sp["size"] <= k))
+            n0 = np.empty((n_dates, len(prior_keys)))
+            w0 = np.zeros((n_dates, len(prior_keys), len(sizes), k))
+            for p, key in enumerate(prior_keys):
+                sp = next(sp for sp in specs if prior_of(sp) == key)
+                wanted = {int(x["size"]) for x in specs if prior_of(x) == key}
+                for s, ks in enumerate(sizes):           # w0 over the prefix (ref:692-695 / 670-672); n0 does not depend on size
+                    if ks in wanted:
+                        w0[:, p, s, :ks], n0[:, p] = batch.prior_inputs(trading_dates, dict(sp, size=ks), market_data, caps[:, :ks])
+                    else:                                # no spec asks for this pair: any finite prior does, its result is not read
+                        w0[:, p, s, :ks] = 1.0 / ks
+        b = _native.Batch(_native.default_device(), "conjugate" if conj else "jeffreys", k, N, kw["n_r"],
+                          gammas[0] if same_gamma else 1.0, n_dates, kw.get("m") or 0)
+        try:
+            b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m", "w0", "n0")},
+                     **(dict(w0=kw["w0"], n0=kw["n0"]) if conj else {}))
+            weights, status, _ = b.size_sweep(sizes, n0, w0, want_aux=False)
+        finally:
+            b.close()
+        swept = (weights, status, labels, kw["col_idx"], caps, mask, prior_keys)
+    out = []
+    for sp in specs:
+        ks = int(sp["size"])
+        if swept is None or ks not in sizes:
+            res = _weights_for_dates(trading_dates, sp, market_data)
+        else:
+            weights, status, labels, cols, caps, mask, prior_keys = swept
+            s = sizes.index(ks)
+            p = prior_keys.index((sp["weighting_strategy"], sp["mcm_scaling"])) if conj else 0
+            ok = mask[:, s]
+            _raise_on_status(status[ok, p, s])
+            w = np.ascontiguousarray(weights[:, p, s, :ks])
+            if not same_gamma:
+                w = 1.0 / sp["risk_aversion"] * w
+            lab = [row[:ks] for row in labels]
+            res = (w, lab, np.ascontiguousarray(cols[:, :ks]), np.ascontiguousarray(caps[:, :ks]))
+            if not ok.all():                             # these dates' smaller universe is not the pack's prefix, or has other rows
+                miss = np.flatnonzero(~ok)
+                alone = _weights_for_dates([trading_dates[i] for i in miss], sp, market_data)
+                for j, i in enumerate(miss):
+                    res[0][i], res[1][i], res[2][i], res[3][i] = alone[0][j], alone[1][j], alone[2][j], alone[3][j]
+        if conj:
+            res = _fill_spec_cache([sp], trading_dates, market_data, res[0], n_dates, True, res[1], res[2], res[3])[0]
+        out.append(res)
+    return out
+
+
 def _replicated_weights(kw, priors, n_specs, k, N, gamma):
     """Every window once per spec in ONE device batch of n_specs x n_dates windows."""
     per_window = ("row_idx", "n_rows", "col_idx", "rf_adj", "hf_row_idx", "hf_count")
