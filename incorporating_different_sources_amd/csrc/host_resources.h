@@ -7,7 +7,7 @@
 #include <cstddef>
 
 // The one decision about device calls.  destroy_handle / destroy_batch decide ONCE whether the runtime still answers
-// (tangency_api.cpp) and clear this flag around their `delete`: the destructors below then drop their handles without a
+// (tangency_api.cpp: lifetime) and clear this flag around their `delete`: the destructors below then drop their handles without a
 // HIP call.  Thread-local: every host thread tears down its own objects.
 inline thread_local bool t_device_calls = true;
 

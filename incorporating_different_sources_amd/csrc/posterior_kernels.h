@@ -1,4 +1,4 @@
-// posterior_kernels.h - internal interface between the C-ABI (tangency_api.cpp) and the HIP kernels.
+// posterior_kernels.h - internal interface between the host layer (tangency_api.cpp, tangency_sweep.cpp) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

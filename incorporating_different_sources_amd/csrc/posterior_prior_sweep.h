@@ -1,4 +1,5 @@
-// posterior_prior_sweep.h - internal interface between the C-ABI (tangency_api.cpp) and the two kernels of the prior sweep.
+// posterior_prior_sweep.h - internal interface between the sweeps of the C-ABI (tangency_sweep.cpp) and the two kernels of the
+// prior sweep.
 #pragma once
 #include "posterior_kernels.h"
 

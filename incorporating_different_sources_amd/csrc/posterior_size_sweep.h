@@ -1,5 +1,5 @@
-// posterior_size_sweep.h - internal interface between the C-ABI (tangency_api.cpp) and the kernel of the size sweep
-// (posterior_size_sweep.hip).  The Gram passes are the existing ones: tp_gram_launch (posterior_prior_sweep.h) for a
+// posterior_size_sweep.h - internal interface between the sweeps of the C-ABI (tangency_sweep.cpp) and the kernel of the size
+// sweep (posterior_size_sweep.hip).  The Gram passes are the existing ones: tp_gram_launch (posterior_prior_sweep.h) for a
 // conjugate batch, the batch's own run kernel with its kept-matrix and kept-right-hand-side stores for a Jeffreys batch.
 #pragma once
 #include "posterior_kernels.h"

@@ -1,5 +1,5 @@
-// posterior_solve_sweep_tiled.h - internal interface between the C-ABI (tangency_api.cpp) and the two kernels of the solve
-// sweep on the large-k tiled path (posterior_solve_sweep_tiled.hip, tp_batch_solve_sweep_tiled).
+// posterior_solve_sweep_tiled.h - internal interface between the sweeps of the C-ABI (tangency_sweep.cpp) and the two kernels of
+// the solve sweep on the large-k tiled path (posterior_solve_sweep_tiled.hip, tp_batch_solve_sweep_tiled).
 #pragma once
 #include "posterior_kernels.h"
 

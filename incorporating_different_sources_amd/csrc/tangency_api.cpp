@@ -1,5 +1,5 @@
-// tangency_api.cpp - C-ABI of libtangency.so (include/tangency_posterior.h): contexts, device
-// buffers, launches, timing and the RCCL gather.  Compiled with hipcc; no kernels in this file.
+// tangency_api.cpp - C-ABI of libtangency.so (include/tangency_posterior.h): lifetime, uploads, runs, downloads, timing
+// and regions (the sweeps: tangency_sweep.cpp, the gather: tangency_comm.cpp).  Compiled with hipcc; no kernels in this file.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -107,7 +107,9 @@ int check_params(tp_handle_t h, const tp_params_t* p, int64_t W) {
     return TP_OK;
 }
 
-tp_kargs_t make_kargs(tp_batch_t b) {
+}  // namespace
+
+tp_kargs_t tp_host::make_kargs(tp_batch_t b) {
     tp_kargs_t a;
     memset(&a, 0, sizeof a);
     a.panel = (const double*)b->panel.p;
@@ -171,7 +173,7 @@ tp_kargs_t make_kargs(tp_batch_t b) {
     return a;
 }
 
-int ensure_lane_streams(tp_handle_t h, int lanes) {
+static int ensure_lane_streams(tp_handle_t h, int lanes) {
     HIP_TRY(h, h->lane_start.create(hipEventDisableTiming));
     for (int l = 0; l < lanes; ++l) {
         HIP_TRY(h, h->lane_stream[l].create());
@@ -180,20 +182,17 @@ int ensure_lane_streams(tp_handle_t h, int lanes) {
     return TP_OK;
 }
 
-// The span a timed launch uses: inside a region the next slot of the ring (read by tp_region_end) while slots remain,
-// the handle's kernel span otherwise.
-Span& timed_span(tp_handle_t h) {
+Span& tp_host::timed_span(tp_handle_t h) {
     return h->in_region && h->ring_used < (int)h->ring.size() ? h->ring[(size_t)h->ring_used] : h->kernel_span;
 }
 
-// the end of what timed_span(h) brackets; a ring slot is used up
-int timed_done(tp_handle_t h, Span& span) {
+int tp_host::timed_done(tp_handle_t h, Span& span) {
     HIP_TRY(h, span.end(h->stream));
     if (&span != &h->kernel_span) ++h->ring_used;
     return TP_OK;
 }
 
-int launch(tp_batch_t b, const tp_kargs_t& a, int64_t count, bool timed) {
+int tp_host::launch(tp_batch_t b, const tp_kargs_t& a, int64_t count, bool timed) {
     tp_handle_t h = b->h;
     if (count <= 0) return TP_OK;
     if (count > 0x7fffffffLL) return fail(h, TP_ERR_INVALID, "too many windows in one launch");
@@ -249,6 +248,28 @@ int launch(tp_batch_t b, const tp_kargs_t& a, int64_t count, bool timed) {
     h->last_launch = tp_launch_info_t{(int)(count < b->tiled_capacity ? count : b->tiled_capacity), 256, 36864, ws[0].NS * 4};
     return span ? timed_done(h, *span) : TP_OK;
 }
+
+// Before and after the launches of a tp_batch_run or a sweep.
+int tp_host::begin_launches(tp_batch_t b) {
+    tp_handle_t h = b->h;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (b->upload_pending) {          // tp_batch_upload_async: the kernel stream waits for the copy stream's event
+        HIP_TRY(h, hipStreamWaitEvent(h->stream, b->upload_done, 0));
+        b->upload_pending = false;
+    }
+    return TP_OK;
+}
+
+int tp_host::end_launches(tp_batch_t b) {
+    tp_handle_t h = b->h;
+    // the end of the launches, recorded EVERY time: a later tp_batch_upload_async of this batch - also the first one,
+    // after synchronous uploads - makes the copy stream wait for it before it overwrites what the launches read
+    HIP_TRY(h, b->ran.create(hipEventDisableTiming));
+    HIP_TRY(h, hipEventRecord(b->ran, h->stream));
+    return flush_gather(h);      // with the next kernel queued, put the requested gather of the previous run on its stream
+}
+
+namespace {
 
 // device_calls = false, or a runtime that answers "deinitialised": only the host structures go.  That is decided
 // here, once; the members' destructors obey it (t_device_calls).
@@ -631,26 +652,6 @@ int tp_batch_download_posterior(tp_batch_t b, double* M) {
     return download(h, {{M, b->post.p, sizeof(double) * (size_t)b->post_count * (size_t)b->p.k * (size_t)b->p.k}});
 }
 
-// Before and after the launches of a tp_batch_run or a tp_batch_solve_sweep.
-static int begin_launches(tp_batch_t b) {
-    tp_handle_t h = b->h;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (b->upload_pending) {          // tp_batch_upload_async: the kernel stream waits for the copy stream's event
-        HIP_TRY(h, hipStreamWaitEvent(h->stream, b->upload_done, 0));
-        b->upload_pending = false;
-    }
-    return TP_OK;
-}
-
-static int end_launches(tp_batch_t b) {
-    tp_handle_t h = b->h;
-    // the end of the launches, recorded EVERY time: a later tp_batch_upload_async of this batch - also the first one,
-    // after synchronous uploads - makes the copy stream wait for it before it overwrites what the launches read
-    HIP_TRY(h, b->ran.create(hipEventDisableTiming));
-    HIP_TRY(h, hipEventRecord(b->ran, h->stream));
-    return flush_gather(h);      // with the next kernel queued, put the requested gather of the previous run on its stream
-}
-
 int tp_batch_run(tp_batch_t b) {
     if (!b) return TP_ERR_INVALID;
     tp_handle_t h = b->h;
@@ -672,584 +673,6 @@ int tp_batch_run(tp_batch_t b) {
     tp_kargs_t a = make_kargs(b);
     rc = launch(b, a, b->W, true);
     return rc != TP_OK ? rc : end_launches(b);
-}
-
-// Solve sweep.  Windows go through in sub-ranges of `chunk` windows: the batch's own run kernel stores the matrices of a
-// sub-range (the keep_posterior store) and, once, every window's default right-hand side (the keep_rhs store) into the
-// sweep's workspace, then posterior_sweep_kernel solves the sub-range's (window, shift) pairs.  Default chunk: as many
-// windows as TP_SWEEP_WORKSPACE_BYTES of matrices hold (256 MiB, the size of the Infinity Cache: the solve kernel reads
-// what the Gram pass has just written), never more than 2^30 (window, shift) pairs per launch.
-#define TP_SWEEP_WORKSPACE_BYTES (256ull << 20)
-// What the two solve sweeps share - tp_batch_solve_sweep (`tiled` = false, k <= tp_sweep_max_assets()) and
-// tp_batch_solve_sweep_tiled (above it): the argument checks, the drain of the handle's stream, the windows per sub-range, the
-// sweep's buffers and the copies of the caller's arrays.  *chunk_out = 0: W = 0, nothing to launch (sw_S / sw_R are set).
-static int solve_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_shift, const double* shift, int32_t n_rhs,
-                               const double* rhs, int32_t default_rhs, int* S_out, int* R_out, int64_t* chunk_out) {
-    tp_handle_t h = b->h;
-    const int k = b->p.k;
-    const int64_t W = b->W;
-    *chunk_out = 0;
-    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
-    if (n_shift < 0) return fail(h, TP_ERR_INVALID, "%s: n_shift=%d < 0", name, n_shift);
-    if (n_rhs < 0) return fail(h, TP_ERR_INVALID, "%s: n_rhs=%d < 0", name, n_rhs);
-    if (shift && b->p.strategy != TP_STRATEGY_JEFFREYS)
-        return fail(h, TP_ERR_INVALID, "%s: a shift applies to the Jeffreys strategy only", name);
-    if (shift && n_shift < 1) return fail(h, TP_ERR_INVALID, "%s: shift given with n_shift=0", name);
-    if (!shift && n_shift > 1) return fail(h, TP_ERR_INVALID, "%s: n_shift=%d without shift", name, n_shift);
-    const int S = n_shift > 1 ? n_shift : 1;
-    const long long R = (default_rhs ? 1 : 0) + (long long)n_rhs;
-    if (R < 1 || R > TP_SWEEP_MAX_RHS)
-        return fail(h, TP_ERR_INVALID, "%s: %lld right-hand sides per window outside [1, %d]", name, R, TP_SWEEP_MAX_RHS);
-    if (n_rhs > 0 && !rhs) return fail(h, TP_ERR_INVALID, "%s: n_rhs=%d without rhs", name, n_rhs);
-    if (shift)
-        for (int64_t i = 0; i < 2 * W * S; ++i)
-            if (!(shift[i] >= 0.0) || !std::isfinite(shift[i]))
-                return fail(h, TP_ERR_INVALID, "%s: shift[%lld] must be finite and >= 0", name, (long long)i);
-    if (!tiled && k > tp_sweep_max_assets())
-        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d exceeds the sweep kernel's largest universe %d", name, k, tp_sweep_max_assets());
-    if (tiled && k <= tp_sweep_max_assets())
-        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d is served by tp_batch_solve_sweep (k <= %d)", name, k, tp_sweep_max_assets());
-    if (tiled && k + R > tp_max_assets() + 1)
-        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d with %lld right-hand sides exceeds the arena side %d", name, k, R, tp_max_assets() + 1);
-    int rc = begin_launches(b);
-    if (rc != TP_OK) return rc;
-    // Unlike tp_batch_run the call drains the handle's stream here (documented in the header): an earlier sweep may still
-    // read the buffers about to be reallocated or refilled, and the kernel span may still be waiting to be read
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    rc = harvest_kernel_time(h);
-    if (rc != TP_OK) return rc;
-    b->sw_S = 0; b->sw_R = 0;
-    *S_out = S; *R_out = (int)R;
-    if (W == 0) { b->sw_S = S; b->sw_R = (int)R; return TP_OK; }
-    // windows per sub-range
-    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
-    int64_t chunk = h->sweep_chunk_windows > 0 ? h->sweep_chunk_windows : (int64_t)(TP_SWEEP_WORKSPACE_BYTES / mat_bytes);
-    if (tiled && chunk > (int64_t)(TP_SWEEP_WORKSPACE_BYTES / mat_bytes)) chunk = (int64_t)(TP_SWEEP_WORKSPACE_BYTES / mat_bytes);
-    if (chunk > (1ll << 30) / S) chunk = (1ll << 30) / S;
-    if (chunk < 1) chunk = 1;
-    if (chunk > W) chunk = W;
-    const std::string what = std::string(name) + ": ";
-    rc = ensure(h, b->sw_post, mat_bytes * (size_t)chunk, (what + "kept matrices of one sub-range").c_str());
-    if (!tiled) {                                      // outputs of the run kernel that serves as the Gram pass
-        if (rc == TP_OK) rc = ensure(h, b->sw_weights, sizeof(double) * (size_t)W * k, (what + "weights of the Gram pass").c_str());
-        if (rc == TP_OK) rc = ensure(h, b->sw_status, sizeof(int32_t) * (size_t)W, (what + "statuses of the Gram pass").c_str());
-        if (rc == TP_OK) rc = ensure(h, b->sw_aux, sizeof(double) * (size_t)W * TP_AUX_STRIDE, (what + "aux of the Gram pass").c_str());
-    }
-    if (rc == TP_OK) rc = ensure(h, b->sw_rhs0, sizeof(double) * (size_t)W * k, (what + "default right-hand sides").c_str());
-    if (rc == TP_OK) rc = ensure(h, b->sw_x, sizeof(double) * (size_t)W * S * (size_t)R * k, (what + "solutions").c_str());
-    if (rc == TP_OK) rc = ensure(h, b->sw_xstatus, sizeof(int32_t) * (size_t)W * S, (what + "solution statuses").c_str());
-    if (rc == TP_OK && shift) rc = ensure(h, b->sw_shift, sizeof(double) * 2 * (size_t)W * S, (what + "shifts").c_str());
-    if (rc == TP_OK && n_rhs > 0) rc = ensure(h, b->sw_rhs, sizeof(double) * (size_t)W * n_rhs * k, (what + "right-hand sides").c_str());
-    if (rc != TP_OK) return rc;
-    // the caller's arrays: copied here, no host pointer is kept
-    if (shift) HIP_TRY(h, hipMemcpyAsync(b->sw_shift.p, shift, sizeof(double) * 2 * (size_t)W * S, hipMemcpyHostToDevice, h->stream));
-    if (n_rhs > 0) HIP_TRY(h, hipMemcpyAsync(b->sw_rhs.p, rhs, sizeof(double) * (size_t)W * n_rhs * k, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
-    *chunk_out = chunk;
-    return TP_OK;
-}
-
-// the Gram pass of a solve sweep: the batch as a plain run would see it - no custom right-hand side, no shift - writing into
-// the sweep's buffers, and without the shared block sums (whether those are used depends on W: M_w must not)
-static tp_kargs_t solve_sweep_gram_kargs(tp_batch_t b) {
-    tp_kargs_t a = make_kargs(b);
-    a.rhs = nullptr;
-    a.shift = nullptr;
-    a.prefix = nullptr; a.winsum = nullptr; a.prefix_nblk = 0;
-    for (int i = 0; i < 4; ++i) a.winsum_L[i] = 0;
-    a.weights = (double*)b->sw_weights.p;
-    a.status = (int*)b->sw_status.p;
-    a.aux = (double*)b->sw_aux.p;
-    a.out_rhs = (double*)b->sw_rhs0.p;
-    a.out_post = (double*)b->sw_post.p;
-    a.stamps = nullptr;
-    return a;
-}
-
-int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift, int32_t n_rhs, const double* rhs,
-                         int32_t default_rhs) {
-    if (!b) return TP_ERR_INVALID;
-    tp_handle_t h = b->h;
-    const int k = b->p.k;
-    const int64_t W = b->W;
-    int S = 0, R = 0;
-    int64_t chunk = 0;
-    int rc = solve_sweep_prepare(b, "tp_batch_solve_sweep", false, n_shift, shift, n_rhs, rhs, default_rhs, &S, &R, &chunk);
-    if (rc != TP_OK || chunk == 0) return rc;
-    tp_kargs_t a = solve_sweep_gram_kargs(b);
-    tp_sweep_kargs_t sa;
-    memset(&sa, 0, sizeof sa);
-    sa.post = (const double*)b->sw_post.p;
-    sa.default_rhs = default_rhs ? (const double*)b->sw_rhs0.p : nullptr;
-    sa.rhs = n_rhs > 0 ? (const double*)b->sw_rhs.p : nullptr;
-    sa.shift = shift ? (const double*)b->sw_shift.p : nullptr;
-    sa.x = (double*)b->sw_x.p;
-    sa.status = (int*)b->sw_xstatus.p;
-    sa.k = k; sa.S = S; sa.R = R; sa.n_rhs = n_rhs;
-    sa.gamma = b->p.gamma;
-    const tp_launch_info_t keep_launch = h->last_launch;      // tp_last_launch describes tp_batch_run launches
-    // one span around all launches: a sweep is one step of tp_region_steps, kernel_ms = Gram passes + solves
-    Span& span = timed_span(h);
-    HIP_TRY(h, span.begin(h->stream));
-    for (int64_t w0 = 0; w0 < W; w0 += chunk) {
-        const int64_t n = W - w0 < chunk ? W - w0 : chunk;
-        a.w_first = w0; a.w_count = n;
-        a.post_w0 = w0; a.post_count = n;
-        rc = launch(b, a, n, false);
-        if (rc != TP_OK) { h->last_launch = keep_launch; return rc; }
-        sa.w_first = w0; sa.w_count = n;
-        const hipError_t e = tp_sweep_launch(sa, h->stream);
-        if (e != hipSuccess) { h->last_launch = keep_launch; return fail(h, TP_ERR_HIP, "sweep kernel launch failed: %s", hipGetErrorString(e)); }
-    }
-    h->last_launch = keep_launch;
-    rc = timed_done(h, span);
-    if (rc != TP_OK) return rc;
-    b->sw_S = S; b->sw_R = R;
-    return end_launches(b);                            // (the sweep reads the batch's inputs and writes none of its results)
-}
-
-// The sweep's own tiled workspace (arena, inverse diagonal blocks, flags) at the sweep's geometry, KP from k + R: as many
-// (window, shift) entries as the large-k arena budget allows (tiled_arena_entries, the rule ensure_tiled_ws sizes by; what this
-// workspace already holds counts as free), at most `entries`.  The batch's run workspace is left as it is.
-static int ensure_sweep_tiled_ws(tp_batch_t b, int R, int64_t entries, tp_tiled_ws_t* ws, int64_t* cap_out) {
-    tp_handle_t h = b->h;
-    int KP, NS, NSB;
-    tp_solve_sweep_tiled_geometry(b->p.k, R, &KP, &NS, &NSB);
-    const size_t per_entry = sizeof(double) * ((size_t)KP * KP + (size_t)NSB * 64 * 64) + sizeof(int);
-    int64_t G = tiled_arena_entries(h, per_entry, 1, b->swt_arena.bytes + b->swt_rinv.bytes + b->swt_flags.bytes);
-    if (G > entries) G = entries;
-    int rc = ensure(h, b->swt_arena, sizeof(double) * (size_t)G * KP * KP, "tp_batch_solve_sweep_tiled: arena");
-    if (rc == TP_OK) rc = ensure(h, b->swt_rinv, sizeof(double) * (size_t)G * NSB * 64 * 64, "tp_batch_solve_sweep_tiled: inverse diagonal blocks");
-    if (rc == TP_OK) rc = ensure(h, b->swt_flags, sizeof(int) * (size_t)G, "tp_batch_solve_sweep_tiled: flags");
-    if (rc != TP_OK) return rc;
-    memset(ws, 0, sizeof *ws);
-    ws->arena = (double*)b->swt_arena.p; ws->rinv = (double*)b->swt_rinv.p; ws->flags = (int*)b->swt_flags.p;
-    ws->KP = KP; ws->NS = NS; ws->NSB = NSB;
-    *cap_out = G;
-    return TP_OK;
-}
-
-// Solve sweep above tp_sweep_max_assets(), on the large-k tiled pipeline.  Per sub-range of windows (one k x k matrix per
-// window inside TP_SWEEP_WORKSPACE_BYTES, at least one window) the batch's own tiled Gram stage - its real strategy, no custom
-// right-hand side, no shift, no shared sums - leaves M_w in sw_post (the kept-matrix store) and the default right-hand side in
-// sw_rhs0 (the kept-right-hand-side store), in groups of as many windows as the batch's run workspace holds.  Then the
-// sub-range's (window, shift) pairs go through the SWEEP's workspace in groups of its capacity: posterior_solve_sweep_tiled.hip
-// fills them, the block steps of the tiled factorisation factorise them and forward-substitute the R columns, and the sweep's
-// own kernel back-substitutes.
-int tp_batch_solve_sweep_tiled(tp_batch_t b, int32_t n_shift, const double* shift, int32_t n_rhs, const double* rhs,
-                               int32_t default_rhs) {
-    if (!b) return TP_ERR_INVALID;
-    tp_handle_t h = b->h;
-    const int k = b->p.k;
-    const int64_t W = b->W;
-    int S = 0, R = 0;
-    int64_t chunk = 0;
-    int rc = solve_sweep_prepare(b, "tp_batch_solve_sweep_tiled", true, n_shift, shift, n_rhs, rhs, default_rhs, &S, &R, &chunk);
-    if (rc != TP_OK || chunk == 0) return rc;
-    // the batch's run workspace (lane 0) as a run would size it, for the Gram stage; the sweep's own for the entries
-    tp_tiled_ws_t wsl[TP_MAX_LANES];
-    int lanes = 1;
-    rc = ensure_tiled_ws(b, wsl, &lanes);
-    if (rc != TP_OK) return rc;
-    const int64_t gcap = b->tiled_capacity;
-    tp_tiled_ws_t ws;
-    int64_t cap = 0;
-    rc = ensure_sweep_tiled_ws(b, R, chunk * S, &ws, &cap);
-    if (rc != TP_OK) return rc;
-    tp_kargs_t a = solve_sweep_gram_kargs(b);
-    a.weights = nullptr; a.status = nullptr; a.aux = nullptr;          // (the Gram stage writes none of them)
-    a.hf_prefix = nullptr; a.hf_winsum = nullptr;                      // no shared intraday sums either
-    tp_solve_sweep_tiled_kargs_t sa;
-    memset(&sa, 0, sizeof sa);
-    sa.post = (const double*)b->sw_post.p;
-    sa.default_rhs = default_rhs ? (const double*)b->sw_rhs0.p : nullptr;
-    sa.rhs = n_rhs > 0 ? (const double*)b->sw_rhs.p : nullptr;
-    sa.shift = shift ? (const double*)b->sw_shift.p : nullptr;
-    sa.x = (double*)b->sw_x.p;
-    sa.status = (int*)b->sw_xstatus.p;
-    sa.k = k; sa.S = S; sa.R = R; sa.n_rhs = n_rhs;
-    sa.gamma = b->p.gamma;
-    // the block steps read k, w_count (set per group below) and the kernel choices; everything else stays zero
-    tp_kargs_t fa;
-    memset(&fa, 0, sizeof fa);
-    fa.k = k;
-    fa.opts = h->opts;
-    // one span around all launches: a sweep is one step of tp_region_steps, kernel_ms = Gram passes + fills + factorisations
-    // + solves (tp_last_launch keeps describing tp_batch_run launches: nothing here writes it)
-    Span& span = timed_span(h);
-    HIP_TRY(h, span.begin(h->stream));
-    for (int64_t w0 = 0; w0 < W; w0 += chunk) {
-        const int64_t n = W - w0 < chunk ? W - w0 : chunk;
-        for (int64_t g0 = 0; g0 < n; g0 += gcap) {
-            a.w_first = w0 + g0; a.w_count = n - g0 < gcap ? n - g0 : gcap;
-            a.post_w0 = w0; a.post_count = n;
-            const hipError_t e = tp_tiled_gram_launch(a, wsl[0], h->stream, false);
-            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled solve sweep Gram launch failed: %s", hipGetErrorString(e));
-        }
-        const int64_t E = n * S;
-        for (int64_t e0 = 0; e0 < E; e0 += cap) {
-            sa.wc_first = w0;
-            sa.e_first = w0 * S + e0; sa.e_count = E - e0 < cap ? E - e0 : cap;
-            hipError_t e = tp_solve_sweep_tiled_fill_launch(sa, ws, h->stream);
-            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled solve sweep fill launch failed: %s", hipGetErrorString(e));
-            fa.w_count = sa.e_count;
-            e = tp_tiled_block_steps_launch(fa, ws, h->stream);
-            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled solve sweep factor launch failed: %s", hipGetErrorString(e));
-            e = tp_solve_sweep_tiled_solve_launch(sa, ws, h->stream);
-            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled solve sweep solve launch failed: %s", hipGetErrorString(e));
-        }
-    }
-    rc = timed_done(h, span);
-    if (rc != TP_OK) return rc;
-    b->sw_S = S; b->sw_R = R;
-    return end_launches(b);                            // (the sweep reads the batch's inputs and writes none of its results)
-}
-
-int tp_batch_download_sweep(tp_batch_t b, double* x, int32_t* status) {
-    if (!b) return TP_ERR_INVALID;
-    tp_handle_t h = b->h;
-    if (b->sw_S < 1 || b->sw_R < 1)
-        return fail(h, TP_ERR_INVALID, "tp_batch_download_sweep: no tp_batch_solve_sweep before it");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)b->W * b->sw_S;           // (W = 0: nothing to copy)
-    return download(h, {{x, b->sw_x.p, sizeof(double) * n * b->sw_R * b->p.k}, {status, b->sw_xstatus.p, sizeof(int32_t) * n}});
-}
-
-int tp_batch_download_sweep_rhs(tp_batch_t b, double* rhs_out) {
-    if (!b) return TP_ERR_INVALID;
-    tp_handle_t h = b->h;
-    if (b->sw_S < 1 || b->sw_R < 1)
-        return fail(h, TP_ERR_INVALID, "tp_batch_download_sweep_rhs: no tp_batch_solve_sweep before it");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (b->W > 0 && !rhs_out) return fail(h, TP_ERR_INVALID, "tp_batch_download_sweep_rhs: rhs_out is NULL");
-    return download(h, {{rhs_out, b->sw_rhs0.p, sizeof(double) * (size_t)b->W * b->p.k}});
-}
-
-// What the prior sweeps and the size sweep share - tp_batch_prior_sweep (`tiled` = false, k <= tp_sweep_max_assets()),
-// tp_batch_prior_sweep_tiled (above it) and tp_batch_size_sweep (`sz` given: n_size universes per (window, prior), buffers of its
-// own, a Jeffreys batch allowed - without priors): the argument checks, the drain of the handle's stream, the windows per
-// sub-range (C and T: two k x k matrices per window inside TP_SWEEP_WORKSPACE_BYTES, never more than 2^30 (window, prior) pairs),
-// the sweep's buffers and the copies of the caller's arrays.  *chunk_out = 0: W = 0, nothing to launch (the sweep's shape is set).
-struct SizeAxis { int32_t n_size; const int32_t* sizes; };
-static int prior_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_prior, const double* n0, const double* w0,
-                               int64_t* chunk_out, const SizeAxis* sz = nullptr) {
-    tp_handle_t h = b->h;
-    const int k = b->p.k;
-    const int64_t W = b->W;
-    *chunk_out = 0;
-    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
-    if (!sz && !conj) return fail(h, TP_ERR_INVALID, "%s applies to the conjugate strategy only", name);
-    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
-    if (sz) {
-        if (sz->n_size < 1 || sz->n_size > TP_SWEEP_MAX_RHS)
-            return fail(h, TP_ERR_INVALID, "%s: n_size=%d outside [1, %d]", name, sz->n_size, TP_SWEEP_MAX_RHS);
-        if (!sz->sizes) return fail(h, TP_ERR_INVALID, "%s: sizes is NULL", name);
-        for (int s = 0; s < sz->n_size; ++s)
-            if (sz->sizes[s] < 1 || sz->sizes[s] > k || (s > 0 && sz->sizes[s] <= sz->sizes[s - 1]))
-                return fail(h, TP_ERR_INVALID, "%s: sizes[%d]=%d: strictly increasing sizes within [1, %d] expected", name, s, sz->sizes[s], k);
-    }
-    if (sz && !conj && (n_prior != 0 || n0 || w0))
-        return fail(h, TP_ERR_INVALID, "%s: a Jeffreys batch takes no priors (n_prior = 0, n0 = w0 = NULL)", name);
-    const int P = conj ? n_prior : 1;
-    const int S = sz ? sz->n_size : 1;
-    if (conj) {
-        if (n_prior < 1) return fail(h, TP_ERR_INVALID, "%s: n_prior=%d < 1", name, n_prior);
-        if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "%s: %s is NULL", name, !n0 ? "n0" : "w0");
-        for (int64_t i = 0; i < W * P; ++i)
-            if (!(n0[i] > 0.0) || !std::isfinite(n0[i]))
-                return fail(h, TP_ERR_INVALID, "%s: n0[%lld] must be finite and > 0", name, (long long)i);
-        for (int64_t e = 0; e < W * P * S; ++e) {          // (a size sweep reads the first sizes[s] entries of a vector only)
-            const int ke = sz ? sz->sizes[e % S] : k;
-            for (int i = 0; i < ke; ++i)
-                if (!std::isfinite(w0[e * k + i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)(e * k + i));
-        }
-    }
-    if (!tiled && k > tp_sweep_max_assets())
-        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d exceeds the sweep kernel's largest universe %d", name, k, tp_sweep_max_assets());
-    if (tiled && k <= tp_sweep_max_assets())
-        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d is served by tp_batch_prior_sweep (k <= %d)", name, k, tp_sweep_max_assets());
-    int rc = begin_launches(b);
-    if (rc != TP_OK) return rc;
-    // like tp_batch_solve_sweep the call drains the handle's stream here: an earlier launch may still use the buffers (and the
-    // tiled workspace) about to be reallocated or refilled, and the kernel span may still be waiting to be read
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    rc = harvest_kernel_time(h);
-    if (rc != TP_OK) return rc;
-    if (sz) { b->zs_P = 0; b->zs_S = 0; } else b->ps_P = 0;
-    if (W == 0) { if (sz) { b->zs_P = P; b->zs_S = S; } else b->ps_P = P; return TP_OK; }
-    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
-    int64_t chunk = h->sweep_chunk_windows > 0 ? h->sweep_chunk_windows : (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes));
-    if (chunk > (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes))) chunk = (int64_t)(TP_SWEEP_WORKSPACE_BYTES / (2 * mat_bytes));
-    if (chunk > (1ll << 30) / P) chunk = (1ll << 30) / P;
-    if (chunk < 1) chunk = 1;
-    if (chunk > W) chunk = W;
-    const size_t WP = (size_t)W * (size_t)P;
-    const size_t WPS = WP * (size_t)S;
-    const std::string what = std::string(name) + ": ";
-    DevBuf& dC = sz ? b->zs_C : b->ps_C;  DevBuf& dT = sz ? b->zs_T : b->ps_T;  DevBuf& dt = sz ? b->zs_t : b->ps_t;
-    DevBuf& dn0 = sz ? b->zs_n0 : b->ps_n0;  DevBuf& dw0 = sz ? b->zs_w0 : b->ps_w0;
-    DevBuf& dwts = sz ? b->zs_weights : b->ps_weights;  DevBuf& dst = sz ? b->zs_status : b->ps_status;  DevBuf& daux = sz ? b->zs_aux : b->ps_aux;
-    rc = TP_OK;
-    if (conj) rc = ensure(h, dC, mat_bytes * (size_t)chunk, (what + "intraday scatters of one sub-range").c_str());
-    if (rc == TP_OK) rc = ensure(h, dT, mat_bytes * (size_t)chunk, (what + (conj ? "daily Grams of one sub-range" : "matrices of one sub-range")).c_str());
-    if (rc == TP_OK) rc = ensure(h, dt, sizeof(double) * (size_t)W * k, (what + "daily column sums").c_str());
-    if (rc == TP_OK && conj) rc = ensure(h, dn0, sizeof(double) * WP, (what + "prior strengths").c_str());
-    if (rc == TP_OK && conj) rc = ensure(h, dw0, sizeof(double) * WPS * k, (what + "prior weights").c_str());
-    if (rc == TP_OK) rc = ensure(h, dwts, sizeof(double) * WPS * k, (what + "weights").c_str());
-    if (rc == TP_OK) rc = ensure(h, dst, sizeof(int32_t) * WPS, (what + "statuses").c_str());
-    if (rc == TP_OK) rc = ensure(h, daux, sizeof(double) * WPS * TP_AUX_STRIDE, (what + "aux").c_str());
-    if (rc == TP_OK && sz) rc = ensure(h, b->zs_sizes, sizeof(int32_t) * (size_t)S, (what + "sizes").c_str());
-    if (rc == TP_OK && sz && !conj) {                      // outputs of the run kernel that serves as the Gram pass
-        rc = ensure(h, b->zs_gw, sizeof(double) * (size_t)W * k, (what + "weights of the Gram pass").c_str());
-        if (rc == TP_OK) rc = ensure(h, b->zs_gs, sizeof(int32_t) * (size_t)W, (what + "statuses of the Gram pass").c_str());
-        if (rc == TP_OK) rc = ensure(h, b->zs_ga, sizeof(double) * (size_t)W * TP_AUX_STRIDE, (what + "aux of the Gram pass").c_str());
-    }
-    if (rc != TP_OK) return rc;
-    // the caller's arrays: copied here, no host pointer is kept
-    if (conj) {
-        HIP_TRY(h, hipMemcpyAsync(dn0.p, n0, sizeof(double) * WP, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(dw0.p, w0, sizeof(double) * WPS * k, hipMemcpyHostToDevice, h->stream));
-    }
-    if (sz) HIP_TRY(h, hipMemcpyAsync(b->zs_sizes.p, sz->sizes, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
-    *chunk_out = chunk;
-    return TP_OK;
-}
-
-// Gram pass of a prior sweep or a conjugate size sweep: the windows' rows as a plain run reads them; no prior, no shared block
-// sums, none of the run's outputs
-static tp_gram_kargs_t prior_sweep_gram_kargs(tp_batch_t b, const DevBuf& C, const DevBuf& T, const DevBuf& t) {
-    tp_gram_kargs_t ga;
-    memset(&ga, 0, sizeof ga);
-    ga.in = make_kargs(b);
-    ga.in.w0 = nullptr; ga.in.n0 = nullptr;
-    ga.in.rhs = nullptr; ga.in.shift = nullptr;
-    ga.in.prefix = nullptr; ga.in.winsum = nullptr; ga.in.prefix_nblk = 0;
-    for (int i = 0; i < 4; ++i) ga.in.winsum_L[i] = 0;
-    ga.in.weights = nullptr; ga.in.status = nullptr; ga.in.aux = nullptr;
-    ga.in.out_rhs = nullptr; ga.in.out_post = nullptr; ga.in.post_count = 0; ga.in.stamps = nullptr;
-    ga.C = (double*)C.p; ga.T = (double*)T.p; ga.t = (double*)t.p;
-    return ga;
-}
-
-// Prior sweep.  Windows go through in sub-ranges of `chunk` windows: the Gram pass (posterior_gram_nt.hip) stores C and T of
-// a sub-range - two k x k matrices per window inside TP_SWEEP_WORKSPACE_BYTES - and t, then posterior_prior_sweep_kernel
-// solves the sub-range's (window, prior) pairs; never more than 2^30 pairs per launch.
-int tp_batch_prior_sweep(tp_batch_t b, int32_t n_prior, const double* n0, const double* w0) {
-    if (!b) return TP_ERR_INVALID;
-    tp_handle_t h = b->h;
-    const int k = b->p.k;
-    const int64_t W = b->W;
-    const int P = n_prior;
-    int64_t chunk = 0;
-    int rc = prior_sweep_prepare(b, "tp_batch_prior_sweep", false, n_prior, n0, w0, &chunk);
-    if (rc != TP_OK || chunk == 0) return rc;
-
-    tp_gram_kargs_t ga = prior_sweep_gram_kargs(b, b->ps_C, b->ps_T, b->ps_t);
-    tp_prior_sweep_kargs_t sa;
-    memset(&sa, 0, sizeof sa);
-    sa.C = (const double*)b->ps_C.p; sa.T = (const double*)b->ps_T.p; sa.t = (const double*)b->ps_t.p;
-    sa.n0 = (const double*)b->ps_n0.p; sa.w0 = (const double*)b->ps_w0.p;
-    sa.hf_count = (const int*)b->hf_count.p;
-    sa.weights = (double*)b->ps_weights.p; sa.status = (int*)b->ps_status.p; sa.aux = (double*)b->ps_aux.p;
-    sa.k = k; sa.P = P; sa.N = b->p.N; sa.m = b->p.m;
-    sa.gamma = b->p.gamma;
-    // one span around all launches: a sweep is one step of tp_region_steps, kernel_ms = Gram passes + solves
-    // (tp_last_launch keeps describing tp_batch_run launches: nothing here writes it)
-    Span& span = timed_span(h);
-    HIP_TRY(h, span.begin(h->stream));
-    for (int64_t w0i = 0; w0i < W; w0i += chunk) {
-        const int64_t n = W - w0i < chunk ? W - w0i : chunk;
-        ga.in.w_first = w0i; ga.in.w_count = n;
-        hipError_t e = tp_gram_launch(ga, h->stream);
-        if (e == hipErrorNotSupported)
-            return fail(h, TP_ERR_UNSUPPORTED, "tp_batch_prior_sweep: windows of %d daily / %d intraday rows in the index layout are "
-                                               "too long for the Gram pass", b->p.n_r, b->p.m);
-        if (e != hipSuccess) return fail(h, TP_ERR_HIP, "prior sweep Gram launch failed: %s", hipGetErrorString(e));
-        sa.w_first = w0i; sa.w_count = n;
-        e = tp_prior_sweep_launch(sa, h->stream);
-        if (e != hipSuccess) return fail(h, TP_ERR_HIP, "prior sweep kernel launch failed: %s", hipGetErrorString(e));
-    }
-    rc = timed_done(h, span);
-    if (rc != TP_OK) return rc;
-    b->ps_P = P;
-    return end_launches(b);                            // (the sweep reads the batch's inputs and writes none of its results)
-}
-
-// Prior sweep above tp_sweep_max_assets(), on the large-k tiled pipeline.  Per sub-range of windows (two k x k matrices per
-// window inside TP_SWEEP_WORKSPACE_BYTES, at least one window) the batch's own tiled Gram stage runs twice, steered by its
-// arguments - as a Jeffreys batch without centring over the daily rows (T into ps_T through the kept-matrix store, t into ps_t
-// through the kept-right-hand-side store) and as a Jeffreys batch centred by the window's row count over the INTRADAY rows,
-// the daily-panel fields pointed at the intraday panel (C = Y'Y - (Y'1)(Y'1)'/m into ps_C).  Then the sub-range's (window,
-// prior) pairs go through the arena in groups of at most tiled_capacity entries: posterior_prior_sweep_tiled.hip fills them,
-// tp_tiled_factor_launch factorises and solves them into the sweep's buffers.
-int tp_batch_prior_sweep_tiled(tp_batch_t b, int32_t n_prior, const double* n0, const double* w0) {
-    if (!b) return TP_ERR_INVALID;
-    tp_handle_t h = b->h;
-    const int k = b->p.k;
-    const int64_t W = b->W;
-    const int P = n_prior;
-    int64_t chunk = 0;
-    int rc = prior_sweep_prepare(b, "tp_batch_prior_sweep_tiled", true, n_prior, n0, w0, &chunk);
-    if (rc != TP_OK || chunk == 0) return rc;
-    // the batch's own tiled workspace (lane 0) and the pieces of a C w0 per arena entry
-    tp_tiled_ws_t wsl[TP_MAX_LANES];
-    int lanes = 1;
-    rc = ensure_tiled_ws(b, wsl, &lanes, chunk * P);
-    if (rc != TP_OK) return rc;
-    const int64_t cap = b->tiled_capacity;
-    rc = ensure(h, b->t_part[0], sizeof(double) * (size_t)cap * wsl[0].NS * wsl[0].NS * 64, "tp_batch_prior_sweep_tiled: prior products");
-    if (rc != TP_OK) return rc;
-    tp_tiled_ws_t ws = wsl[0];
-    ws.part = (double*)b->t_part[0].p;
-
-    // T and t: the daily rows as a plain run reads them, uncentred; no prior, no shared block sums, no custom right-hand side
-    tp_kargs_t ta = make_kargs(b);
-    ta.strategy = TP_STRATEGY_JEFFREYS;
-    ta.center_rows = 2;
-    ta.w0 = nullptr; ta.n0 = nullptr;
-    ta.rhs = nullptr; ta.shift = nullptr;
-    ta.prefix = nullptr; ta.winsum = nullptr; ta.prefix_nblk = 0; ta.prefix_blk0 = 0;
-    for (int i = 0; i < 4; ++i) ta.winsum_L[i] = 0;
-    ta.weights = nullptr; ta.status = nullptr; ta.aux = nullptr; ta.stamps = nullptr;
-    ta.out_rhs = (double*)b->ps_t.p;
-    ta.out_post = (double*)b->ps_T.p;
-    // C: the same stage over the intraday rows - the daily-panel fields name the intraday panel (its own 32-bit offset flags:
-    // make_kargs formed hf_off32 from that panel's bytes, leading dimension and m), centred by the window's row count
-    tp_kargs_t ca = ta;
-    ca.panel = ta.hf_panel; ca.start = ta.hf_start; ca.row_idx = ta.hf_row_idx; ca.n_rows = ta.hf_count;
-    ca.n_r = b->p.m; ca.rf_adj = nullptr;
-    ca.panel_ld = ta.hf_ld; ca.panel_off32 = ta.hf_off32;
-    ca.center_rows = 1;
-    ca.out_rhs = nullptr;
-    ca.out_post = (double*)b->ps_C.p;
-    for (tp_kargs_t* g : {&ta, &ca}) { g->hf_panel = nullptr; g->hf_start = nullptr; g->hf_row_idx = nullptr; g->hf_count = nullptr; g->hf_off32 = 0; }
-    tp_prior_sweep_tiled_kargs_t sa;
-    memset(&sa, 0, sizeof sa);
-    sa.C = (const double*)b->ps_C.p; sa.T = (const double*)b->ps_T.p; sa.t = (const double*)b->ps_t.p;
-    sa.n0 = (const double*)b->ps_n0.p; sa.w0 = (const double*)b->ps_w0.p;
-    sa.hf_count = (const int*)b->hf_count.p;
-    sa.k = k; sa.P = P; sa.m = b->p.m;
-    // factorisation and solve of the arena entries: a conjugate "batch" of (window, prior) pairs writing the sweep's buffers
-    tp_kargs_t fa;
-    memset(&fa, 0, sizeof fa);
-    fa.strategy = TP_STRATEGY_CONJUGATE;
-    fa.k = k; fa.N = b->p.N; fa.n_r = b->p.n_r; fa.m = b->p.m; fa.gamma = b->p.gamma;
-    fa.opts = h->opts;
-    fa.weights = (double*)b->ps_weights.p; fa.status = (int*)b->ps_status.p; fa.aux = (double*)b->ps_aux.p;
-    fa.dbg_w = -1;
-    // one span around all launches: a sweep is one step of tp_region_steps, kernel_ms = Gram passes + fills + solves
-    // (tp_last_launch keeps describing tp_batch_run launches: nothing here writes it)
-    Span& span = timed_span(h);
-    HIP_TRY(h, span.begin(h->stream));
-    for (int64_t w0i = 0; w0i < W; w0i += chunk) {
-        const int64_t n = W - w0i < chunk ? W - w0i : chunk;
-        for (int64_t g0 = 0; g0 < n; g0 += cap) {
-            for (tp_kargs_t* g : {&ta, &ca}) {
-                g->w_first = w0i + g0; g->w_count = n - g0 < cap ? n - g0 : cap;
-                g->post_w0 = w0i; g->post_count = n;
-                const hipError_t e = tp_tiled_gram_launch(*g, ws, h->stream, false);
-                if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled prior sweep Gram launch failed: %s", hipGetErrorString(e));
-            }
-        }
-        const int64_t E = n * P;
-        for (int64_t e0 = 0; e0 < E; e0 += cap) {
-            sa.wc_first = w0i;
-            sa.e_first = w0i * P + e0; sa.e_count = E - e0 < cap ? E - e0 : cap;
-            hipError_t e = tp_prior_sweep_tiled_launch(sa, ws, h->stream);
-            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled prior sweep fill launch failed: %s", hipGetErrorString(e));
-            fa.w_first = sa.e_first; fa.w_count = sa.e_count;
-            e = tp_tiled_factor_launch(fa, ws, h->stream);
-            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled prior sweep factor launch failed: %s", hipGetErrorString(e));
-        }
-    }
-    rc = timed_done(h, span);
-    if (rc != TP_OK) return rc;
-    b->ps_P = P;
-    return end_launches(b);                            // (the sweep reads the batch's inputs and writes none of its results)
-}
-
-int tp_batch_download_prior_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux) {
-    if (!b) return TP_ERR_INVALID;
-    tp_handle_t h = b->h;
-    if (b->ps_P < 1) return fail(h, TP_ERR_INVALID, "tp_batch_download_prior_sweep: no tp_batch_prior_sweep before it");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)b->W * b->ps_P;           // (W = 0: nothing to copy)
-    return download(h, {{weights, b->ps_weights.p, sizeof(double) * n * b->p.k}, {status, b->ps_status.p, sizeof(int32_t) * n},
-                        {aux, b->ps_aux.p, sizeof(double) * n * TP_AUX_STRIDE}});
-}
-
-// Size sweep.  Sub-ranges as in tp_batch_prior_sweep.  Conjugate: the same Gram pass stores C, T and t.  Jeffreys: the batch's
-// own run kernel - as the solve sweep steers it: no custom right-hand side, no shift, no shared block sums, outputs into the
-// sweep's buffers - keeps M (its centring flag applied) and t; it reads the daily inputs only.  Then posterior_size_sweep_kernel
-// factorises every (window, prior) once at k and solves every size over its prefix.
-int tp_batch_size_sweep(tp_batch_t b, int32_t n_size, const int32_t* sizes, int32_t n_prior, const double* n0, const double* w0) {
-    if (!b) return TP_ERR_INVALID;
-    tp_handle_t h = b->h;
-    const int k = b->p.k;
-    const int64_t W = b->W;
-    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
-    const int P = conj ? n_prior : 1;
-    const SizeAxis sz{n_size, sizes};
-    int64_t chunk = 0;
-    int rc = prior_sweep_prepare(b, "tp_batch_size_sweep", false, n_prior, n0, w0, &chunk, &sz);
-    if (rc != TP_OK || chunk == 0) return rc;
-    tp_gram_kargs_t ga = prior_sweep_gram_kargs(b, b->zs_C, b->zs_T, b->zs_t);
-    tp_kargs_t ja;
-    memset(&ja, 0, sizeof ja);
-    if (!conj) {
-        ja = solve_sweep_gram_kargs(b);
-        ja.weights = (double*)b->zs_gw.p; ja.status = (int*)b->zs_gs.p; ja.aux = (double*)b->zs_ga.p;
-        ja.out_rhs = (double*)b->zs_t.p; ja.out_post = (double*)b->zs_T.p;
-    }
-    tp_size_sweep_kargs_t sa;
-    memset(&sa, 0, sizeof sa);
-    sa.C = conj ? (const double*)b->zs_C.p : nullptr;
-    sa.T = (const double*)b->zs_T.p; sa.t = (const double*)b->zs_t.p;
-    sa.n0 = conj ? (const double*)b->zs_n0.p : nullptr; sa.w0 = conj ? (const double*)b->zs_w0.p : nullptr;
-    sa.hf_count = (const int*)b->hf_count.p;
-    sa.sizes = (const int*)b->zs_sizes.p;
-    sa.weights = (double*)b->zs_weights.p; sa.status = (int*)b->zs_status.p; sa.aux = (double*)b->zs_aux.p;
-    sa.k = k; sa.P = P; sa.S = n_size; sa.N = b->p.N; sa.m = b->p.m;
-    sa.gamma = b->p.gamma;
-    const tp_launch_info_t keep_launch = h->last_launch;      // tp_last_launch describes tp_batch_run launches
-    // one span around all launches: a sweep is one step of tp_region_steps, kernel_ms = Gram passes + solves
-    Span& span = timed_span(h);
-    HIP_TRY(h, span.begin(h->stream));
-    for (int64_t w0i = 0; w0i < W; w0i += chunk) {
-        const int64_t n = W - w0i < chunk ? W - w0i : chunk;
-        if (conj) {
-            ga.in.w_first = w0i; ga.in.w_count = n;
-            const hipError_t e = tp_gram_launch(ga, h->stream);
-            if (e == hipErrorNotSupported)
-                return fail(h, TP_ERR_UNSUPPORTED, "tp_batch_size_sweep: windows of %d daily / %d intraday rows in the index layout are "
-                                                   "too long for the Gram pass", b->p.n_r, b->p.m);
-            if (e != hipSuccess) return fail(h, TP_ERR_HIP, "size sweep Gram launch failed: %s", hipGetErrorString(e));
-        } else {
-            ja.w_first = w0i; ja.w_count = n;
-            ja.post_w0 = w0i; ja.post_count = n;
-            rc = launch(b, ja, n, false);
-            h->last_launch = keep_launch;
-            if (rc != TP_OK) return rc;
-        }
-        sa.w_first = w0i; sa.w_count = n;
-        const hipError_t e = tp_size_sweep_launch(sa, h->stream);
-        if (e != hipSuccess) return fail(h, TP_ERR_HIP, "size sweep kernel launch failed: %s", hipGetErrorString(e));
-    }
-    rc = timed_done(h, span);
-    if (rc != TP_OK) return rc;
-    b->zs_P = P; b->zs_S = n_size;
-    return end_launches(b);                            // (the sweep reads the batch's inputs and writes none of its results)
-}
-
-int tp_batch_download_size_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux) {
-    if (!b) return TP_ERR_INVALID;
-    tp_handle_t h = b->h;
-    if (b->zs_P < 1 || b->zs_S < 1) return fail(h, TP_ERR_INVALID, "tp_batch_download_size_sweep: no tp_batch_size_sweep before it");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)b->W * b->zs_P * b->zs_S;  // (W = 0: nothing to copy)
-    return download(h, {{weights, b->zs_weights.p, sizeof(double) * n * b->p.k}, {status, b->zs_status.p, sizeof(int32_t) * n},
-                        {aux, b->zs_aux.p, sizeof(double) * n * TP_AUX_STRIDE}});
 }
 
 int tp_synchronize(tp_handle_t h) {
@@ -1400,6 +823,5 @@ int tp_last_launch(tp_handle_t h, int* grid, int* block, int* lds_bytes, int* nt
     if (ntile) *ntile = h->last_launch.ntile;
     return TP_OK;
 }
-
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// tangency_host.h - internal to the host layer of libtangency.so (tangency_api.cpp, tangency_plan.cpp,
-// tangency_comm.cpp): the handle and batch structures and the helpers the three files share.
+// tangency_host.h - internal to the host layer of libtangency.so (tangency_api.cpp, tangency_sweep.cpp,
+// tangency_plan.cpp, tangency_comm.cpp): the handle and batch structures and the helpers the four files share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -65,6 +65,32 @@ struct tp_handle_s {
 
 struct PriceStaging { DevBuf prices, num, den; };   // price front-end: prices and the row pairs of the returns
 
+// Every sweep family has buffers of its own, so that a sweep leaves the batch's results, kept matrices and kept right-hand
+// sides alone - and the other families' results: each download returns what its own last sweep wrote.  Plain DevBufs, freed
+// with the batch (destroy_batch drains the streams first), declared - and so freed - in the order they always were.
+
+// Solve sweeps.  `post` holds the matrices of ONE sub-range of windows at a time.
+struct SolveSweepWs {
+    DevBuf weights, status, aux;    // outputs of the run kernel that serves as the Gram pass (tp_batch_solve_sweep)
+    DevBuf rhs0, post;              // every window's default right-hand side [W x k]; kept matrices [chunk x k x k]
+    DevBuf shift, rhs, x, xstatus;  // the caller's shifts and right-hand sides; solutions and their statuses
+    // tp_batch_solve_sweep_tiled: its own workspace of (window, shift) entries at the sweep's geometry (KP from k + R) - the
+    // batch's run workspace keeps the size and shape tp_batch_run gives it
+    DevBuf arena, rinv, flags;
+    int S = 0, R = 0;               // shape of the last sweep (0: none yet)
+};
+
+// Prior sweeps (`ps`) and the size sweep (`zs`): one type, two instances - a size sweep must not disturb what
+// tp_batch_download_prior_sweep returns, and the reverse.  C / T hold the matrices of ONE sub-range at a time: the intraday
+// scatters and daily Grams (a Jeffreys size sweep: M in T, no C).
+struct PriorSweepWs {
+    DevBuf C, T, t, n0, w0;
+    DevBuf sizes;                   // size sweep: the universes' sizes [S]
+    DevBuf weights, status, aux;
+    DevBuf gw, gs, ga;              // Jeffreys size sweep: outputs of the run kernel that serves as its Gram pass
+    int P = 0, S = 0;               // shape of the last sweep (0: none yet; a prior sweep has S = 1)
+};
+
 struct tp_batch_s {
     tp_handle_t h = nullptr;
     tp_params_t p{};
@@ -74,20 +100,8 @@ struct tp_batch_s {
     DevBuf weights, status, aux, dbg, gather_w, gather_s, weights2, status2, stamps, rhs, out_rhs, shift;
     DevBuf post;                                              // kept posterior matrices [post_count x k x k] (tp_batch_keep_posterior)
     int64_t post_w0 = 0, post_count = 0;
-    // solve sweep (tp_batch_solve_sweep): buffers of its own, so that a sweep leaves the batch's results, kept matrices and
-    // kept right-hand sides alone.  sw_post holds the matrices of ONE sub-range of windows at a time
-    DevBuf sw_weights, sw_status, sw_aux, sw_rhs0, sw_post, sw_shift, sw_rhs, sw_x, sw_xstatus;
-    int sw_S = 0, sw_R = 0;                                   // shape of the last sweep (0: none yet)
-    // tiled solve sweep (tp_batch_solve_sweep_tiled): its own workspace of (window, shift) entries at the sweep's geometry
-    // (KP from k + R) - the run workspace below keeps the size and shape tp_batch_run gives it
-    DevBuf swt_arena, swt_rinv, swt_flags;
-    // prior sweep (tp_batch_prior_sweep): buffers of its own as well.  ps_C / ps_T hold the two Grams of ONE sub-range at a time
-    DevBuf ps_C, ps_T, ps_t, ps_n0, ps_w0, ps_weights, ps_status, ps_aux;
-    int ps_P = 0;                                             // priors per window of the last prior sweep (0: none yet)
-    // size sweep (tp_batch_size_sweep): buffers of its own again.  zs_C / zs_T hold the matrices of ONE sub-range at a time (a
-    // Jeffreys batch: M in zs_T, no zs_C); zs_gw / zs_gs / zs_ga take the outputs of the run kernel that serves as its Gram pass
-    DevBuf zs_C, zs_T, zs_t, zs_n0, zs_w0, zs_sizes, zs_weights, zs_status, zs_aux, zs_gw, zs_gs, zs_ga;
-    int zs_P = 0, zs_S = 0;                                   // shape of the last size sweep (0: none yet)
+    SolveSweepWs sw;                                          // tp_batch_solve_sweep / _solve_sweep_tiled
+    PriorSweepWs ps, zs;                                      // tp_batch_prior_sweep / _prior_sweep_tiled; tp_batch_size_sweep
     PriceStaging fe, fe_hf;                                   // daily and intraday (freed after a synchronous upload)
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)
@@ -149,6 +163,16 @@ inline int harvest_kernel_time(tp_handle_t h) {
 // drain the kernel stream, read the kernel span, copy what has a destination, drain
 struct Copy { void* dst; const void* src; size_t bytes; };
 int download(tp_handle_t h, std::initializer_list<Copy> copies);
+
+// tangency_api.cpp: what the sweeps (tangency_sweep.cpp) launch and time with
+tp_kargs_t make_kargs(tp_batch_t b);                   // the batch as tp_batch_run launches it
+int launch(tp_batch_t b, const tp_kargs_t& a, int64_t count, bool timed);
+// The span a timed launch uses: inside a region the next slot of the ring (read by tp_region_end) while slots remain,
+// the handle's kernel span otherwise.
+Span& timed_span(tp_handle_t h);
+int timed_done(tp_handle_t h, Span& span);             // the end of what timed_span(h) brackets; a ring slot is used up
+int begin_launches(tp_batch_t b);                      // before and after the launches of a tp_batch_run or a sweep
+int end_launches(tp_batch_t b);
 
 // tangency_plan.cpp: input validation, upload planning, large-k launch planning
 int validate_pairs(tp_handle_t h, const char* what, const int32_t* num, const int32_t* den, int64_t n, int64_t price_rows);

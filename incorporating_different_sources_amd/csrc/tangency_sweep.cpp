@@ -1,0 +1,573 @@
+// tangency_sweep.cpp - the sweeps of the C-ABI of libtangency.so (include/tangency_posterior.h): many solves per window
+// from one Gram pass - tp_batch_solve_sweep, _prior_sweep, _size_sweep, the two tiled forms above tp_sweep_max_assets(), and
+// their downloads.  Every sweep is: checks, a drain of the handle's stream, its workspace (SolveSweepWs / PriorSweepWs,
+// tangency_host.h), then per sub-range of windows a Gram stage and a solve stage inside one timed span.
+#include <cmath>
+#include <cstring>
+#include <algorithm>
+#include <string>
+
+#include "tangency_host.h"
+
+using namespace tp_host;
+
+// Bound of the matrices one sub-range of windows keeps: 256 MiB, the size of the Infinity Cache (the solve kernel reads what
+// the Gram pass has just written).
+#define TP_SWEEP_WORKSPACE_BYTES (256ull << 20)
+
+namespace {
+
+// ---- what the five sweeps share ---------------------------------------------------------------------------------------
+
+// the sweep kernels serve k <= tp_sweep_max_assets(), the tiled forms (`partner`: the sweep below them) the universes above
+int check_sweep_k(tp_handle_t h, bool tiled, const char* name, const char* partner, int k) {
+    if (!tiled && k > tp_sweep_max_assets())
+        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d exceeds the sweep kernel's largest universe %d", name, k, tp_sweep_max_assets());
+    if (tiled && k <= tp_sweep_max_assets())
+        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d is served by %s (k <= %d)", name, k, partner, tp_sweep_max_assets());
+    return TP_OK;
+}
+
+// a[0 .. n) of the caller: every entry finite and >= 0 (`positive`: > 0)
+int check_finite_sign(tp_handle_t h, const char* name, const char* what, const double* a, int64_t n, bool positive) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(a[i]) || a[i] < 0.0 || (positive && a[i] == 0.0))
+            return fail(h, TP_ERR_INVALID, "%s: %s[%lld] must be finite and %s", name, what, (long long)i, positive ? "> 0" : ">= 0");
+    return TP_OK;
+}
+
+// Unlike tp_batch_run a sweep drains the handle's stream before it starts (documented in the header): an earlier launch may
+// still use the buffers (and the tiled workspace) about to be reallocated or refilled, and the kernel span may still be
+// waiting to be read
+int drain_for_sweep(tp_batch_t b) {
+    tp_handle_t h = b->h;
+    int rc = begin_launches(b);
+    if (rc != TP_OK) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return harvest_kernel_time(h);
+}
+
+// Windows per sub-range: the "sweep_chunk_windows" option, else as many as TP_SWEEP_WORKSPACE_BYTES hold at `bytes_per_window`
+// of kept matrices; never more than 2^30 (window, shift) or (window, prior) pairs per launch; within [1, W].
+// clamp_option_to_workspace = false, the plain solve sweep only: its option is documented as overriding the workspace bound
+// (tp_set_option in the header); the later sweeps honour it below the bound.
+int64_t sweep_chunk(tp_handle_t h, size_t bytes_per_window, int64_t pairs_per_window, int64_t W, bool clamp_option_to_workspace) {
+    const int64_t fit = (int64_t)(TP_SWEEP_WORKSPACE_BYTES / bytes_per_window);
+    int64_t chunk = h->sweep_chunk_windows > 0 ? h->sweep_chunk_windows : fit;
+    if (clamp_option_to_workspace) chunk = std::min(chunk, fit);
+    chunk = std::min(chunk, ((int64_t)1 << 30) / pairs_per_window);
+    return std::min(std::max<int64_t>(chunk, 1), W);
+}
+
+// The batch as a plain run would see it, with nothing attached: no custom right-hand side, no shift, no shared daily or
+// intraday block sums (whether those are used depends on W: a sweep's matrices must not), no stamps, no outputs.  A sweep's
+// Gram stage sets what it adds.
+tp_kargs_t neutral_kargs(tp_batch_t b) {
+    tp_kargs_t a = make_kargs(b);
+    a.rhs = nullptr; a.shift = nullptr;
+    a.prefix = nullptr; a.winsum = nullptr; a.prefix_nblk = 0; a.prefix_blk0 = 0;
+    for (int i = 0; i < 4; ++i) a.winsum_L[i] = 0;
+    a.hf_prefix = nullptr; a.hf_winsum = nullptr;
+    a.weights = nullptr; a.status = nullptr; a.aux = nullptr;
+    a.out_rhs = nullptr; a.out_post = nullptr; a.post_count = 0;
+    a.stamps = nullptr;
+    return a;
+}
+
+int launched(tp_handle_t h, hipError_t e, const char* what) {
+    return e == hipSuccess ? TP_OK : fail(h, TP_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+}
+
+// f(first, count) over [0, total) in groups of at most `step`; stops at the first error
+template <class F>
+int in_groups(int64_t total, int64_t step, F f) {
+    for (int64_t i0 = 0; i0 < total; i0 += step) {
+        const int rc = f(i0, std::min(step, total - i0));
+        if (rc != TP_OK) return rc;
+    }
+    return TP_OK;
+}
+
+// The launches of a sweep, body(w0, n) per sub-range of `chunk` windows, inside ONE span: a sweep is one step of
+// tp_region_steps, kernel_ms = all its launches.  tp_last_launch keeps describing tp_batch_run launches, whatever the body
+// launched and however it ended.  set_shape() records the sweep's shape for its download - after success only.
+template <class Body, class SetShape>
+int run_sweep(tp_batch_t b, int64_t chunk, Body body, SetShape set_shape) {
+    tp_handle_t h = b->h;
+    const tp_launch_info_t keep_launch = h->last_launch;
+    Span& span = timed_span(h);
+    HIP_TRY(h, span.begin(h->stream));
+    int rc = in_groups(b->W, chunk, body);
+    h->last_launch = keep_launch;
+    if (rc == TP_OK) rc = timed_done(h, span);
+    if (rc != TP_OK) return rc;
+    set_shape();
+    return end_launches(b);                            // (the sweep reads the batch's inputs and writes none of its results)
+}
+
+// Tiled sweeps: the Gram stage of the batch's own tiled pipeline over the windows [w0, w0 + n) of a sub-range, every pass of
+// `passes` per group of as many windows as the run workspace holds (`cap`); the kept-matrix store covers the sub-range
+int tiled_gram_stage(tp_batch_t b, const char* what, std::initializer_list<tp_kargs_t*> passes, const tp_tiled_ws_t& ws, int64_t cap,
+                     int64_t w0, int64_t n) {
+    return in_groups(n, cap, [&](int64_t g0, int64_t ng) {
+        for (tp_kargs_t* g : passes) {
+            g->w_first = w0 + g0; g->w_count = ng;
+            g->post_w0 = w0; g->post_count = n;
+            const int rc = launched(b->h, tp_tiled_gram_launch(*g, ws, b->h->stream, false), what);
+            if (rc != TP_OK) return rc;
+        }
+        return TP_OK;
+    });
+}
+
+// ---- solve sweeps -----------------------------------------------------------------------------------------------------
+
+// What the two solve sweeps share - tp_batch_solve_sweep (`tiled` = false, k <= tp_sweep_max_assets()) and
+// tp_batch_solve_sweep_tiled (above it): the argument checks, the drain, the windows per sub-range (one k x k matrix per
+// window), the sweep's buffers and the copies of the caller's arrays.  *chunk_out = 0: W = 0, nothing to launch (the shape is set).
+int solve_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_shift, const double* shift, int32_t n_rhs,
+                        const double* rhs, int32_t default_rhs, int* S_out, int* R_out, int64_t* chunk_out) {
+    tp_handle_t h = b->h;
+    SolveSweepWs& ws = b->sw;
+    const int k = b->p.k;
+    const int64_t W = b->W;
+    *chunk_out = 0;
+    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
+    if (n_shift < 0) return fail(h, TP_ERR_INVALID, "%s: n_shift=%d < 0", name, n_shift);
+    if (n_rhs < 0) return fail(h, TP_ERR_INVALID, "%s: n_rhs=%d < 0", name, n_rhs);
+    if (shift && b->p.strategy != TP_STRATEGY_JEFFREYS)
+        return fail(h, TP_ERR_INVALID, "%s: a shift applies to the Jeffreys strategy only", name);
+    if (shift && n_shift < 1) return fail(h, TP_ERR_INVALID, "%s: shift given with n_shift=0", name);
+    if (!shift && n_shift > 1) return fail(h, TP_ERR_INVALID, "%s: n_shift=%d without shift", name, n_shift);
+    const int S = n_shift > 1 ? n_shift : 1;
+    const long long R = (default_rhs ? 1 : 0) + (long long)n_rhs;
+    if (R < 1 || R > TP_SWEEP_MAX_RHS)
+        return fail(h, TP_ERR_INVALID, "%s: %lld right-hand sides per window outside [1, %d]", name, R, TP_SWEEP_MAX_RHS);
+    if (n_rhs > 0 && !rhs) return fail(h, TP_ERR_INVALID, "%s: n_rhs=%d without rhs", name, n_rhs);
+    int rc = shift ? check_finite_sign(h, name, "shift", shift, 2 * W * S, false) : TP_OK;
+    if (rc == TP_OK) rc = check_sweep_k(h, tiled, name, "tp_batch_solve_sweep", k);
+    if (rc != TP_OK) return rc;
+    if (tiled && k + R > tp_max_assets() + 1)
+        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d with %lld right-hand sides exceeds the arena side %d", name, k, R, tp_max_assets() + 1);
+    rc = drain_for_sweep(b);
+    if (rc != TP_OK) return rc;
+    ws.S = 0; ws.R = 0;
+    *S_out = S; *R_out = (int)R;
+    if (W == 0) { ws.S = S; ws.R = (int)R; return TP_OK; }
+    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
+    const int64_t chunk = sweep_chunk(h, mat_bytes, S, W, tiled);
+    const std::string what = std::string(name) + ": ";
+    rc = ensure(h, ws.post, mat_bytes * (size_t)chunk, (what + "kept matrices of one sub-range").c_str());
+    if (!tiled) {                                      // outputs of the run kernel that serves as the Gram pass
+        if (rc == TP_OK) rc = ensure(h, ws.weights, sizeof(double) * (size_t)W * k, (what + "weights of the Gram pass").c_str());
+        if (rc == TP_OK) rc = ensure(h, ws.status, sizeof(int32_t) * (size_t)W, (what + "statuses of the Gram pass").c_str());
+        if (rc == TP_OK) rc = ensure(h, ws.aux, sizeof(double) * (size_t)W * TP_AUX_STRIDE, (what + "aux of the Gram pass").c_str());
+    }
+    if (rc == TP_OK) rc = ensure(h, ws.rhs0, sizeof(double) * (size_t)W * k, (what + "default right-hand sides").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.x, sizeof(double) * (size_t)W * S * (size_t)R * k, (what + "solutions").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.xstatus, sizeof(int32_t) * (size_t)W * S, (what + "solution statuses").c_str());
+    if (rc == TP_OK && shift) rc = ensure(h, ws.shift, sizeof(double) * 2 * (size_t)W * S, (what + "shifts").c_str());
+    if (rc == TP_OK && n_rhs > 0) rc = ensure(h, ws.rhs, sizeof(double) * (size_t)W * n_rhs * k, (what + "right-hand sides").c_str());
+    if (rc != TP_OK) return rc;
+    // the caller's arrays: copied here, no host pointer is kept
+    if (shift) HIP_TRY(h, hipMemcpyAsync(ws.shift.p, shift, sizeof(double) * 2 * (size_t)W * S, hipMemcpyHostToDevice, h->stream));
+    if (n_rhs > 0) HIP_TRY(h, hipMemcpyAsync(ws.rhs.p, rhs, sizeof(double) * (size_t)W * n_rhs * k, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
+    *chunk_out = chunk;
+    return TP_OK;
+}
+
+// The sweep's own tiled workspace (arena, inverse diagonal blocks, flags) at the sweep's geometry, KP from k + R: as many
+// (window, shift) entries as the large-k arena budget allows (tiled_arena_entries, the rule ensure_tiled_ws sizes by; what this
+// workspace already holds counts as free), at most `entries`.  The batch's run workspace is left as it is.
+int ensure_sweep_tiled_ws(tp_batch_t b, int R, int64_t entries, tp_tiled_ws_t* ws, int64_t* cap_out) {
+    tp_handle_t h = b->h;
+    SolveSweepWs& sw = b->sw;
+    int KP, NS, NSB;
+    tp_solve_sweep_tiled_geometry(b->p.k, R, &KP, &NS, &NSB);
+    const size_t per_entry = sizeof(double) * ((size_t)KP * KP + (size_t)NSB * 64 * 64) + sizeof(int);
+    int64_t G = tiled_arena_entries(h, per_entry, 1, sw.arena.bytes + sw.rinv.bytes + sw.flags.bytes);
+    if (G > entries) G = entries;
+    int rc = ensure(h, sw.arena, sizeof(double) * (size_t)G * KP * KP, "tp_batch_solve_sweep_tiled: arena");
+    if (rc == TP_OK) rc = ensure(h, sw.rinv, sizeof(double) * (size_t)G * NSB * 64 * 64, "tp_batch_solve_sweep_tiled: inverse diagonal blocks");
+    if (rc == TP_OK) rc = ensure(h, sw.flags, sizeof(int) * (size_t)G, "tp_batch_solve_sweep_tiled: flags");
+    if (rc != TP_OK) return rc;
+    memset(ws, 0, sizeof *ws);
+    ws->arena = (double*)sw.arena.p; ws->rinv = (double*)sw.rinv.p; ws->flags = (int*)sw.flags.p;
+    ws->KP = KP; ws->NS = NS; ws->NSB = NSB;
+    *cap_out = G;
+    return TP_OK;
+}
+
+// ---- prior sweeps and the size sweep ------------------------------------------------------------------------------------
+
+// What the prior sweeps and the size sweep share - tp_batch_prior_sweep (`tiled` = false, k <= tp_sweep_max_assets()),
+// tp_batch_prior_sweep_tiled (above it) and tp_batch_size_sweep (`sz` given: n_size universes per (window, prior), a Jeffreys
+// batch allowed - without priors), each on the workspace `ws` of its own: the argument checks, the drain, the windows per
+// sub-range (C and T: two k x k matrices per window), the sweep's buffers and the copies of the caller's arrays.
+// *chunk_out = 0: W = 0, nothing to launch (the sweep's shape is set).
+struct SizeAxis { int32_t n_size; const int32_t* sizes; };
+int prior_sweep_prepare(tp_batch_t b, PriorSweepWs& ws, const char* name, bool tiled, int32_t n_prior, const double* n0,
+                        const double* w0, int64_t* chunk_out, const SizeAxis* sz = nullptr) {
+    tp_handle_t h = b->h;
+    const int k = b->p.k;
+    const int64_t W = b->W;
+    *chunk_out = 0;
+    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
+    if (!sz && !conj) return fail(h, TP_ERR_INVALID, "%s applies to the conjugate strategy only", name);
+    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
+    if (sz) {
+        if (sz->n_size < 1 || sz->n_size > TP_SWEEP_MAX_RHS)
+            return fail(h, TP_ERR_INVALID, "%s: n_size=%d outside [1, %d]", name, sz->n_size, TP_SWEEP_MAX_RHS);
+        if (!sz->sizes) return fail(h, TP_ERR_INVALID, "%s: sizes is NULL", name);
+        for (int s = 0; s < sz->n_size; ++s)
+            if (sz->sizes[s] < 1 || sz->sizes[s] > k || (s > 0 && sz->sizes[s] <= sz->sizes[s - 1]))
+                return fail(h, TP_ERR_INVALID, "%s: sizes[%d]=%d: strictly increasing sizes within [1, %d] expected", name, s, sz->sizes[s], k);
+    }
+    if (sz && !conj && (n_prior != 0 || n0 || w0))
+        return fail(h, TP_ERR_INVALID, "%s: a Jeffreys batch takes no priors (n_prior = 0, n0 = w0 = NULL)", name);
+    const int P = conj ? n_prior : 1;
+    const int S = sz ? sz->n_size : 1;
+    int rc = TP_OK;
+    if (conj) {
+        if (n_prior < 1) return fail(h, TP_ERR_INVALID, "%s: n_prior=%d < 1", name, n_prior);
+        if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "%s: %s is NULL", name, !n0 ? "n0" : "w0");
+        rc = check_finite_sign(h, name, "n0", n0, W * P, true);
+        if (rc != TP_OK) return rc;
+        for (int64_t e = 0; e < W * P * S; ++e) {          // (a size sweep reads the first sizes[s] entries of a vector only)
+            const int ke = sz ? sz->sizes[e % S] : k;
+            for (int i = 0; i < ke; ++i)
+                if (!std::isfinite(w0[e * k + i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)(e * k + i));
+        }
+    }
+    rc = check_sweep_k(h, tiled, name, "tp_batch_prior_sweep", k);
+    if (rc == TP_OK) rc = drain_for_sweep(b);
+    if (rc != TP_OK) return rc;
+    ws.P = 0; ws.S = 0;
+    if (W == 0) { ws.P = P; ws.S = S; return TP_OK; }
+    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
+    const int64_t chunk = sweep_chunk(h, 2 * mat_bytes, P, W, true);
+    const size_t WP = (size_t)W * (size_t)P;
+    const size_t WPS = WP * (size_t)S;
+    const std::string what = std::string(name) + ": ";
+    if (conj) rc = ensure(h, ws.C, mat_bytes * (size_t)chunk, (what + "intraday scatters of one sub-range").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.T, mat_bytes * (size_t)chunk, (what + (conj ? "daily Grams of one sub-range" : "matrices of one sub-range")).c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.t, sizeof(double) * (size_t)W * k, (what + "daily column sums").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, ws.n0, sizeof(double) * WP, (what + "prior strengths").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, ws.w0, sizeof(double) * WPS * k, (what + "prior weights").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.weights, sizeof(double) * WPS * k, (what + "weights").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.status, sizeof(int32_t) * WPS, (what + "statuses").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.aux, sizeof(double) * WPS * TP_AUX_STRIDE, (what + "aux").c_str());
+    if (rc == TP_OK && sz) rc = ensure(h, ws.sizes, sizeof(int32_t) * (size_t)S, (what + "sizes").c_str());
+    if (rc == TP_OK && sz && !conj) {                      // outputs of the run kernel that serves as the Gram pass
+        rc = ensure(h, ws.gw, sizeof(double) * (size_t)W * k, (what + "weights of the Gram pass").c_str());
+        if (rc == TP_OK) rc = ensure(h, ws.gs, sizeof(int32_t) * (size_t)W, (what + "statuses of the Gram pass").c_str());
+        if (rc == TP_OK) rc = ensure(h, ws.ga, sizeof(double) * (size_t)W * TP_AUX_STRIDE, (what + "aux of the Gram pass").c_str());
+    }
+    if (rc != TP_OK) return rc;
+    // the caller's arrays: copied here, no host pointer is kept
+    if (conj) {
+        HIP_TRY(h, hipMemcpyAsync(ws.n0.p, n0, sizeof(double) * WP, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(ws.w0.p, w0, sizeof(double) * WPS * k, hipMemcpyHostToDevice, h->stream));
+    }
+    if (sz) HIP_TRY(h, hipMemcpyAsync(ws.sizes.p, sz->sizes, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
+    *chunk_out = chunk;
+    return TP_OK;
+}
+
+// Gram pass of a prior sweep or a conjugate size sweep (posterior_gram_nt.hip) over the windows [w0, w0 + n): the windows' rows
+// as a plain run reads them, no prior; C and T of the sub-range and t go into `ws`
+int gram_pass(tp_batch_t b, const char* name, const char* what, tp_gram_kargs_t& ga, int64_t w0, int64_t n) {
+    ga.in.w_first = w0; ga.in.w_count = n;
+    const hipError_t e = tp_gram_launch(ga, b->h->stream);
+    if (e == hipErrorNotSupported)
+        return fail(b->h, TP_ERR_UNSUPPORTED, "%s: windows of %d daily / %d intraday rows in the index layout are "
+                                              "too long for the Gram pass", name, b->p.n_r, b->p.m);
+    return launched(b->h, e, what);
+}
+
+tp_gram_kargs_t gram_pass_kargs(tp_batch_t b, const PriorSweepWs& ws) {
+    tp_gram_kargs_t ga;
+    memset(&ga, 0, sizeof ga);
+    ga.in = neutral_kargs(b);
+    ga.in.w0 = nullptr; ga.in.n0 = nullptr;
+    ga.C = (double*)ws.C.p; ga.T = (double*)ws.T.p; ga.t = (double*)ws.t.p;
+    return ga;
+}
+
+// the results of the last sweep on `ws`: [W x P x S] weight vectors, statuses and aux rows (W = 0: nothing to copy)
+int download_prior_ws(tp_batch_t b, const PriorSweepWs& ws, double* weights, int32_t* status, double* aux) {
+    HIP_TRY(b->h, hipSetDevice(b->h->device));
+    const size_t n = (size_t)b->W * ws.P * ws.S;
+    return download(b->h, {{weights, ws.weights.p, sizeof(double) * n * b->p.k}, {status, ws.status.p, sizeof(int32_t) * n},
+                           {aux, ws.aux.p, sizeof(double) * n * TP_AUX_STRIDE}});
+}
+
+}  // namespace
+
+extern "C" {
+
+// Solve sweep.  Per sub-range the batch's own run kernel stores the matrices of the sub-range (the keep_posterior store) and
+// every window's default right-hand side (the keep_rhs store) into the sweep's workspace, then posterior_sweep_kernel solves
+// the sub-range's (window, shift) pairs.
+int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift, int32_t n_rhs, const double* rhs,
+                         int32_t default_rhs) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    SolveSweepWs& ws = b->sw;
+    int S = 0, R = 0;
+    int64_t chunk = 0;
+    int rc = solve_sweep_prepare(b, "tp_batch_solve_sweep", false, n_shift, shift, n_rhs, rhs, default_rhs, &S, &R, &chunk);
+    if (rc != TP_OK || chunk == 0) return rc;
+    tp_kargs_t a = neutral_kargs(b);
+    a.weights = (double*)ws.weights.p; a.status = (int*)ws.status.p; a.aux = (double*)ws.aux.p;
+    a.out_rhs = (double*)ws.rhs0.p;
+    a.out_post = (double*)ws.post.p;
+    tp_sweep_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.post = (const double*)ws.post.p;
+    sa.default_rhs = default_rhs ? (const double*)ws.rhs0.p : nullptr;
+    sa.rhs = n_rhs > 0 ? (const double*)ws.rhs.p : nullptr;
+    sa.shift = shift ? (const double*)ws.shift.p : nullptr;
+    sa.x = (double*)ws.x.p;
+    sa.status = (int*)ws.xstatus.p;
+    sa.k = b->p.k; sa.S = S; sa.R = R; sa.n_rhs = n_rhs;
+    sa.gamma = b->p.gamma;
+    return run_sweep(b, chunk, [&](int64_t w0, int64_t n) {
+        a.w_first = w0; a.w_count = n;
+        a.post_w0 = w0; a.post_count = n;
+        const int rcl = launch(b, a, n, false);
+        if (rcl != TP_OK) return rcl;
+        sa.w_first = w0; sa.w_count = n;
+        return launched(h, tp_sweep_launch(sa, h->stream), "sweep kernel");
+    }, [&] { ws.S = S; ws.R = R; });
+}
+
+// Solve sweep above tp_sweep_max_assets(), on the large-k tiled pipeline.  Per sub-range the batch's own tiled Gram stage - its
+// real strategy - leaves M_w in sw.post (the kept-matrix store) and the default right-hand side in sw.rhs0 (the
+// kept-right-hand-side store).  Then the sub-range's (window, shift) pairs go through the SWEEP's workspace in groups of its
+// capacity: posterior_solve_sweep_tiled.hip fills them, the block steps of the tiled factorisation factorise them and
+// forward-substitute the R columns, and the sweep's own kernel back-substitutes.
+int tp_batch_solve_sweep_tiled(tp_batch_t b, int32_t n_shift, const double* shift, int32_t n_rhs, const double* rhs,
+                               int32_t default_rhs) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    SolveSweepWs& sw = b->sw;
+    int S = 0, R = 0;
+    int64_t chunk = 0;
+    int rc = solve_sweep_prepare(b, "tp_batch_solve_sweep_tiled", true, n_shift, shift, n_rhs, rhs, default_rhs, &S, &R, &chunk);
+    if (rc != TP_OK || chunk == 0) return rc;
+    // the batch's run workspace (lane 0) as a run would size it, for the Gram stage; the sweep's own for the entries
+    tp_tiled_ws_t wsl[TP_MAX_LANES];
+    int lanes = 1;
+    rc = ensure_tiled_ws(b, wsl, &lanes);
+    if (rc != TP_OK) return rc;
+    const int64_t gcap = b->tiled_capacity;
+    tp_tiled_ws_t ws;
+    int64_t cap = 0;
+    rc = ensure_sweep_tiled_ws(b, R, chunk * S, &ws, &cap);
+    if (rc != TP_OK) return rc;
+    tp_kargs_t a = neutral_kargs(b);                   // (the Gram stage writes no weights, statuses or aux)
+    a.out_rhs = (double*)sw.rhs0.p;
+    a.out_post = (double*)sw.post.p;
+    tp_solve_sweep_tiled_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.post = (const double*)sw.post.p;
+    sa.default_rhs = default_rhs ? (const double*)sw.rhs0.p : nullptr;
+    sa.rhs = n_rhs > 0 ? (const double*)sw.rhs.p : nullptr;
+    sa.shift = shift ? (const double*)sw.shift.p : nullptr;
+    sa.x = (double*)sw.x.p;
+    sa.status = (int*)sw.xstatus.p;
+    sa.k = b->p.k; sa.S = S; sa.R = R; sa.n_rhs = n_rhs;
+    sa.gamma = b->p.gamma;
+    // the block steps read k, w_count (set per group below) and the kernel choices; everything else stays zero
+    tp_kargs_t fa;
+    memset(&fa, 0, sizeof fa);
+    fa.k = b->p.k;
+    fa.opts = h->opts;
+    return run_sweep(b, chunk, [&](int64_t w0, int64_t n) {
+        const int rcg = tiled_gram_stage(b, "tiled solve sweep Gram", {&a}, wsl[0], gcap, w0, n);
+        if (rcg != TP_OK) return rcg;
+        return in_groups(n * S, cap, [&](int64_t e0, int64_t ne) {
+            sa.wc_first = w0;
+            sa.e_first = w0 * S + e0; sa.e_count = ne;
+            int rce = launched(h, tp_solve_sweep_tiled_fill_launch(sa, ws, h->stream), "tiled solve sweep fill");
+            fa.w_count = ne;
+            if (rce == TP_OK) rce = launched(h, tp_tiled_block_steps_launch(fa, ws, h->stream), "tiled solve sweep factor");
+            if (rce == TP_OK) rce = launched(h, tp_solve_sweep_tiled_solve_launch(sa, ws, h->stream), "tiled solve sweep solve");
+            return rce;
+        });
+    }, [&] { sw.S = S; sw.R = R; });
+}
+
+int tp_batch_download_sweep(tp_batch_t b, double* x, int32_t* status) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    const SolveSweepWs& ws = b->sw;
+    if (ws.S < 1 || ws.R < 1)
+        return fail(h, TP_ERR_INVALID, "tp_batch_download_sweep: no tp_batch_solve_sweep before it");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)b->W * ws.S;              // (W = 0: nothing to copy)
+    return download(h, {{x, ws.x.p, sizeof(double) * n * ws.R * b->p.k}, {status, ws.xstatus.p, sizeof(int32_t) * n}});
+}
+
+int tp_batch_download_sweep_rhs(tp_batch_t b, double* rhs_out) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    if (b->sw.S < 1 || b->sw.R < 1)
+        return fail(h, TP_ERR_INVALID, "tp_batch_download_sweep_rhs: no tp_batch_solve_sweep before it");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (b->W > 0 && !rhs_out) return fail(h, TP_ERR_INVALID, "tp_batch_download_sweep_rhs: rhs_out is NULL");
+    return download(h, {{rhs_out, b->sw.rhs0.p, sizeof(double) * (size_t)b->W * b->p.k}});
+}
+
+// Prior sweep.  Per sub-range the Gram pass stores C and T of the sub-range and t, then posterior_prior_sweep_kernel solves
+// the sub-range's (window, prior) pairs.
+int tp_batch_prior_sweep(tp_batch_t b, int32_t n_prior, const double* n0, const double* w0) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    PriorSweepWs& ws = b->ps;
+    const int P = n_prior;
+    int64_t chunk = 0;
+    int rc = prior_sweep_prepare(b, ws, "tp_batch_prior_sweep", false, n_prior, n0, w0, &chunk);
+    if (rc != TP_OK || chunk == 0) return rc;
+    tp_gram_kargs_t ga = gram_pass_kargs(b, ws);
+    tp_prior_sweep_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.C = (const double*)ws.C.p; sa.T = (const double*)ws.T.p; sa.t = (const double*)ws.t.p;
+    sa.n0 = (const double*)ws.n0.p; sa.w0 = (const double*)ws.w0.p;
+    sa.hf_count = (const int*)b->hf_count.p;
+    sa.weights = (double*)ws.weights.p; sa.status = (int*)ws.status.p; sa.aux = (double*)ws.aux.p;
+    sa.k = b->p.k; sa.P = P; sa.N = b->p.N; sa.m = b->p.m;
+    sa.gamma = b->p.gamma;
+    return run_sweep(b, chunk, [&](int64_t wf, int64_t n) {
+        const int rcg = gram_pass(b, "tp_batch_prior_sweep", "prior sweep Gram", ga, wf, n);
+        if (rcg != TP_OK) return rcg;
+        sa.w_first = wf; sa.w_count = n;
+        return launched(h, tp_prior_sweep_launch(sa, h->stream), "prior sweep kernel");
+    }, [&] { ws.P = P; ws.S = 1; });
+}
+
+// Prior sweep above tp_sweep_max_assets(), on the large-k tiled pipeline.  Per sub-range the batch's own tiled Gram stage runs
+// twice, steered by its arguments - as a Jeffreys batch without centring over the daily rows (T into ps.T through the
+// kept-matrix store, t into ps.t through the kept-right-hand-side store) and as a Jeffreys batch centred by the window's row
+// count over the INTRADAY rows, the daily-panel fields pointed at the intraday panel (C = Y'Y - (Y'1)(Y'1)'/m into ps.C).
+// Then the sub-range's (window, prior) pairs go through the batch's run workspace - borrowed, and grown to hold them - in
+// groups of at most tiled_capacity entries: posterior_prior_sweep_tiled.hip fills them, tp_tiled_factor_launch factorises and
+// solves them into the sweep's buffers.
+int tp_batch_prior_sweep_tiled(tp_batch_t b, int32_t n_prior, const double* n0, const double* w0) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    PriorSweepWs& ps = b->ps;
+    const int P = n_prior;
+    int64_t chunk = 0;
+    int rc = prior_sweep_prepare(b, ps, "tp_batch_prior_sweep_tiled", true, n_prior, n0, w0, &chunk);
+    if (rc != TP_OK || chunk == 0) return rc;
+    // the batch's own tiled workspace (lane 0) and the pieces of a C w0 per arena entry
+    tp_tiled_ws_t wsl[TP_MAX_LANES];
+    int lanes = 1;
+    rc = ensure_tiled_ws(b, wsl, &lanes, chunk * P);
+    if (rc != TP_OK) return rc;
+    const int64_t cap = b->tiled_capacity;
+    rc = ensure(h, b->t_part[0], sizeof(double) * (size_t)cap * wsl[0].NS * wsl[0].NS * 64, "tp_batch_prior_sweep_tiled: prior products");
+    if (rc != TP_OK) return rc;
+    tp_tiled_ws_t ws = wsl[0];
+    ws.part = (double*)b->t_part[0].p;
+
+    // T and t: the daily rows as a plain run reads them, uncentred and without the prior
+    tp_kargs_t ta = neutral_kargs(b);
+    ta.strategy = TP_STRATEGY_JEFFREYS;
+    ta.center_rows = 2;
+    ta.w0 = nullptr; ta.n0 = nullptr;
+    ta.out_rhs = (double*)ps.t.p;
+    ta.out_post = (double*)ps.T.p;
+    // C: the same stage over the intraday rows - the daily-panel fields name the intraday panel (its own 32-bit offset flags:
+    // make_kargs formed hf_off32 from that panel's bytes, leading dimension and m), centred by the window's row count
+    tp_kargs_t ca = ta;
+    ca.panel = ta.hf_panel; ca.start = ta.hf_start; ca.row_idx = ta.hf_row_idx; ca.n_rows = ta.hf_count;
+    ca.n_r = b->p.m; ca.rf_adj = nullptr;
+    ca.panel_ld = ta.hf_ld; ca.panel_off32 = ta.hf_off32;
+    ca.center_rows = 1;
+    ca.out_rhs = nullptr;
+    ca.out_post = (double*)ps.C.p;
+    for (tp_kargs_t* g : {&ta, &ca}) { g->hf_panel = nullptr; g->hf_start = nullptr; g->hf_row_idx = nullptr; g->hf_count = nullptr; g->hf_off32 = 0; }
+    tp_prior_sweep_tiled_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.C = (const double*)ps.C.p; sa.T = (const double*)ps.T.p; sa.t = (const double*)ps.t.p;
+    sa.n0 = (const double*)ps.n0.p; sa.w0 = (const double*)ps.w0.p;
+    sa.hf_count = (const int*)b->hf_count.p;
+    sa.k = b->p.k; sa.P = P; sa.m = b->p.m;
+    // factorisation and solve of the arena entries: a conjugate "batch" of (window, prior) pairs writing the sweep's buffers
+    tp_kargs_t fa;
+    memset(&fa, 0, sizeof fa);
+    fa.strategy = TP_STRATEGY_CONJUGATE;
+    fa.k = b->p.k; fa.N = b->p.N; fa.n_r = b->p.n_r; fa.m = b->p.m; fa.gamma = b->p.gamma;
+    fa.opts = h->opts;
+    fa.weights = (double*)ps.weights.p; fa.status = (int*)ps.status.p; fa.aux = (double*)ps.aux.p;
+    fa.dbg_w = -1;
+    return run_sweep(b, chunk, [&](int64_t wf, int64_t n) {
+        const int rcg = tiled_gram_stage(b, "tiled prior sweep Gram", {&ta, &ca}, ws, cap, wf, n);
+        if (rcg != TP_OK) return rcg;
+        return in_groups(n * P, cap, [&](int64_t e0, int64_t ne) {
+            sa.wc_first = wf;
+            sa.e_first = wf * P + e0; sa.e_count = ne;
+            const int rce = launched(h, tp_prior_sweep_tiled_launch(sa, ws, h->stream), "tiled prior sweep fill");
+            if (rce != TP_OK) return rce;
+            fa.w_first = sa.e_first; fa.w_count = ne;
+            return launched(h, tp_tiled_factor_launch(fa, ws, h->stream), "tiled prior sweep factor");
+        });
+    }, [&] { ps.P = P; ps.S = 1; });
+}
+
+int tp_batch_download_prior_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux) {
+    if (!b) return TP_ERR_INVALID;
+    if (b->ps.P < 1) return fail(b->h, TP_ERR_INVALID, "tp_batch_download_prior_sweep: no tp_batch_prior_sweep before it");
+    return download_prior_ws(b, b->ps, weights, status, aux);
+}
+
+// Size sweep.  Sub-ranges as in tp_batch_prior_sweep.  Conjugate: the same Gram pass stores C, T and t.  Jeffreys: the batch's
+// own run kernel - as the solve sweep steers it, outputs into the sweep's buffers - keeps M (its centring flag applied) and t;
+// it reads the daily inputs only.  Then posterior_size_sweep_kernel factorises every (window, prior) once at k and solves
+// every size over its prefix.
+int tp_batch_size_sweep(tp_batch_t b, int32_t n_size, const int32_t* sizes, int32_t n_prior, const double* n0, const double* w0) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    PriorSweepWs& ws = b->zs;
+    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
+    const int P = conj ? n_prior : 1;
+    const SizeAxis sz{n_size, sizes};
+    int64_t chunk = 0;
+    int rc = prior_sweep_prepare(b, ws, "tp_batch_size_sweep", false, n_prior, n0, w0, &chunk, &sz);
+    if (rc != TP_OK || chunk == 0) return rc;
+    tp_gram_kargs_t ga = gram_pass_kargs(b, ws);       // conjugate
+    tp_kargs_t ja = neutral_kargs(b);                  // Jeffreys
+    ja.weights = (double*)ws.gw.p; ja.status = (int*)ws.gs.p; ja.aux = (double*)ws.ga.p;
+    ja.out_rhs = (double*)ws.t.p; ja.out_post = (double*)ws.T.p;
+    tp_size_sweep_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.C = conj ? (const double*)ws.C.p : nullptr;
+    sa.T = (const double*)ws.T.p; sa.t = (const double*)ws.t.p;
+    sa.n0 = conj ? (const double*)ws.n0.p : nullptr; sa.w0 = conj ? (const double*)ws.w0.p : nullptr;
+    sa.hf_count = (const int*)b->hf_count.p;
+    sa.sizes = (const int*)ws.sizes.p;
+    sa.weights = (double*)ws.weights.p; sa.status = (int*)ws.status.p; sa.aux = (double*)ws.aux.p;
+    sa.k = b->p.k; sa.P = P; sa.S = n_size; sa.N = b->p.N; sa.m = b->p.m;
+    sa.gamma = b->p.gamma;
+    return run_sweep(b, chunk, [&](int64_t wf, int64_t n) {
+        ja.w_first = wf; ja.w_count = n;
+        ja.post_w0 = wf; ja.post_count = n;
+        const int rcg = conj ? gram_pass(b, "tp_batch_size_sweep", "size sweep Gram", ga, wf, n) : launch(b, ja, n, false);
+        if (rcg != TP_OK) return rcg;
+        sa.w_first = wf; sa.w_count = n;
+        return launched(h, tp_size_sweep_launch(sa, h->stream), "size sweep kernel");
+    }, [&] { ws.P = P; ws.S = n_size; });
+}
+
+int tp_batch_download_size_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux) {
+    if (!b) return TP_ERR_INVALID;
+    if (b->zs.P < 1 || b->zs.S < 1) return fail(b->h, TP_ERR_INVALID, "tp_batch_download_size_sweep: no tp_batch_size_sweep before it");
+    return download_prior_ws(b, b->zs, weights, status, aux);
+}
+
+}  // extern "C"
