@@ -136,12 +136,12 @@ int tp_destroy(tp_handle_t h);
  * (TP_WAVE_KERNEL, TP_TILED_WAVE, TP_TILED_FUSE, TP_NO_SHARED_GRAM, TP_TILED_ARENA_GIB, TP_TILED_ARENA_MIB) are read
  * ONCE, in tp_create; afterwards only this call changes them - no launch reads the environment.
  *   "wave_kernel"      -1 automatic | 0 multi-wave register-tile kernel | 1 one-wave kernel | 2 two-wave kernel
- *   "tiled_wave"       -1 automatic | 0 four-wave Gram / diagonal-block kernels of the large-k path | 2 Gram with
- *                      two super-tiles per wavefront
+ *   "tiled_wave"       -1 automatic | 0 four-wave Gram / diagonal-block kernels of the large-k path | 1 one wavefront per
+ *                      super-tile / block (what automatic picks); any other value: TP_ERR_INVALID (in the
+ *                      environment: automatic)
  *   "tiled_fuse"       -1 automatic | 0 / 1 three-kernel / fused left-looking update of the large-k path
  *   "no_shared_gram"   1 = as if every batch carried TP_FLAG_NO_SHARED_GRAM (takes effect at the next upload)
- *   "tiled_arena_gib" / "tiled_arena_mib"  in-flight arena of the large-k path, per lane (0: default)
- *   "tiled_lanes"      sub-batches of the large-k path in flight at once, each on a stream of its own (0 / 1: one)
+ *   "tiled_arena_gib" / "tiled_arena_mib"  in-flight arena of the large-k path (0: default)
  *   "hf_share_min_blocks"  large-k path, conjugate: intraday windows that advance by a fixed stride share the Grams of
  *                      their whole stride-long blocks from this many whole blocks per window on (default 6; takes effect
  *                      at the next upload; "no_shared_gram" switches the scheme off)

@@ -37,7 +37,7 @@
 //
 // Notes for whoever edits this file (each cost a measurable factor on MI355X):
 //  * tile coordinates must be compile-time constants (for_tiles / static_for) and the whole window
-//    body is instantiated per wave index (TP_WAVE_SPECIALISE): otherwise the accumulator array is
+//    body is instantiated per wave index (posterior_fused_kernel): otherwise the accumulator array is
 //    indexed through pointer-phis and lands in scratch;
 //  * build with -mllvm -sink-common-insts=false for the same reason;
 //  * nothing may consume a prefetched panel value before the MFMA block (load_chunk), and the
@@ -49,10 +49,7 @@
 // (included by posterior_fused_nt.hip, once per tile count NT)
 
 // how many 4-row MFMA k-steps of a staged chunk are unrolled together (operand reads in flight)
-#ifndef TP_KSTEP_UNROLL
-#define TP_KSTEP_UNROLL 1
-#endif
-constexpr int tp_kstep_unroll = TP_KSTEP_UNROLL;
+constexpr int tp_kstep_unroll = 1;
 
 // Diagnostic build only (make TP_STAMP=1): per-window s_memtime stamps at the phase boundaries, written
 // to a buffer of their own (never into an output).  The product build compiles none of this.
@@ -1152,38 +1149,25 @@ __device__ __forceinline__ void window_body(const tp_kargs_t& A, double* lds, co
     TP_MARK(7);
 }
 
-// TP_WAVE_SPECIALISE = 1: the whole window body is instantiated once per wave index (tile
-// coordinates are immediates everywhere, accumulators never cross a dispatch merge);
-// 0: only the tile-touching snippets branch on the wave index.
+// The whole window body is instantiated once per wave index (tile coordinates are immediates
+// everywhere, accumulators never cross a dispatch merge).
 // Occupancy the register allocator is asked to keep (wavefronts per SIMD; for NW = 4 that is
 // workgroups per CU).  The serial pivot chain of the factorisation is hidden by windows in flight,
 // not by ILP: on MI355X 4 resident windows per CU with ~270 spilled dwords beat 2 without spills
 // (5.7 vs 4.1 M windows/s at k=100).  Tile counts whose accumulators alone exceed the budget get less.
-#ifdef TP_MIN_WAVES_PER_SIMD
-constexpr int tp_min_waves_for_tiles(int) { return TP_MIN_WAVES_PER_SIMD; }
-#else
 constexpr int tp_min_waves_for_tiles(int nt) {
     // measured per tile count (tools/sweep_k.py): nt 9: 3 -> +12 % over 2 (k=143); nt 11-12: 2 -> +35 % over 1 (k=175, 191)
     return nt <= 7 ? 4 : nt <= 9 ? 3 : 2;       // nt 6: 4 waves per window at 4 waves/SIMD, +6 % over 2 x 2 (k=95)
 }
-#endif
-
-#ifndef TP_WAVE_SPECIALISE
-#define TP_WAVE_SPECIALISE 1
-#endif
 
 template <int NT, int NW, bool LEAN>
 __global__ void __launch_bounds__(64 * NW, tp_min_waves_for_tiles(NT)) posterior_fused_kernel(const tp_kargs_t A) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if TP_WAVE_SPECIALISE
     wave_dispatch<NW>(wv, [&](auto wc) __attribute__((always_inline)) {
         window_body<NT, NW, decltype(wc)::value, LEAN>(A, lds, tid, decltype(wc)::value);
     });
-#else
-    window_body<NT, NW, -1, LEAN>(A, lds, tid, wv);
-#endif
 }
 
 // Grams of the aligned C::CH-row blocks of the daily panel, one workgroup per block, with the staging and MFMA loop of
@@ -1290,8 +1274,4 @@ int blocks_per_cu() {
 
 // wavefronts per workgroup for a tile count: the tiles (NT (NT+1)/2 x 8 accumulator registers, spread over the
 // waves) must fit the register file at the occupancy tp_min_waves_for_tiles asks for; measured per tile count
-#ifdef TP_NW_OVERRIDE
-constexpr int tp_waves_for_tiles(int) { return TP_NW_OVERRIDE; }
-#else
 constexpr int tp_waves_for_tiles(int nt) { return nt <= 3 ? 1 : (nt <= 5 ? 2 : (nt <= 12 ? 4 : 8)); }
-#endif

@@ -13,7 +13,7 @@
 // them from the batch's arguments, never from the environment.
 struct tp_kopts_t {
     int wave_kernel = -1;   // register-tile path: 0 = multi-wave kernel, 1 = one-wave kernel (k <= 143), 2 = two-wave kernel
-    int tiled_wave = -1;    // large-k path: 0 = the 4-wave Gram / diagonal-block kernels
+    int tiled_wave = -1;    // large-k path: 0 = the 4-wave Gram / diagonal-block kernels, 1 = the one-wave kernels (-1, 0, 1 only)
     int tiled_fuse = -1;    // large-k path: 0 / 1 = three-kernel / fused left-looking update + solve
 };
 
@@ -127,17 +127,8 @@ __host__ __device__ inline double* tp_post_window(const tp_kargs_t& a, long long
     return (a.out_post != nullptr && p >= 0 && p < a.post_count) ? a.out_post + p * (long long)a.k * a.k : nullptr;
 }
 // Stores of the kept matrices: written once, read by nobody on the device - non-temporal, so that they do not evict the
-// panel rows the windows share from L2 / MALL.  TP_POST_NT=0 builds plain stores (A/B measurements).
-#ifndef TP_POST_NT
-#define TP_POST_NT 1
-#endif
-__device__ __forceinline__ void tp_post_store(double* p, double v) {
-#if TP_POST_NT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
+// panel rows the windows share from L2 / MALL.  (Against plain stores: not measured)
+__device__ __forceinline__ void tp_post_store(double* p, double v) { __builtin_nontemporal_store(v, p); }
 
 // register-tile fused kernel (posterior_fused.hip): k <= tp_fused_max_assets()
 int tp_fused_max_assets(void);
@@ -160,7 +151,6 @@ struct tp_tiled_ws_t {
 int tp_tiled_max_assets(void);
 void tp_tiled_geometry(int k, int* KP, int* NS, int* NSB);
 hipError_t tp_tiled_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream, bool build_prefix);
-hipError_t tp_tiled_prefix_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream);
 // the two halves of tp_tiled_launch: the Gram stage leaves the bordered matrices in the arena (and stores out_rhs / out_post);
 // the factor stage factorises and solves whatever a.w_count matrices the arena holds (entry e -> output slot a.w_first + e)
 hipError_t tp_tiled_gram_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream, bool build_prefix);

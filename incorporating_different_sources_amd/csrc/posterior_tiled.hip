@@ -806,12 +806,9 @@ void tp_tiled_geometry(int k, int* KP, int* NS, int* NSB) {
 // rate (9.5 % of the run).  Runs after tiled_diag*_kernel(j), which needs the updated tile (j, j) first (its own launch).
 // Staging as in tile64_kernel; in the TRSM part the B half of chunk c (rows 16c..16c+15 of the tile) comes from the
 // accumulators of wave c instead of from memory.
-// chunks of operand loads in flight in the left-looking update.  2 (A/B build -DTP_SYRK_DEPTH=2, round 3: 136 instead of
-// 112 registers, three instead of four workgroups per CU) measured 32.0 / 18.4 ms against 31.7 / 18.3 ms per 8,192 windows
-// at k = 500 (conjugate / Jeffreys): the kernel is bound by HBM bytes (4.6 TB/s read + written), not by their latency
-#ifndef TP_SYRK_DEPTH
-#define TP_SYRK_DEPTH 1
-#endif
+// ONE chunk of operand loads in flight in the left-looking update.  Two (round 3: 136 instead of 112 registers, three
+// instead of four workgroups per CU) measured 32.0 / 18.4 ms against 31.7 / 18.3 ms per 8,192 windows at k = 500
+// (conjugate / Jeffreys): the kernel is bound by HBM bytes (4.6 TB/s read + written), not by their latency
 __global__ void __launch_bounds__(NTHREADS) tile64_syrk_trsm_kernel(const tp_kargs_t A, const tp_tiled_ws_t ws, const int j) {
     __shared__ __attribute__((aligned(16))) double lds[2 * CH * LDX];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -856,27 +853,7 @@ __global__ void __launch_bounds__(NTHREADS) tile64_syrk_trsm_kernel(const tp_kar
                 acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, lb[4 * s4 * LDX + 64 + 16 * b], acc[b], 0, 0, 1);
         }
     };
-    double* buf0 = lds;
-#if TP_SYRK_DEPTH == 2
-    double* buf1 = lds + CH * LDX;
-    double v2[8];
-    if (nchunks > 0) { load(v, 0); store(buf0, v); }
-    if (nchunks > 1) load(v, 1);
-    __syncthreads();
-    for (int ch = 0; ch < nchunks; ch += 2) {             // nchunks = 4 j: even
-        if (ch + 2 < nchunks) load(v2, ch + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(buf0);
-        store(buf1, v);                                    // chunk ch + 1
-        __syncthreads();
-        if (ch + 3 < nchunks) load(v, ch + 3);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(buf1);
-        if (ch + 2 < nchunks) store(buf0, v2);
-        __syncthreads();
-    }
-#else
-    if (nchunks > 0) { load(v, 0); store(buf0, v); }
+    if (nchunks > 0) { load(v, 0); store(lds, v); }
     __syncthreads();
     for (int ch = 0; ch < nchunks; ++ch) {
         double* cur = lds + (ch & 1) * CH * LDX;
@@ -888,7 +865,6 @@ __global__ void __launch_bounds__(NTHREADS) tile64_syrk_trsm_kernel(const tp_kar
         if (more) store(nxt, v);
         __syncthreads();
     }
-#endif
     // ---- R_jJ = R_jj^-T A_jJ: chunk c = rows 16c..16c+15 of R_jj^-1 (A half, from memory) and of the tile (B half, wave c's registers)
     d4 res[4];
 #pragma unroll
@@ -950,7 +926,7 @@ size_t tp_tiled_prefix_bytes(int k, long long panel_rows, int n_L, int* nblk_out
 }
 
 // the shared block Grams and block-window sums of a run, once per run
-hipError_t tp_tiled_prefix_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream) {
+static hipError_t tp_tiled_prefix_launch(const tp_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream) {
     const int NS = ws.NS;
     const bool conj = a.strategy == 0;
     const bool lean = (a.panel_off32 & (a.row_idx ? 1 : 2)) && (!conj || (a.hf_off32 & (a.hf_row_idx ? 1 : 2)));
@@ -978,10 +954,10 @@ hipError_t tp_tiled_gram_launch(const tp_kargs_t& a_in, const tp_tiled_ws_t& ws,
         hipError_t e = tp_tiled_prefix_launch(a, ws, stream);
         if (e != hipSuccess) return e;
     }
-    // one wavefront per super-tile (posterior_tiled_wave.h) unless TP_TILED_WAVE=0 asks for the 4-wave kernels (A/B runs)
+    // one wavefront per super-tile (posterior_tiled_wave.h) unless tiled_wave = 0 asks for the 4-wave kernels (the tests' reference)
     const bool use_wave = a.opts.tiled_wave != 0;
     // shared intraday sums of this sub-batch (tangency_api.cpp plans them; the default one-wave kernels only)
-    const bool hfs = conj && a_in.hf_winsum != nullptr && use_wave && a_in.opts.tiled_wave != 2;
+    const bool hfs = conj && a_in.hf_winsum != nullptr && use_wave;
     if (!hfs) a.hf_winsum = nullptr;
     if (hfs) {
         const long long ntile = (long long)NS * (NS + 1) / 2;
@@ -998,17 +974,13 @@ hipError_t tp_tiled_gram_launch(const tp_kargs_t& a_in, const tp_tiled_ws_t& ws,
     }
     if (hfs)
         hipLaunchKernelGGL(tiled_gram_wave_hfs_kernel, xcd_grid(NS * (NS + 1) / 2, G), dim3(64), 0, stream, a, ws);
-    else if (a.opts.tiled_wave == 2) {        // 64 x 128 per wavefront (A/B: option tiled_wave = 2)
-        int np = 0;
-        for (int i = 0; i < NS; ++i) np += (NS - i + 1) / 2;
-        hipLaunchKernelGGL(tiled_gram_wave_pair_kernel, xcd_grid(np, G), dim3(64), 0, stream, a, ws, np);
-    } else if (use_wave && !conj)             // Jeffreys: the rank-one term J = T - t t'/N inside the Gram kernel
+    else if (use_wave && !conj)               // Jeffreys: the rank-one term J = T - t t'/N inside the Gram kernel
         hipLaunchKernelGGL(tiled_gram_wave_rank1_kernel, xcd_grid(NS * (NS + 1) / 2, G), dim3(64), 0, stream, a, ws);
     else if (use_wave)
         hipLaunchKernelGGL(tiled_gram_wave_kernel, xcd_grid(NS * (NS + 1) / 2, G), dim3(64), 0, stream, a, ws);
     else if (lean) hipLaunchKernelGGL(tiled_gram_lean_kernel, xcd_grid(NS * (NS + 1) / 2, G), dim3(NTHREADS), 0, stream, a, ws);
     else hipLaunchKernelGGL(tile64_kernel<MODE_GRAM>, xcd_grid(NS * (NS + 1) / 2, G), dim3(NTHREADS), 0, stream, a, ws, 0);
-    if (!conj && !(use_wave && a.opts.tiled_wave != 2)) hipLaunchKernelGGL(tiled_rank1_kernel, xcd_grid(NS * (NS + 1) / 2, G), dim3(NTHREADS), 0, stream, a, ws);
+    if (!conj && !use_wave) hipLaunchKernelGGL(tiled_rank1_kernel, xcd_grid(NS * (NS + 1) / 2, G), dim3(NTHREADS), 0, stream, a, ws);
     hipLaunchKernelGGL(tiled_clear_kernel, dim3(G), dim3(NTHREADS), 0, stream, a, ws);
     if (a.out_post != nullptr && a.w_first < a.post_w0 + a.post_count && a.w_first + G > a.post_w0)
         hipLaunchKernelGGL(tiled_post_kernel, xcd_grid(NS * (NS + 1) / 2, G), dim3(NTHREADS), 0, stream, a, ws);

@@ -34,8 +34,7 @@ __device__ __forceinline__ void tw_settle8(d4& c0, d4& c1, d4& c2, d4& c3, d4& c
 // One pass over rows: acc(a, b) += rows[:, A group a]' rows[:, B group b], a, b = 0..3, 4 rows per k-step.
 //  HF:  intraday rows sqrt(s) (y - ybar), border column c sqrt(s) z_r (ref:317-333, 489)
 //  !HF: daily rows minus the risk-free adjustment, border column 1 (ref:57, 180, 222)
-//  NB: 16-column B groups per k-step: 4 = one 64 x 64 super-tile, 8 = two super-tiles side by side (64 x 128, the pair
-//  kernel: the A operands are loaded once for both)
+//  NB: 16-column B groups per k-step: 4 = one 64 x 64 super-tile
 //  CS: also keep the column sums of the staged values (this lane's rows only) in cs[] - the Jeffreys rank-one term fused
 //  into the Gram kernel needs t = X'1 for the rows AND the columns of the super-tile (gram64_wave_body, RANK1)
 //  SUBR (!HF): subtract the reference row yb[] first (shared intraday sums: every row relative to ONE row of the panel, so
@@ -128,19 +127,15 @@ __device__ __forceinline__ void tw_gram_pass(const TRows& src, const int (&co)[4
     });
 }
 
-// PAIR: the wave owns super-tiles (SI, SJ) AND (SI, SJ + 1): 32 tiles = all 256 AGPRs, one wave per SIMD, 12 operand loads
-// and 32 MFMAs per k-step (a diagonal pair: 8 loads, 26 MFMAs) instead of 2 x (8 loads, 16 MFMAs)
-// RANK1 (Jeffreys, 64 x 64 form): J = T - t t'/N (+ the optional shift d I + e 1 1') applied to the super-tile while it is
+// RANK1 (Jeffreys): J = T - t t'/N (+ the optional shift d I + e 1 1') applied to the super-tile while it is
 // still in registers, instead of by tiled_rank1_kernel's read-modify-write pass over the whole arena (34 % of a Jeffreys
 // run at k = 500: 9.1 ms per 8,192 windows, its column of t read with a 4 KB stride).  t for the rows of SI and the columns
 // of SJ: the border column of the shared table slots of super-tiles (SI, NS-1) and (SJ, NS-1) (four lanes hold it) plus
 // the column sums of the rows this wave stages itself, put together in 1 KB of LDS.
-template <bool DIAG, bool EDGE, bool PAIR = false, bool RANK1 = false>
+template <bool DIAG, bool EDGE, bool RANK1 = false>
 __device__ __forceinline__ void gram64_wave_body(const tp_kargs_t& A, const tp_tiled_ws_t& ws, const long long wl, const int SI,
                                                  const int SJ, double* tv_lds = nullptr) {
-    static_assert(!(PAIR && RANK1), "the fused rank-one term is built for the 64 x 64 form");
-    constexpr int NB = PAIR ? 8 : 4;
-    constexpr int NC = 4 + NB;
+    constexpr int NB = 4, NC = 8;
     const int lane = threadIdx.x;
     const int fr = lane & 15, fq = lane >> 4;
     const long long w = A.w_first + wl;
@@ -158,8 +153,8 @@ __device__ __forceinline__ void gram64_wave_body(const tp_kargs_t& A, const tp_t
     bool cval[NC], cbord[NC];
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
-        // operand groups 0..3: the A groups (super-tile column SI); 4..: the B groups of SJ (and SJ + 1).  A diagonal
-        // super-tile uses the first NB entries only: SI's groups, then (pair) those of SI + 1
+        // operand groups 0..3: the A groups (super-tile column SI); 4..7: the B groups of SJ.  A diagonal super-tile uses
+        // the first NB entries only: SI's groups
         const int st = DIAG ? SI + (i >> 2) : (i < 4 ? SI : SJ + ((i - 4) >> 2));
         const int gc = 64 * st + fr + 16 * (i & 3);
         cval[i] = !EDGE || gc < k;
@@ -266,7 +261,6 @@ __device__ __forceinline__ void gram64_wave_body(const tp_kargs_t& A, const tp_t
 #pragma unroll
         for (int b = 0; b < NB; ++b) tj[b] = tv_lds[64 + 16 * b + fr];
     }
-    // (the super-tiles of a pair are neighbours in the row-major numbering of the triangle: slot of (SI, SJ + 1) = slot + 1)
     const d2* q = shared ? (const d2*)(A.winsum + (((long long)li * A.prefix_nblk + tb0) * ntile + pair_index(SI, SJ, ws.NS)) * (SB * SB)) + lane
                          : nullptr;
     static_for<0, 4>([&](auto ac) __attribute__((always_inline)) {
@@ -277,7 +271,7 @@ __device__ __forceinline__ void gram64_wave_body(const tp_kargs_t& A, const tp_t
 #pragma unroll
             for (int b = 0; b < NB; ++b)
 #pragma unroll
-                for (int h = 0; h < 2; ++h) v2[b][h] = q[(b >> 2) * (SB * SB / 2) + a * 512 + ((b & 3) * 2 + h) * 64];
+                for (int h = 0; h < 2; ++h) v2[b][h] = q[a * 512 + (b * 2 + h) * 64];
         }
         static_for<0, NB>([&](auto bc) __attribute__((always_inline)) {
             constexpr int b = decltype(bc)::value;
@@ -648,50 +642,16 @@ __global__ void __launch_bounds__(64, 2) tiled_gram_wave_rank1_kernel(const tp_k
     const bool edge = !(64 * SJ + 63 < A.k);
     __shared__ double tv[128];
     if (SI == SJ) {
-        if (edge) gram64_wave_body<true, true, false, true>(A, ws, wl, SI, SJ, tv);
-        else gram64_wave_body<true, false, false, true>(A, ws, wl, SI, SJ, tv);
+        if (edge) gram64_wave_body<true, true, true>(A, ws, wl, SI, SJ, tv);
+        else gram64_wave_body<true, false, true>(A, ws, wl, SI, SJ, tv);
     } else {
-        if (edge) gram64_wave_body<false, true, false, true>(A, ws, wl, SI, SJ, tv);
-        else gram64_wave_body<false, false, false, true>(A, ws, wl, SI, SJ, tv);
+        if (edge) gram64_wave_body<false, true, true>(A, ws, wl, SI, SJ, tv);
+        else gram64_wave_body<false, false, true>(A, ws, wl, SI, SJ, tv);
     }
 }
 
-// 64 x 128 per wavefront: super-tiles (I, J) and (I, J + 1) of a window, J = I, I + 2, ... (a single one at the end of an odd
-// row).  Half the waves, each with all 256 AGPRs, ONE per SIMD: the 70 % matrix-pipe utilisation of the 64 x 64 form comes
-// with two waves per SIMD whose vector / load phases do not hide under each other's MFMAs (MI355X: a wave streaming fp64
-// MFMAs leaves its SIMD partner one vector instruction per MFMA); here a k-step is 32 MFMAs (2,048 cycles) for 12 loads.
-__device__ __forceinline__ int tw_pair_count(int NS) { int n = 0; for (int i = 0; i < NS; ++i) n += (NS - i + 1) / 2; return n; }
-__device__ __forceinline__ void tw_pair_decode(int p, int NS, int& SI, int& SJ, bool& two) {
-    int i = 0, rem = p;
-    while (rem >= (NS - i + 1) / 2) { rem -= (NS - i + 1) / 2; ++i; }
-    SI = i; SJ = i + 2 * rem; two = SJ + 1 < NS;
-}
-__global__ void __launch_bounds__(64, 1) tiled_gram_wave_pair_kernel(const tp_kargs_t A, const tp_tiled_ws_t ws, const int NP) {
-    long long wl;
-    int tile, SI, SJ;
-    bool two;
-    if (!xcd_window_tile(NP, A.w_count, wl, tile)) return;
-    tw_pair_decode(tile, ws.NS, SI, SJ, two);
-    const int last = SJ + (two ? 1 : 0);
-    const bool edge = !(64 * last + 63 < A.k);
-    if (two) {
-        if (SI == SJ) {
-            if (edge) gram64_wave_body<true, true, true>(A, ws, wl, SI, SJ);
-            else gram64_wave_body<true, false, true>(A, ws, wl, SI, SJ);
-        } else {
-            if (edge) gram64_wave_body<false, true, true>(A, ws, wl, SI, SJ);
-            else gram64_wave_body<false, false, true>(A, ws, wl, SI, SJ);
-        }
-    } else {
-        if (SI == SJ) {
-            if (edge) gram64_wave_body<true, true>(A, ws, wl, SI, SJ);
-            else gram64_wave_body<true, false>(A, ws, wl, SI, SJ);
-        } else {
-            if (edge) gram64_wave_body<false, true>(A, ws, wl, SI, SJ);
-            else gram64_wave_body<false, false>(A, ws, wl, SI, SJ);
-        }
-    }
-}
+// Measured and NOT kept (round 3): 64 x 128 per wavefront - super-tiles (I, J) and (I, J + 1) by one wave with all 256
+// AGPRs, one wave per SIMD, a k-step of 32 MFMAs for 12 loads.  Slower than two 64 x 64 waves per SIMD.
 
 // Measured and NOT kept (round 2): the factorisation's SYRK and TRSM super-tiles in the same one-wave form (eight loads
 // and 16 MFMAs per k-step, no staging at all).  They read the ARENA - 22 GB per 4,096 windows at k = 500, from HBM, each
@@ -718,16 +678,10 @@ __device__ __forceinline__ void tw_mfma_agpr_neg(d4& c, double a, double b) {
 // UPDATE: the block first takes its left-looking update A_jj -= sum_{q<j} R_qj' R_qj here (rows 0 .. 64 j - 1 of the arena,
 // columns of super-tile j: four operand loads and ten MFMAs per 4-row k-step, the tiles on and above the diagonal only)
 // instead of in a launch of its own (tile64_kernel<MODE_SYRK_DIAG>: 201 us per block step at k = 500, 8 % of the run).
-// waves per SIMD the register allocator is asked to keep.  Two (round 3, A/B build -DTP_DIAG_OCC=2: 128 + 128 registers, 51
-// spilled) measured 16.36-16.53 ms against 16.28-16.30 ms per 4,096 windows at k = 500 and +-0 at k = 1000: not adopted
-#ifndef TP_DIAG_OCC
-#define TP_DIAG_OCC 1
-#endif
-#ifndef TP_DIAG_DEPTH
-#define TP_DIAG_DEPTH 8
-#endif
+// One wave per SIMD for the register allocator.  Two (round 3: 128 + 128 registers, 51 spilled) measured 16.36-16.53 ms
+// against 16.28-16.30 ms per 4,096 windows at k = 500 and +-0 at k = 1000: not adopted
 template <bool UPDATE>
-__global__ void __launch_bounds__(64, TP_DIAG_OCC) tiled_diag_wave_kernel(const tp_kargs_t A, const tp_tiled_ws_t ws, const int j) {
+__global__ void __launch_bounds__(64, 1) tiled_diag_wave_kernel(const tp_kargs_t A, const tp_tiled_ws_t ws, const int j) {
     constexpr int MLD = 17;
     __shared__ __attribute__((aligned(16))) double lds[256 + 256 + 16 * MLD];          // diagonal tile | identity | M_a
     double* DG = lds;
@@ -782,11 +736,11 @@ __global__ void __launch_bounds__(64, TP_DIAG_OCC) tiled_diag_wave_kernel(const 
                 });
             });
         };
-        // TP_DIAG_DEPTH k-steps of operand loads in flight (nks = 16 j is a multiple of it: no remainder code).  Eight
+        // D k-steps of operand loads in flight (nks = 16 j is a multiple of it: no remainder code).  Eight
         // against the three of round 2 measured +-0 (k = 500, 8,192 windows: 31.7 / 18.3 ms conjugate / Jeffreys either
         // way): the kernel is bound by its serial work (ten MFMAs per k-step, then 64 pivots), not by the latency of
         // the arena rows.
-        constexpr int D = TP_DIAG_DEPTH;
+        constexpr int D = 8;
         static_assert(16 % D == 0, "the update loop runs whole groups of D k-steps");
         double v[D][4];
         static_for<0, D>([&](auto dc) __attribute__((always_inline)) { load(v[decltype(dc)::value], decltype(dc)::value); });

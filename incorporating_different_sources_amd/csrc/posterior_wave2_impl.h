@@ -35,13 +35,8 @@ namespace {
 // Which instantiations factorise in the data-flow form.  At 11 and 12 tiles per side (39 tiles per wave, seven of them in
 // VGPRs) its extra live values made the register allocator move an accumulator tile between the two register files INSIDE
 // the row loop of the general-layout conjugate kernel - a read of an MFMA result two instructions after its issue, which
-// tools/check_mfma_hazards.py rejects - so that one keeps the barrier form.  TP_WAVE2_DATAFLOW = 0 / 1 forces one form
-// everywhere (A/B builds).
-#ifdef TP_WAVE2_DATAFLOW
-constexpr bool w2_dataflow(int, bool, int) { return TP_WAVE2_DATAFLOW != 0; }
-#else
+// tools/check_mfma_hazards.py rejects - so that one keeps the barrier form.
 constexpr bool w2_dataflow(int nt, bool lean, int mode) { return !((nt == 11 || nt == 12) && !lean && mode == 0); }
-#endif
 
 template <int NT_, int NWV_, bool DF_>
 struct W2Cfg {
@@ -779,12 +774,9 @@ __device__ __forceinline__ void w2_body(const tp_kargs_t& A, double* lds) {
     TP_MARK(7);
 }
 
-// waves per SIMD the register allocator is asked to keep (TP_WAVE2_OCC: A/B builds; 2 needs <= 14 tiles per wave)
-#ifndef TP_WAVE2_OCC
-#define TP_WAVE2_OCC 1
-#endif
+// one wave per SIMD for the register allocator (two would need <= 14 tiles per wave)
 template <int NT, int NWV, bool LEAN, int MODE>
-__global__ void __launch_bounds__(64 * NWV, TP_WAVE2_OCC) posterior_wave2_kernel(const tp_kargs_t A) {
+__global__ void __launch_bounds__(64 * NWV, 1) posterior_wave2_kernel(const tp_kargs_t A) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     wave_dispatch<NWV>(wv, [&](auto wc) __attribute__((always_inline)) {

@@ -939,11 +939,7 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
 // Windows (= waves) per SIMD the register allocator is asked to keep: the accumulators take 8 registers per tile, the
 // row pipeline about 100; two or more waves per SIMD also double the vector issue rate (one wave alone issues an fp64
 // vector instruction every ~9 cycles, two get one every ~4.75: tools/coexec_probe.hip).
-#ifdef TP_WAVE_OCC
-constexpr int wave_occupancy(int) { return TP_WAVE_OCC; }
-#else
 constexpr int wave_occupancy(int nt) { return nt <= 3 ? 4 : nt <= 5 ? 2 : 1; }
-#endif
 
 template <int NT, bool LEAN, int MODE>
 __global__ void __launch_bounds__(64, wave_occupancy(NT)) posterior_wave_kernel(const tp_kargs_t A) {

@@ -173,15 +173,6 @@ tp_kargs_t tp_host::make_kargs(tp_batch_t b) {
     return a;
 }
 
-static int ensure_lane_streams(tp_handle_t h, int lanes) {
-    HIP_TRY(h, h->lane_start.create(hipEventDisableTiming));
-    for (int l = 0; l < lanes; ++l) {
-        HIP_TRY(h, h->lane_stream[l].create());
-        HIP_TRY(h, h->lane_done[l].create(hipEventDisableTiming));
-    }
-    return TP_OK;
-}
-
 Span& tp_host::timed_span(tp_handle_t h) {
     return h->in_region && h->ring_used < (int)h->ring.size() ? h->ring[(size_t)h->ring_used] : h->kernel_span;
 }
@@ -205,47 +196,27 @@ int tp_host::launch(tp_batch_t b, const tp_kargs_t& a, int64_t count, bool timed
     }
     // large-k path: sub-batches of in-flight windows through the tiled pipeline
     if (a.dbg_S1 != nullptr) return fail(h, TP_ERR_UNSUPPORTED, "matrix read-back is not available on the large-k path");
-    tp_tiled_ws_t ws[TP_MAX_LANES];
-    int lanes = 1;
-    int rc = ensure_tiled_ws(b, ws, &lanes);
+    tp_tiled_ws_t ws;
+    int rc = ensure_tiled_ws(b, &ws);
     if (rc != TP_OK) return rc;
-    if (lanes > 1) { rc = ensure_lane_streams(h, lanes); if (rc != TP_OK) return rc; }
     if (span) HIP_TRY(h, span->begin(h->stream));
-    tp_kargs_t whole = a;
-    if (lanes > 1 && b->prefix_per_sub) { rc = plan_daily_tables(b, whole, true); if (rc != TP_OK) return rc; }
-    if (lanes > 1) {
-        // the shared sums once, on the kernel stream; then every lane's stream starts behind them
-        hipError_t e = tp_tiled_prefix_launch(whole, ws[0], h->stream);
-        if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled pipeline launch failed: %s", hipGetErrorString(e));
-        HIP_TRY(h, hipEventRecord(h->lane_start, h->stream));
-        for (int l = 0; l < lanes; ++l) HIP_TRY(h, hipStreamWaitEvent(h->lane_stream[l], h->lane_start, 0));
-    }
-    int64_t sb = 0;
-    for (int64_t w0 = 0; w0 < count; w0 += b->tiled_capacity, ++sb) {
-        tp_kargs_t sub = lanes > 1 ? whole : a;
+    for (int64_t w0 = 0; w0 < count; w0 += b->tiled_capacity) {
+        tp_kargs_t sub = a;
         sub.w_first = a.w_first + w0;
         sub.w_count = (count - w0 < b->tiled_capacity) ? (count - w0) : b->tiled_capacity;
-        const int l = (int)(sb % lanes);
-        if (b->prefix_per_sub && lanes == 1) {
-            rc = plan_daily_tables(b, sub, false);
+        if (b->prefix_per_sub) {
+            rc = plan_daily_tables(b, sub);
             if (rc != TP_OK) return rc;
         }
-        if (b->hf_B > 0 && lanes == 1 && a.strategy == TP_STRATEGY_CONJUGATE) {
+        if (b->hf_B > 0 && a.strategy == TP_STRATEGY_CONJUGATE) {
             rc = plan_hf_tables(b, sub);
             if (rc != TP_OK) return rc;
         }
         // (per-sub-batch tables: every sub-batch builds its own; a whole-panel table: the first one builds it)
-        hipError_t e = tp_tiled_launch(sub, ws[l], lanes > 1 ? h->lane_stream[l] : h->stream,
-                                       lanes == 1 && (b->prefix_per_sub || w0 == 0));
+        hipError_t e = tp_tiled_launch(sub, ws, h->stream, b->prefix_per_sub || w0 == 0);
         if (e != hipSuccess) return fail(h, TP_ERR_HIP, "tiled pipeline launch failed: %s", hipGetErrorString(e));
     }
-    if (lanes > 1) {
-        for (int l = 0; l < lanes; ++l) {
-            HIP_TRY(h, hipEventRecord(h->lane_done[l], h->lane_stream[l]));
-            HIP_TRY(h, hipStreamWaitEvent(h->stream, h->lane_done[l], 0));
-        }
-    }
-    h->last_launch = tp_launch_info_t{(int)(count < b->tiled_capacity ? count : b->tiled_capacity), 256, 36864, ws[0].NS * 4};
+    h->last_launch = tp_launch_info_t{(int)(count < b->tiled_capacity ? count : b->tiled_capacity), 256, 36864, ws.NS * 4};
     return span ? timed_done(h, *span) : TP_OK;
 }
 
@@ -281,7 +252,7 @@ int destroy_batch(tp_batch_t b, bool device_calls) {
         // ranks may already be waiting in: issue it before the buffers go away - dropping it would hang them.
         // (not at process exit: the peers may be gone, and a collective nobody answers would hang the exit)
         if (h->deferred == b && !g_exiting.load()) (void)flush_gather(h);
-        (void)hipStreamSynchronize(h->stream);      // (the lanes of the large-k path have joined the kernel stream)
+        (void)hipStreamSynchronize(h->stream);      // every launch of the batch went onto the kernel stream
         if (h->comm_stream) (void)hipStreamSynchronize(h->comm_stream);   // a gather may still read the results
         if (b->upload_done) (void)hipEventSynchronize(b->upload_done);    // copies may still write the inputs
     }
@@ -351,11 +322,11 @@ int tp_create(int device_id, tp_handle_t* out) {
     // the environment is read here and nowhere else (see tp_handle_s::opts)
     h->opts.wave_kernel = env_int("TP_WAVE_KERNEL", -1);
     h->opts.tiled_wave = env_int("TP_TILED_WAVE", -1);
+    if (h->opts.tiled_wave < -1 || h->opts.tiled_wave > 1) h->opts.tiled_wave = -1;   // outside -1 / 0 / 1: automatic
     h->opts.tiled_fuse = env_int("TP_TILED_FUSE", -1);
     h->no_shared_gram = getenv("TP_NO_SHARED_GRAM") != nullptr ? 1 : 0;
     h->tiled_arena_gib = env_int("TP_TILED_ARENA_GIB", 0);
     h->tiled_arena_mib = env_int("TP_TILED_ARENA_MIB", 0);
-    h->tiled_lanes = env_int("TP_TILED_LANES", 0);
     h->phase_limit = env_int("TP_PHASE_LIMIT", 0);
     {
         std::lock_guard<std::mutex> lk(g_registry_mutex);
@@ -370,12 +341,14 @@ int tp_set_option(tp_handle_t h, const char* name, int value) {
     if (!h || !name) return TP_ERR_INVALID;
     const std::string n(name);
     if (n == "wave_kernel") h->opts.wave_kernel = value;
-    else if (n == "tiled_wave") h->opts.tiled_wave = value;
+    else if (n == "tiled_wave") {
+        if (value < -1 || value > 1) return fail(h, TP_ERR_INVALID, "tp_set_option: tiled_wave=%d is not -1, 0 or 1", value);
+        h->opts.tiled_wave = value;
+    }
     else if (n == "tiled_fuse") h->opts.tiled_fuse = value;
     else if (n == "no_shared_gram") h->no_shared_gram = value != 0;
     else if (n == "tiled_arena_gib") h->tiled_arena_gib = value;
     else if (n == "tiled_arena_mib") h->tiled_arena_mib = value;
-    else if (n == "tiled_lanes") h->tiled_lanes = value;
     else if (n == "hf_share_min_blocks") h->hf_share_min_blocks = value;
     else if (n == "sweep_chunk_windows") {
         if (value < 0) return fail(h, TP_ERR_INVALID, "tp_set_option: sweep_chunk_windows=%d < 0", value);

@@ -16,7 +16,6 @@
 #include "posterior_size_sweep.h"
 #include "posterior_solve_sweep_tiled.h"
 
-#define TP_MAX_LANES 4
 #define TP_REGION_MAX_STEPS 512
 
 // Members are destroyed in reverse order of declaration: the kernel stream is declared before every other stream and
@@ -47,12 +46,8 @@ struct tp_handle_s {
     int no_shared_gram = 0;         // TP_NO_SHARED_GRAM / "no_shared_gram"
     int hf_share_min_blocks = 6;    // "hf_share_min_blocks": whole intraday blocks per window from which the large-k path shares them
     int tiled_arena_gib = 0;        // TP_TILED_ARENA_GIB / "tiled_arena_gib" (0: default)
-    int tiled_arena_mib = 0;        // TP_TILED_ARENA_MIB / "tiled_arena_mib": a sub-GiB arena per lane (depth-first sub-batches)
-    int tiled_lanes = 0;            // TP_TILED_LANES / "tiled_lanes": sub-batches in flight on streams of their own (0: default)
+    int tiled_arena_mib = 0;        // TP_TILED_ARENA_MIB / "tiled_arena_mib": a sub-GiB arena (tests: many sub-batches from few windows)
     int sweep_chunk_windows = 0;    // "sweep_chunk_windows": windows per sub-range of tp_batch_solve_sweep / _prior_sweep / _size_sweep (0: automatic)
-    Stream lane_stream[TP_MAX_LANES];
-    Event lane_done[TP_MAX_LANES];
-    Event lane_start;
     int phase_limit = 0;            // TP_PHASE_LIMIT (diagnostic builds only)
     std::vector<tp_batch_t> batches;   // live batches of this handle (destroyed with it if the caller forgot them)
     // per-step kernel times inside a tp_region_begin / tp_region_end bracket: every timed launch of the region records
@@ -106,8 +101,7 @@ struct tp_batch_s {
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)
     int winsum_L[4] = {0, 0, 0, 0};                           // register-tile path: the whole-block counts of the windows
-    DevBuf t_arena[TP_MAX_LANES], t_rinv[TP_MAX_LANES], t_ybar[TP_MAX_LANES], t_zc[TP_MAX_LANES], t_scal[TP_MAX_LANES],
-        t_flags[TP_MAX_LANES];                                // large-k path workspace, one per lane
+    DevBuf t_arena, t_rinv, t_ybar, t_zc, t_scal, t_flags;    // large-k path workspace
     // large-k path, conjugate: shared intraday sums (posterior_tiled_wave.h).  Decided at upload (plan_shared_hf): the
     // windows' intraday rows are contiguous, of one length, and advance by hf_B rows; the tables are per sub-batch
     // large-k path: the daily tables cover the blocks of the sub-batch in flight (plan_daily_tables); host copies of
@@ -119,9 +113,8 @@ struct tp_batch_s {
     int hf_B = 0, hf_L = 0;                                   // rows per block (0 = not shared), whole blocks per window
     long long hf_phase = 0;                                   // blocks start at rows = hf_phase (mod hf_B)
     DevBuf hf_prefix;                                         // block Grams + block-window sums of the sub-batch in flight
-    DevBuf t_part[TP_MAX_LANES];                              // pieces of S0 w0 per (window, row block, column block)
-    int64_t tiled_capacity = 0;                               // windows in flight per sub-batch (per lane)
-    int tiled_lanes = 0;                                      // lanes the workspace was sized for
+    DevBuf t_part;                                            // pieces of S0 w0 per (window, row block, column block)
+    int64_t tiled_capacity = 0;                               // windows in flight per sub-batch
     bool uploaded = false;
     bool gathered = false;
     bool rhs_valid = false;                          // out_rhs was allocated before the last run (tp_batch_keep_rhs)
@@ -177,13 +170,13 @@ int end_launches(tp_batch_t b);
 // tangency_plan.cpp: input validation, upload planning, large-k launch planning
 int validate_pairs(tp_handle_t h, const char* what, const int32_t* num, const int32_t* den, int64_t n, int64_t price_rows);
 int validate_inputs(tp_handle_t h, const tp_params_t& p, int64_t W, const tp_inputs_t* in_raw);
-// entries a tiled arena of `per_entry` bytes each may hold: the budget is 32 GiB (shared among `lanes`), never more than a third
+// entries a tiled arena of `per_entry` bytes each may hold: the budget is 32 GiB, never more than a third
 // of what is free (`held` bytes, about to be reallocated, count as free), tiled_arena_gib / _mib override it; 1 .. 65,535
-int64_t tiled_arena_entries(tp_handle_t h, size_t per_entry, int lanes = 1, size_t held = 0);
+int64_t tiled_arena_entries(tp_handle_t h, size_t per_entry, size_t held = 0);
 // `entries`: arena slots a caller other than a run could fill at once (the tiled prior sweep: (window, prior) pairs); the
 // workspace holds up to max(W, entries) of them where the arena budget allows
-int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int* lanes_out, int64_t entries = 0);
-int plan_daily_tables(tp_batch_t b, tp_kargs_t& sub, bool whole);
+int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int64_t entries = 0);
+int plan_daily_tables(tp_batch_t b, tp_kargs_t& sub);
 int plan_hf_tables(tp_batch_t b, tp_kargs_t& sub);
 int plan_shared_gram(tp_batch_t b, const tp_inputs_t* in);
 void plan_shared_hf(tp_batch_t b, const tp_inputs_t* in);

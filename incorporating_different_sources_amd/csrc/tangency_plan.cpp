@@ -83,9 +83,9 @@ int validate_inputs(tp_handle_t h, const tp_params_t& p, int64_t W, const tp_inp
 }
 
 // The arena budget of the large-k path, in entries of `per_entry` bytes: 32 GiB of the 288 (fewer, larger launches: measured
-// +2-4 % over 6 GiB at k = 500) shared among `lanes`, never more than a third of what is free (`held`: bytes the caller is
-// about to reallocate, counted as free); tiled_arena_gib overrides it, tiled_arena_mib sets a lane's own arena.
-int64_t tiled_arena_entries(tp_handle_t h, size_t per_entry, int lanes, size_t held) {
+// +2-4 % over 6 GiB at k = 500), never more than a third of what is free (`held`: bytes the caller is about to reallocate,
+// counted as free); tiled_arena_gib / tiled_arena_mib override it.
+int64_t tiled_arena_entries(tp_handle_t h, size_t per_entry, size_t held) {
     unsigned long long gib = 32;
     { size_t free_b = 0, total_b = 0;
       if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
@@ -93,7 +93,7 @@ int64_t tiled_arena_entries(tp_handle_t h, size_t per_entry, int lanes, size_t h
           if ((free_b >> 30) / 3 < gib) gib = (free_b >> 30) / 3 > 1 ? (free_b >> 30) / 3 : 1;
       } }
     if (h->tiled_arena_gib >= 1 && h->tiled_arena_gib <= 200) gib = (unsigned long long)h->tiled_arena_gib;
-    unsigned long long arena_bytes = (gib << 30) / (unsigned long long)lanes;
+    unsigned long long arena_bytes = gib << 30;
     if (h->tiled_arena_mib >= 1 && h->tiled_arena_mib <= 200 * 1024) arena_bytes = (unsigned long long)h->tiled_arena_mib << 20;
     int64_t G = (int64_t)(arena_bytes / per_entry);
     if (G < 1) G = 1;
@@ -101,69 +101,55 @@ int64_t tiled_arena_entries(tp_handle_t h, size_t per_entry, int lanes, size_t h
     return G;
 }
 
-// Workspace of the large-k path.  Default: ONE lane whose arena holds as many in-flight windows as 32 GiB allow (fewer,
-// larger launches).  Depth-first alternative (options tiled_lanes / tiled_arena_mib): several small sub-batches in flight,
-// each on a stream and a workspace of its own, sized so that all arenas together stay inside the 256 MiB Infinity Cache
-// - the left-looking update then re-reads a window's block rows from cache instead of streaming them from HBM.
-int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int* lanes_out, int64_t entries) {
+// Workspace of the large-k path: ONE arena that holds as many in-flight windows as 32 GiB allow (fewer, larger launches);
+// a batch of more windows runs as sub-batches, one after the other on the kernel stream.  (Several small sub-batches in
+// flight on streams of their own, their arenas inside the 256 MiB Infinity Cache, measured slower everywhere: DESIGN.md 5.)
+int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int64_t entries) {
     tp_handle_t h = b->h;
     int KP, NS, NSB;
     tp_tiled_geometry(b->p.k, &KP, &NS, &NSB);
     const size_t per_window = sizeof(double) * ((size_t)KP * KP + (size_t)NSB * 64 * 64 + KP + (size_t)b->p.m + 8) + 4;
-    int lanes = h->tiled_lanes >= 1 ? (h->tiled_lanes > TP_MAX_LANES ? TP_MAX_LANES : h->tiled_lanes) : 1;
-    int64_t G = tiled_arena_entries(h, per_window, lanes);
+    int64_t G = tiled_arena_entries(h, per_window);
     if (G > (entries > b->W ? entries : b->W)) G = entries > b->W ? entries : b->W;
-    if ((int64_t)lanes * G > b->W) lanes = (int)((b->W + G - 1) / G);
-    if (b->tiled_capacity < G || b->tiled_lanes < lanes) {
-        if (b->tiled_capacity > G) G = b->tiled_capacity;
-        for (int l = 0; l < lanes; ++l) {
-            int rc = ensure(h, b->t_arena[l], sizeof(double) * (size_t)G * KP * KP, "large-k arena");
-            if (rc == TP_OK) rc = ensure(h, b->t_rinv[l], sizeof(double) * (size_t)G * NSB * 64 * 64, "large-k inverse diagonal blocks");
-            if (rc == TP_OK) rc = ensure(h, b->t_ybar[l], sizeof(double) * (size_t)G * KP, "large-k column means");
-            if (rc == TP_OK) rc = ensure(h, b->t_zc[l], sizeof(double) * (size_t)G * (b->p.m > 0 ? b->p.m : 1), "large-k intraday scratch");
-            if (rc == TP_OK) rc = ensure(h, b->t_scal[l], sizeof(double) * (size_t)G * 8, "large-k scalars");
-            if (rc == TP_OK) rc = ensure(h, b->t_flags[l], sizeof(int) * (size_t)G, "large-k flags");
-            if (rc != TP_OK) return rc;
-        }
+    if (b->tiled_capacity < G) {
+        int rc = ensure(h, b->t_arena, sizeof(double) * (size_t)G * KP * KP, "large-k arena");
+        if (rc == TP_OK) rc = ensure(h, b->t_rinv, sizeof(double) * (size_t)G * NSB * 64 * 64, "large-k inverse diagonal blocks");
+        if (rc == TP_OK) rc = ensure(h, b->t_ybar, sizeof(double) * (size_t)G * KP, "large-k column means");
+        if (rc == TP_OK) rc = ensure(h, b->t_zc, sizeof(double) * (size_t)G * (b->p.m > 0 ? b->p.m : 1), "large-k intraday scratch");
+        if (rc == TP_OK) rc = ensure(h, b->t_scal, sizeof(double) * (size_t)G * 8, "large-k scalars");
+        if (rc == TP_OK) rc = ensure(h, b->t_flags, sizeof(int) * (size_t)G, "large-k flags");
+        if (rc != TP_OK) return rc;
         b->tiled_capacity = G;
-        b->tiled_lanes = lanes;
     }
-    if (b->hf_B > 0)
-        for (int l = 0; l < lanes; ++l) {
-            int rc = ensure(h, b->t_part[l], sizeof(double) * (size_t)b->tiled_capacity * NS * NS * 64, "large-k prior products");
-            if (rc != TP_OK) return rc;
-        }
-    for (int l = 0; l < lanes; ++l) {
-        ws[l].arena = (double*)b->t_arena[l].p; ws[l].rinv = (double*)b->t_rinv[l].p; ws[l].ybar = (double*)b->t_ybar[l].p;
-        ws[l].zc = (double*)b->t_zc[l].p; ws[l].scal = (double*)b->t_scal[l].p; ws[l].flags = (int*)b->t_flags[l].p;
-        ws[l].part = (double*)b->t_part[l].p;
-        ws[l].KP = KP; ws[l].NS = NS; ws[l].NSB = NSB;
+    if (b->hf_B > 0) {
+        int rc = ensure(h, b->t_part, sizeof(double) * (size_t)b->tiled_capacity * NS * NS * 64, "large-k prior products");
+        if (rc != TP_OK) return rc;
     }
-    *lanes_out = lanes;
+    ws->arena = (double*)b->t_arena.p; ws->rinv = (double*)b->t_rinv.p; ws->ybar = (double*)b->t_ybar.p;
+    ws->zc = (double*)b->t_zc.p; ws->scal = (double*)b->t_scal.p; ws->flags = (int*)b->t_flags.p;
+    ws->part = (double*)b->t_part.p;
+    ws->KP = KP; ws->NS = NS; ws->NSB = NSB;
     return TP_OK;
 }
 
-// Shared daily sums of the large-k path for ONE sub-batch (or, `whole`, for the whole panel: several lanes in flight): the
-// 16-row blocks its windows cover, block Grams first, one table of block-window sums per whole-block count behind them.
-int plan_daily_tables(tp_batch_t b, tp_kargs_t& sub, bool whole) {
+// Shared daily sums of the large-k path for ONE sub-batch: the 16-row blocks its windows cover, block Grams first, one
+// table of block-window sums per whole-block count behind them.
+int plan_daily_tables(tp_batch_t b, tp_kargs_t& sub) {
     tp_handle_t h = b->h;
     sub.prefix = nullptr; sub.winsum = nullptr; sub.prefix_nblk = 0; sub.prefix_blk0 = 0;
     for (int i = 0; i < 4; ++i) sub.winsum_L[i] = 0;
-    long long lo = 0, hi = b->prefix_nblk;
-    if (!whole) {
-        lo = 0x7fffffffffffffffLL; hi = -1;
-        for (int64_t w = sub.w_first; w < sub.w_first + sub.w_count; ++w) {
-            const long long f = b->h_start[(size_t)w], cnt = b->h_n_rows.empty() ? b->p.n_r : b->h_n_rows[(size_t)w];
-            const long long b0 = (f + 15) / 16, b1 = (f + cnt) / 16;
-            if (b1 <= b0) continue;
-            if (b0 < lo) lo = b0;
-            if (b1 > hi) hi = b1;
-        }
-        if (hi <= lo) return TP_OK;
-        if (hi > b->prefix_nblk) hi = b->prefix_nblk;
-        // sharing pays while the windows' rows outnumber the rows of the blocks a few times over
-        if ((double)sub.w_count * b->p.n_r < 3.0 * 16.0 * (double)(hi - lo)) return TP_OK;
+    long long lo = 0x7fffffffffffffffLL, hi = -1;
+    for (int64_t w = sub.w_first; w < sub.w_first + sub.w_count; ++w) {
+        const long long f = b->h_start[(size_t)w], cnt = b->h_n_rows.empty() ? b->p.n_r : b->h_n_rows[(size_t)w];
+        const long long b0 = (f + 15) / 16, b1 = (f + cnt) / 16;
+        if (b1 <= b0) continue;
+        if (b0 < lo) lo = b0;
+        if (b1 > hi) hi = b1;
     }
+    if (hi <= lo) return TP_OK;
+    if (hi > b->prefix_nblk) hi = b->prefix_nblk;
+    // sharing pays while the windows' rows outnumber the rows of the blocks a few times over
+    if ((double)sub.w_count * b->p.n_r < 3.0 * 16.0 * (double)(hi - lo)) return TP_OK;
     const long long nblk = hi - lo;
     int n_L = 0;
     while (n_L < TP_WINSUM_MAX_L && b->winsum_L[n_L] > 0) ++n_L;

@@ -186,7 +186,7 @@ int ensure_sweep_tiled_ws(tp_batch_t b, int R, int64_t entries, tp_tiled_ws_t* w
     int KP, NS, NSB;
     tp_solve_sweep_tiled_geometry(b->p.k, R, &KP, &NS, &NSB);
     const size_t per_entry = sizeof(double) * ((size_t)KP * KP + (size_t)NSB * 64 * 64) + sizeof(int);
-    int64_t G = tiled_arena_entries(h, per_entry, 1, sw.arena.bytes + sw.rinv.bytes + sw.flags.bytes);
+    int64_t G = tiled_arena_entries(h, per_entry, sw.arena.bytes + sw.rinv.bytes + sw.flags.bytes);
     if (G > entries) G = entries;
     int rc = ensure(h, sw.arena, sizeof(double) * (size_t)G * KP * KP, "tp_batch_solve_sweep_tiled: arena");
     if (rc == TP_OK) rc = ensure(h, sw.rinv, sizeof(double) * (size_t)G * NSB * 64 * 64, "tp_batch_solve_sweep_tiled: inverse diagonal blocks");
@@ -358,10 +358,9 @@ int tp_batch_solve_sweep_tiled(tp_batch_t b, int32_t n_shift, const double* shif
     int64_t chunk = 0;
     int rc = solve_sweep_prepare(b, "tp_batch_solve_sweep_tiled", true, n_shift, shift, n_rhs, rhs, default_rhs, &S, &R, &chunk);
     if (rc != TP_OK || chunk == 0) return rc;
-    // the batch's run workspace (lane 0) as a run would size it, for the Gram stage; the sweep's own for the entries
-    tp_tiled_ws_t wsl[TP_MAX_LANES];
-    int lanes = 1;
-    rc = ensure_tiled_ws(b, wsl, &lanes);
+    // the batch's run workspace as a run would size it, for the Gram stage; the sweep's own for the entries
+    tp_tiled_ws_t gws;
+    rc = ensure_tiled_ws(b, &gws);
     if (rc != TP_OK) return rc;
     const int64_t gcap = b->tiled_capacity;
     tp_tiled_ws_t ws;
@@ -387,7 +386,7 @@ int tp_batch_solve_sweep_tiled(tp_batch_t b, int32_t n_shift, const double* shif
     fa.k = b->p.k;
     fa.opts = h->opts;
     return run_sweep(b, chunk, [&](int64_t w0, int64_t n) {
-        const int rcg = tiled_gram_stage(b, "tiled solve sweep Gram", {&a}, wsl[0], gcap, w0, n);
+        const int rcg = tiled_gram_stage(b, "tiled solve sweep Gram", {&a}, gws, gcap, w0, n);
         if (rcg != TP_OK) return rcg;
         return in_groups(n * S, cap, [&](int64_t e0, int64_t ne) {
             sa.wc_first = w0;
@@ -464,16 +463,14 @@ int tp_batch_prior_sweep_tiled(tp_batch_t b, int32_t n_prior, const double* n0, 
     int64_t chunk = 0;
     int rc = prior_sweep_prepare(b, ps, "tp_batch_prior_sweep_tiled", true, n_prior, n0, w0, &chunk);
     if (rc != TP_OK || chunk == 0) return rc;
-    // the batch's own tiled workspace (lane 0) and the pieces of a C w0 per arena entry
-    tp_tiled_ws_t wsl[TP_MAX_LANES];
-    int lanes = 1;
-    rc = ensure_tiled_ws(b, wsl, &lanes, chunk * P);
+    // the batch's own tiled workspace and the pieces of a C w0 per arena entry
+    tp_tiled_ws_t ws;
+    rc = ensure_tiled_ws(b, &ws, chunk * P);
     if (rc != TP_OK) return rc;
     const int64_t cap = b->tiled_capacity;
-    rc = ensure(h, b->t_part[0], sizeof(double) * (size_t)cap * wsl[0].NS * wsl[0].NS * 64, "tp_batch_prior_sweep_tiled: prior products");
+    rc = ensure(h, b->t_part, sizeof(double) * (size_t)cap * ws.NS * ws.NS * 64, "tp_batch_prior_sweep_tiled: prior products");
     if (rc != TP_OK) return rc;
-    tp_tiled_ws_t ws = wsl[0];
-    ws.part = (double*)b->t_part[0].p;
+    ws.part = (double*)b->t_part.p;
 
     // T and t: the daily rows as a plain run reads them, uncentred and without the prior
     tp_kargs_t ta = neutral_kargs(b);

@@ -32,7 +32,7 @@ def opts(dev):
         dev.set_option(name, int(value))
     yield set_
     for n in names:
-        dev.set_option(n, 0 if n in ("tiled_arena_mib", "tiled_lanes", "no_shared_gram") else -1)
+        dev.set_option(n, 0 if n in ("tiled_arena_mib", "no_shared_gram") else -1)
 
 
 def _kw(inp):
@@ -123,14 +123,13 @@ def test_every_kernel_family_matches_oracle(dev, opts, strategy, k):
     if k <= 239:
         variants = [("wave_kernel", v) for v in (-1, 0, 1, 2)]
     else:
-        variants = [("tiled_wave", -1), ("tiled_wave", 0), ("tiled_fuse", 0), ("tiled_fuse", 1), ("tiled_arena_mib", 1),
-                    ("tiled_lanes", 2)]
+        variants = [("tiled_wave", -1), ("tiled_wave", 0), ("tiled_fuse", 0), ("tiled_fuse", 1), ("tiled_arena_mib", 1)]
     for name, value in variants:
         opts(name, value)
         b, M, _ = run_keep(dev, strategy, inp)
         b.close()
         assert_close(M, ref)
-        opts(name, 0 if name in ("tiled_arena_mib", "tiled_lanes") else -1)
+        opts(name, 0 if name == "tiled_arena_mib" else -1)
 
 
 # ---- 3. layouts -----------------------------------------------------------------------------------------------------

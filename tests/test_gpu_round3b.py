@@ -182,6 +182,31 @@ def test_options_are_per_handle_and_the_environment_is_read_once(native, monkeyp
         dev.close()
 
 
+def test_retired_large_k_options_are_refused_and_leave_the_handle_usable(native):
+    """The depth-first sub-batches ("tiled_lanes") and the 64 x 128 Gram kernel ("tiled_wave" = 2) were measured, not
+    adopted and removed: `set_option` answers both with an error, and the handle that refused them
+    still runs the large-k path - bit-equal to a fresh handle's run of the same batch."""
+    k, N, W = 260, 520, 4
+    inp = synthetic.make_kernel_inputs(k, N, W, seed=13)
+    kw = dict(panel=inp["panel"], start=inp["start"], n_r=inp["n_r"])
+    dev = native.Device(0)
+    try:
+        with pytest.raises(native.TangencyError):
+            dev.set_option("tiled_lanes", 2)
+        with pytest.raises(native.TangencyError):
+            dev.set_option("tiled_wave", 2)
+        wts, status, aux = native.posterior_batch("jeffreys", k, N, 5.0, device=dev, **kw)
+    finally:
+        dev.close()
+    fresh = native.Device(0)
+    try:
+        wts_f, status_f, aux_f = native.posterior_batch("jeffreys", k, N, 5.0, device=fresh, **kw)
+    finally:
+        fresh.close()
+    assert (status == 0).all() and (status_f == 0).all()
+    assert np.array_equal(wts, wts_f) and np.array_equal(aux, aux_f)
+
+
 # ---- the two- / four-wave-per-window kernel (csrc/posterior_wave2_impl.h): 10..15 tiles per side, 144 <= k <= 239 ------
 def _kw(inp, strat):
     kw = dict(panel=inp["panel"], start=inp["start"], n_r=inp["n_r"])
