@@ -183,7 +183,10 @@ int tp_batch_shared_intraday_blocks(tp_batch_t b);
 int tp_host_alloc(void** out, int64_t bytes);
 int tp_host_free(void* p);
 /* Optional right-hand side [W x k] replacing the border column (t for Jeffreys, c S0 w0 + t for the
- * conjugate posterior) in every later tp_batch_run: the weights become (matrix)^-1 rhs / gamma.  NULL
+ * conjugate posterior) in every later tp_batch_run.  Jeffreys: the weights become (matrix)^-1 rhs / gamma.
+ * Conjugate: rhs replaces c S0 w0 + t in w1 = S1^-1 rhs (ref:485-489) and the nu rescale of ref:572-575 still
+ * applies: weights = (n1 + k + 2) w1 / (n1 - w1'S1 w1) / gamma, aux slots 4 and 5 (w1'S1 w1 and the denominator)
+ * and TP_STATUS_BAD_DENOM follow that w1; the plain solve S1^-1 rhs / gamma is tp_batch_solve_sweep's.  NULL
  * restores the default.  Binds the V^-1 1 / V^-1 mu solves of calculate_jorion_portfolio (ref:880-891). */
 int tp_batch_set_rhs(tp_batch_t b, const double* rhs);
 /* Optional per-window shift [W x 2] = (d_w, e_w), Jeffreys strategy only: the matrix that is factorised
@@ -370,7 +373,10 @@ int tp_batch_download(tp_batch_t b, double* weights /* [W x k] */, int32_t* stat
 int tp_batch_download_S1(tp_batch_t b, int64_t w, double* S1 /* [k x k] */); /* posterior scale matrix
                       S1 (ref:358) / Jeffreys J (ref:600) of window w, recomputed by a debug launch */
 /* Read back one window's k x k matrix (symmetric, full storage) and its k-vector, recomputed by a
- * one-window launch; `rhs` may be NULL.  The reference's same-named helper functions bind these. */
+ * one-window launch; `rhs` may be NULL.  The reference's same-named helper functions bind these.
+ * TP_MATRIX_PRIOR centres the intraday rows first (two passes, like DataFrame.cov, ref:317), so every entry of S0
+ * has the relative accuracy of the reference's own; a run forms the same matrix in one pass, equal to rounding in
+ * the norm.  Register-tile path only (k <= 239): TP_ERR_UNSUPPORTED above. */
 #define TP_MATRIX_PRIOR 1      /* S0 (ref:285-333)            and c S0 w0                     */
 #define TP_MATRIX_GRAM 2       /* T  (ref:163-204)            and t (ref:206-245)             */
 #define TP_MATRIX_POSTERIOR 3  /* S1 (ref:358) / J (ref:600)  and c S0 w0 + t (ref:489) / t   */

@@ -531,7 +531,9 @@ class Batch:
         return out
 
     def set_rhs(self, rhs):
-        """Right-hand side [W x k] in place of the border column (None: default t / c S0 w0 + t)."""
+        """Right-hand side [W x k] in place of the border column (None: default t / c S0 w0 + t).  Jeffreys: the weights
+        become (matrix)^-1 rhs / gamma.  Conjugate: rhs replaces c S0 w0 + t in w1 = S1^-1 rhs and the nu rescale of
+        ref:572-575 still applies, weights = (n1 + k + 2) w1 / (n1 - w1'S1 w1) / gamma (`solve_sweep` gives S1^-1 rhs / gamma)."""
         r = _arr(rhs, np.float64, (self.W, self.k), "rhs")
         self.dev._check(lib.tp_batch_set_rhs(self._b, _ptr(r, c_double)))
         return self

@@ -591,8 +591,11 @@ __device__ __forceinline__ void window_body(const tp_kargs_t& A, double* lds, co
         // and t comes out of the SAME MFMAs through a column of ones in the spare column k+1 (phase C applies the
         // rank-one term).  The means pass cost two HBM round trips per window (7 % of its lifetime) and made the
         // intraday panel - the one input that really streams from HBM - be read twice.  Universe sizes with
-        // k+1 a multiple of 16 have no spare column and keep the two-pass form.
-        const bool shifted = kc < 15;
+        // k+1 a multiple of 16 have no spare column and keep the two-pass form.  So does the read-back of S0
+        // (tp_batch_download_matrix, TP_MATRIX_PRIOR) at every size: the shifted form's error is absolute, ~1e-16 of the
+        // terms summed, which an off-diagonal entry that cancels to 1e-6 of its terms shows as 1e-11 relative; centred
+        // first, the entries come out to the relative accuracy of DataFrame.cov's own.
+        const bool shifted = kc < 15 && dbg != 1;
         if (shifted) {
             TP_LANE_CONSTANTS();
             const long long row0 = hs.ridx ? (long long)hs.ridx[0] : hs.first;

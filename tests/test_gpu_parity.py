@@ -309,6 +309,49 @@ def test_log_return_kernel_matches_numpy(native):
         native.default_device().log_returns(P, np.array([rows], np.int32), np.array([0], np.int32))
 
 
+def _log_return_prices(rng, rows, cols):
+    """A price panel with a NaN, a zero and a negative price (and a run of NaNs in the last column)."""
+    P = 100.0 * np.exp(np.cumsum(rng.normal(3e-4, 0.01, size=(rows, cols)), axis=0))
+    P[5, cols - 2] = np.nan; P[100:110, cols - 1] = np.nan; P[300, 3] = 0.0; P[301, 4] = -1.0
+    return P
+
+
+def _assert_log_returns_match_numpy(native, P, num, den):
+    """The assertions of test_log_return_kernel_matches_numpy."""
+    got = native.default_device().log_returns(P, num, den)
+    ref = oracle.log_return_rows(P, num, den)
+    assert got.shape == ref.shape == (len(num), P.shape[1])
+    assert np.array_equal(got == 0.0, ref == 0.0)                 # NaN -> 0 in the same places; exact zeros (p/p)
+    assert np.array_equal(np.abs(got) > 1e300, np.abs(ref) > 1e300)   # +-inf -> +-DBL_MAX in the same places
+    fin = np.abs(ref) < 1e300
+    assert (ref == 0.0).any() and (~fin).any()                    # the NaN, zero and negative prices are among the rows
+    np.testing.assert_allclose(got[fin], ref[fin], rtol=1e-15, atol=1e-18)
+
+
+@pytest.mark.parametrize("cols", [1030, 1029])
+def test_log_return_kernel_over_several_column_blocks(native, cols):
+    """More than one x-block of 512 columns (three; the last one partly outside the panel, its idle lanes leave through the
+    c >= ld guard): 1030 columns take the double2 form, 1029 the scalar form with the odd last column."""
+    rng = np.random.default_rng(43 + cols)
+    rows = 700
+    P = _log_return_prices(rng, rows, cols)
+    num = np.concatenate([np.arange(rows), rng.integers(0, rows, 100)]).astype(np.int32)
+    den = np.concatenate([np.maximum(np.arange(rows) - 1, 0), rng.integers(0, rows, 100)]).astype(np.int32)
+    _assert_log_returns_match_numpy(native, P, num, den)
+
+
+def test_log_return_kernel_strides_over_more_rows_than_its_grid(native):
+    """32,768 + 5 output rows from 700 price rows through repeated num / den: the grid holds 32,768 rows, the last five
+    come from the second trip of the grid-stride loop."""
+    rng = np.random.default_rng(44)
+    rows, cols, n_out = 700, 6, 32768 + 5
+    P = _log_return_prices(rng, rows, cols)
+    num = np.concatenate([np.arange(rows), rng.integers(0, rows, n_out - rows)]).astype(np.int32)
+    den = np.concatenate([np.maximum(np.arange(rows) - 1, 0), rng.integers(0, rows, n_out - rows)]).astype(np.int32)
+    num[-5:], den[-5:] = [301, 300, 6, 5, 699], [300, 299, 5, 4, 0]      # the special prices in the second trip, too
+    _assert_log_returns_match_numpy(native, P, num, den)
+
+
 @pytest.mark.parametrize("k,N", [(10, 60), (100, 250), (300, 400)])
 def test_price_front_end_matches_return_panels(native, k, N):
     """F4: prices + (numerator, denominator) rows into tp_batch_upload give the weights of the same windows
