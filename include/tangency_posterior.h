@@ -253,8 +253,9 @@ int tp_batch_solve_sweep(tp_batch_t b, int32_t n_shift, const double* shift /* [
  * columns; a back substitution of the sweep's own solves them in groups of up to four columns.  Entries go through in groups
  * of the workspace's capacity.  A (window, shift) result depends on the window's rows, its own shift and right-hand sides, k
  * and R only - not on W, S, the positions, the sub-ranges or the size of the workspace.
- * Statuses: TP_STATUS_NOT_PD is the tiled run's rule, a pivot that is not > 0 (no relative floor; a NaN in the window's rows
- * ends here, for every shift of that window); TP_STATUS_NONFINITE: NaN / Inf in any of the R solutions.
+ * Statuses: TP_STATUS_NOT_PD is the tiled run's rule, a pivot that is not > 0 (a NaN in the window's rows ends here, for
+ * every shift of that window), and a pivot no larger than k 2^-52 times its own shifted diagonal element (an exactly repeated
+ * column: rounding noise of either sign); TP_STATUS_NONFINITE: NaN / Inf in any of the R solutions.
  * Streams, timing (one HIP-event pair: one step of tp_region_steps, one kernel_ms over Gram passes, fills, factorisations and
  * solves), the gather hand-over and what the call leaves alone are as for tp_batch_solve_sweep, tp_last_launch included; it
  * waits, on entry, for whatever was queued on the handle's stream.

@@ -137,12 +137,12 @@ __device__ __forceinline__ bool solve_group(const tp_solve_sweep_tiled_kargs_t& 
 
 __global__ void __launch_bounds__(NTHREADS) solve_sweep_tiled_solve_kernel(const tp_solve_sweep_tiled_kargs_t A, const tp_tiled_ws_t ws) {
     extern __shared__ __attribute__((aligned(16))) double sm[];     // wvec [min(R, NG)][KP] | zv [NG][64]
-    __shared__ int anybad;
+    __shared__ int anybad, anylow;
     const long long e = blockIdx.x;
     const int R = A.R;
     double* wvec = sm;
     double* zv = sm + (R < NG ? R : NG) * ws.KP;
-    if (threadIdx.x == 0) anybad = 0;
+    if (threadIdx.x == 0) { anybad = 0; anylow = 0; }
     __syncthreads();
     bool bad = false;
     for (int g0 = 0; g0 < R; g0 += NG) {           // (uniform: every thread reaches every barrier of every group)
@@ -153,10 +153,27 @@ __global__ void __launch_bounds__(NTHREADS) solve_sweep_tiled_solve_kernel(const
         else bad |= solve_group<1>(A, ws, e, g0, wvec, zv);
     }
     if (bad) anybad = 1;
+    // A pivot at the rounding noise of its own diagonal element is not positive definite either: d_i <= k 2^-52 M_ii, the floor
+    // of the LDS prior sweep.  An exactly repeated column has a pivot that is zero in exact arithmetic and of either sign in
+    // floating point; "not > 0" alone let the positive ones through as finite garbage with status OK.  d_i = 1 / (R^-1)_ii^2
+    // from the inverse diagonal blocks the back substitution has just used, M_ii from the kept matrix and the entry's shift.
+    {
+        const int k = A.k;
+        const long long f = A.e_first + e;
+        const double* __restrict__ P = A.post + (f / A.S - A.wc_first) * (long long)k * k;
+        const double sh = A.shift ? A.shift[2 * f] + A.shift[2 * f + 1] : 0.0;
+        const double* rinv = ws.rinv + e * ws.NSB * (long long)(SB * SB);
+        bool low = false;
+        for (int i = threadIdx.x; i < k; i += NTHREADS) {
+            const double ri = rinv[(long long)(i >> 6) * (SB * SB) + (i & 63) * (SB + 1)];
+            if (!(1.0 > (k * 0x1p-52) * (P[(long long)i * k + i] + sh) * (ri * ri))) low = true;     // (a NaN ends here too)
+        }
+        if (low) anylow = 1;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         int st = TP_KSTATUS_OK;
-        if (ws.flags[e]) st = TP_KSTATUS_NOT_PD;
+        if (ws.flags[e] || anylow) st = TP_KSTATUS_NOT_PD;
         else if (anybad) st = TP_KSTATUS_NONFINITE;
         A.status[A.e_first + e] = st;
     }

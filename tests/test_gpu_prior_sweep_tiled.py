@@ -15,13 +15,14 @@ import pytest
 from incorporating_different_sources_amd import _native, synthetic
 from oracle import oracle
 
+from _tiled_sweep_cases import SCALINGS, layouts, make_priors
+
 pytestmark = pytest.mark.gpu
 
 GAMMA = 5.0
 # the bound the project holds such solves to (tests/test_gpu_solve_sweep.py): atol = 1e-10 max(1, |ref|.max()), rtol = 0
 TOL = 1e-10
 SHAPES = [(144, 200), (191, 250), (239, 300), (240, 300), (300, 360)]
-SCALINGS = (0.001, 1, 5, 20)
 
 
 @pytest.fixture(scope="module")
@@ -37,46 +38,6 @@ def assert_close(x, ref, tol=TOL, what=""):
     print(f"{what}: max|sweep - ref| = {err:.3e} (bound {bound:.3e}, |ref|.max() = {np.abs(ref).max():.3e})")
     assert np.isfinite(x).all()
     assert err <= bound, f"{what}: {err:.3e} > {bound:.3e}"
-
-
-def make_priors(rng, W, P, k, N):
-    """(n0 [W x P], w0 [W x P x k]): prior p is scaling SCALINGS[(p // 2) % 4] x (ew, vw)[p % 2], n0 = N scaling U(1, 1.6), vw a
-    normalised, descending log-normal vector, ew 1/k."""
-    n0 = np.empty((W, P))
-    w0 = np.empty((W, P, k))
-    for p in range(P):
-        n0[:, p] = N * SCALINGS[(p // 2) % 4] * rng.uniform(1.0, 1.6, size=W)
-        if p % 2:
-            caps = -np.sort(-rng.lognormal(0.0, 1.0, size=(W, k)), axis=1)
-            w0[:, p, :] = caps / caps.sum(axis=1, keepdims=True)
-        else:
-            w0[:, p, :] = 1.0 / k
-    return n0, w0
-
-
-def layouts(inp, seed, hf_index=False):
-    """(name, panel, upload kwargs, oracle kwargs) of the contiguous layout and of one with row_idx / n_rows / col_idx /
-    rf_adj over a panel with 8 more columns to choose from; `hf_index`: a third one that also has hf_row_idx and a different
-    hf_count per window."""
-    k, W, n_r, m = inp["k"], inp["W"], inp["n_r"], inp["m"]
-    cont = dict(start=inp["start"], hf_panel=inp["hf_panel"], hf_start=inp["hf_start"], w0=inp["w0"], n0=inp["n0"])
-    yield "contiguous", inp["panel"], cont, dict(cont, n_r=n_r, m=m)
-    rng = np.random.default_rng(seed)
-    P = np.concatenate([inp["panel"], rng.normal(0.0, 0.01, size=(inp["panel"].shape[0], 8))], axis=1)
-    H = np.concatenate([inp["hf_panel"], rng.normal(0.0, 0.001, size=(inp["hf_panel"].shape[0], 8))], axis=1)
-    col_idx = np.stack([rng.permutation(P.shape[1])[:k] for _ in range(W)]).astype(np.int32)
-    row_idx = np.stack([inp["start"][w] + np.sort(rng.choice(n_r, n_r, replace=False)) for w in range(W)]).astype(np.int32)
-    n_rows = rng.integers(max(k, n_r - 5), n_r + 1, size=W).astype(np.int32)
-    rf_adj = rng.normal(0, 1e-4, size=(W, n_r))
-    idx = dict(row_idx=row_idx, n_rows=n_rows, col_idx=col_idx, rf_adj=rf_adj, hf_panel=H, hf_start=inp["hf_start"],
-               w0=inp["w0"], n0=inp["n0"])
-    yield "index", P, idx, dict(idx, start=None, n_r=n_r, m=m)
-    if hf_index:
-        hf_row_idx = np.stack([np.sort(rng.choice(H.shape[0], m, replace=False)) for _ in range(W)]).astype(np.int32)
-        hf_count = (m - 3 * np.arange(W) - 1).astype(np.int32)
-        hfi = dict(idx, hf_row_idx=hf_row_idx, hf_count=hf_count)
-        del hfi["hf_start"]
-        yield "index+hf", P, hfi, dict(hfi, start=None, hf_start=None, n_r=n_r, m=m)
 
 
 def oracle_sweep(k, N, panel, okw, n0, w0):

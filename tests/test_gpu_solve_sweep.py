@@ -132,6 +132,45 @@ def test_conjugate_sweep_matches_numpy_solve_of_oracle_S1(dev, k, N):
         assert_close(x, ref, what=f"conjugate k={k} {name}")
 
 
+# ---- 1b. the sizes it claims ----------------------------------------------------------------------------------------
+def check_against_numpy_solve(dev, k, S, n_rhs, default_rhs, seed):
+    """Jeffreys (default centring), N = 2 k + 24 rows, W = 2, shift 0 all-zero: x against numpy.linalg.solve of
+    (T - t t'/N + d I + e 1 1') X = [t |] rhs, all columns at once, T and t from the oracle's statistics."""
+    W, N = 2, max(2 * k + 24, 13)                          # (at least 12 rows per window)
+    inp = synthetic.make_kernel_inputs(k, N, W, seed=seed)
+    rng = np.random.default_rng(seed)
+    shift = make_shift(rng, W, S)
+    rhs = rng.normal(size=(W, n_rhs, k))
+    b = dev.batch("jeffreys", k, N, inp["n_r"], GAMMA, W)
+    b.upload(inp["panel"], start=inp["start"])
+    x, status = b.solve_sweep(shift=shift, rhs=rhs, default_rhs=default_rhs)
+    b.close()
+    R = n_rhs + (1 if default_rhs else 0)
+    assert x.shape == (W, S, R, k) and (status == _native.STATUS_OK).all(), status
+    ref = np.empty_like(x)
+    for w in range(W):
+        X = inp["panel"][inp["start"][w]:inp["start"][w] + inp["n_r"]]
+        T, t = oracle.canonical_statistics_T(X), oracle.canonical_statistics_t(X)
+        B = np.column_stack(([t] if default_rhs else []) + [rhs[w, j] for j in range(n_rhs)])
+        for s in range(S):
+            M = T - np.outer(t, t) / N + shift[w, s, 0] * np.eye(k) + shift[w, s, 1] * np.ones((k, k))
+            ref[w, s] = np.linalg.solve(M, B).T / GAMMA
+    assert_close(x, ref, what=f"k={k} S={S} R={R}")
+
+
+@pytest.mark.parametrize("k", [1, 2, 15, 16, 17, 63, 64, 65, 127, 128, 129, 143])
+def test_solve_sweep_edge_sizes(dev, k):
+    """One and two assets, the tile edges of the Gram pass, the largest universe, and both sides of the sizes at which a lane
+    of sweep_back_substitute takes another solution register (row i of lane i % 64 is register i / 64: k = 64 / 65, 128 / 129)."""
+    check_against_numpy_solve(dev, k, 3, 2, True, 777000 + k)
+
+
+@pytest.mark.parametrize("default_rhs", [True, False], ids=["default+15", "16"])
+def test_solve_sweep_largest_launch(dev, default_rhs):
+    """k = 143 with R = 16: the documented maximum, the largest packed triangle and the largest LDS image (98.3 KiB)."""
+    check_against_numpy_solve(dev, _native.sweep_max_assets(), 2, 15 if default_rhs else 16, default_rhs, 778000)
+
+
 # ---- 2. against the existing device path ----------------------------------------------------------------------------
 @pytest.mark.parametrize("k,N", [(10, 60), (100, 250), (143, 300)])
 def test_single_solve_equals_set_rhs_set_shift_run(dev, k, N):

@@ -16,6 +16,8 @@ import pytest
 from incorporating_different_sources_amd import _native, synthetic
 from oracle import oracle
 
+from _tiled_sweep_cases import layouts, make_shift
+
 pytestmark = pytest.mark.gpu
 
 GAMMA = 5.0
@@ -38,31 +40,6 @@ def assert_close(x, ref, tol=TOL, what=""):
     print(f"{what}: max|sweep - ref| = {err:.3e} (bound {bound:.3e}, |ref|.max() = {np.abs(ref).max():.3e})")
     assert np.isfinite(x).all()
     assert err <= bound, f"{what}: {err:.3e} > {bound:.3e}"
-
-
-def make_shift(rng, W, S):
-    """[W x S x 2]: shift 0 all-zero, d ~ Gamma(1, 10)/2, e ~ U(0, 50)."""
-    sh = np.stack([rng.gamma(1.0, 10.0, size=(W, S)) / 2, rng.uniform(0.0, 50.0, size=(W, S))], axis=2)
-    sh[:, 0, :] = 0.0
-    return sh
-
-
-def layouts(inp, seed):
-    """(name, panel, upload kwargs, oracle kwargs) of the contiguous layout and of one with row_idx / n_rows / col_idx /
-    rf_adj over a panel with 8 more columns to choose from (tests/test_gpu_solve_sweep.py::layouts)."""
-    k, W, n_r = inp["k"], inp["W"], inp["n_r"]
-    cont = dict(start=inp["start"], hf_panel=inp["hf_panel"], hf_start=inp["hf_start"], w0=inp["w0"], n0=inp["n0"])
-    yield "contiguous", inp["panel"], cont, dict(cont, n_r=n_r, m=inp["m"])
-    rng = np.random.default_rng(seed)
-    P = np.concatenate([inp["panel"], rng.normal(0.0, 0.01, size=(inp["panel"].shape[0], 8))], axis=1)
-    H = np.concatenate([inp["hf_panel"], rng.normal(0.0, 0.001, size=(inp["hf_panel"].shape[0], 8))], axis=1)
-    col_idx = np.stack([rng.permutation(P.shape[1])[:k] for _ in range(W)]).astype(np.int32)
-    row_idx = np.stack([inp["start"][w] + np.sort(rng.choice(n_r, n_r, replace=False)) for w in range(W)]).astype(np.int32)
-    n_rows = rng.integers(max(k, n_r - 5), n_r + 1, size=W).astype(np.int32)
-    rf_adj = rng.normal(0, 1e-4, size=(W, n_r))
-    idx = dict(row_idx=row_idx, n_rows=n_rows, col_idx=col_idx, rf_adj=rf_adj, hf_panel=H, hf_start=inp["hf_start"],
-               w0=inp["w0"], n0=inp["n0"])
-    yield "index", P, idx, dict(idx, start=None, n_r=n_r, m=inp["m"])
 
 
 def window_rows(panel, okw, k, w):
