@@ -14,7 +14,8 @@
 //   * register r of an accumulator tile holds rows 4r..4r+3 of the tile in exactly the MFMA operand layout, so
 //     the block row R_jJ = M A_jJ and the trailing update A_IJ -= R_jI' R_jJ of the blocked Cholesky take their
 //     operands from the accumulators themselves - the factorisation touches LDS only for the 16x16 diagonal
-//     tile (to turn it into one column per lane for the pivot chain) and for M = R_jj^-T;
+//     tile (to turn it into one column per lane for the pivot chain, and to broadcast a pivot's multipliers) and for
+//     M = R_jj^-T;
 //   * the back substitution runs along block ROWS: lane-local products over the tiles of the row, one 16-lane
 //     DPP reduction per register, and w_I = M' z by MFMA with z as the A operand - no partial sums through LDS;
 //   * no __syncthreads anywhere.
@@ -33,7 +34,7 @@ struct WCfg {
     static constexpr int NTILES = NT * (NT + 1) / 2;
     static constexpr int MLD = 17;                               // row stride of an M block (conflict-free both ways)
     static constexpr int OFF_M = 0;                              // [NT][16][MLD]  M_j = R_jj^-T, row-major
-    static constexpr int OFF_DG = OFF_M + NT * 16 * MLD;         // [16][16] diagonal tile handed to the pivot chain
+    static constexpr int OFF_DG = OFF_M + NT * 16 * MLD;         // [16][16] diagonal tile for the pivot chain, then two multiplier rows
     static constexpr int OFF_IDT = OFF_DG + 256;                 // [16][16] identity
     static constexpr int OFF_VEC = OFF_IDT + 256;                // [KP] column sums / Jeffreys t / y
     static constexpr int LDS_DOUBLES = OFF_VEC + KP;
@@ -789,10 +790,24 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
             const double* src = (lane < 16) ? (lds + C::OFF_DG) : (lds + C::OFF_IDT);
 #pragma unroll
             for (int i = 0; i < 16; ++i) a[i] = src[i * 16 + c16];
-            // (2) 16 pivots: multipliers by v_readlane, rsqrt (v_rsq_f64 + one cubic step) with look-ahead.  Block rows in
-            // front of the last one have 16 live pivots at compile time (no selects).  A non-positive or NaN pivot makes
-            // its 1/sqrt an infinity or a NaN: 0 * rinv is accumulated per pivot (ONE instruction) and looked at once.
+            // (2) 16 pivots, rsqrt (v_rsq_f64 + one cubic step) with look-ahead.  Block rows in front of the last one have
+            // 16 live pivots at compile time (no selects).  A non-positive or NaN pivot makes its 1/sqrt an infinity or a
+            // NaN: 0 * rinv is accumulated per pivot (ONE instruction) and looked at once.
+            // The scaled pivot row IS the multipliers of the rows below it: lane i holds row i's.
+            //  * The next diagonal element never leaves its lane: lane p+1 holds t = a[p] and a[p+1], and fma(-t, t, a[p+1])
+            //    there is the very fma the row update performs, so the next pivot's 1/sqrt is computed lane-locally and ONE
+            //    v_readlane pair of the finished value is left on the serial path (before: multiplier, update, diagonal, rsqrt).
+            //  * Rows p+1 and p+2 - what the next pivot and its own look-ahead wait for - take their multipliers by
+            //    v_readlane; every other row reads its multiplier from LDS: lanes 0..15 write the scaled pivot row to one of
+            //    two 16-double rows (by pivot parity: a write never meets the previous pivot's reads) at the front of the
+            //    OFF_DG region - free since a[] was loaded - and all lanes read it back at lane-uniform addresses (a
+            //    broadcast), two multipliers per ds_read_b128.  Lanes 16..63 write behind the two rows, so no exec mask is
+            //    switched.  The fma gets the same multiplier in the same operand position: every result keeps its bits.
             constexpr bool ALL16 = j < kI;
+            constexpr int RL = 2;                                     // rows per pivot that keep the v_readlane form
+            typedef double d2 __attribute__((ext_vector_type(2)));
+            double* const mrows = lds + C::OFF_DG;
+            const int mw = (lane < 16) ? lane : 32 + lane;
             double d0 = readlane_d(a[0], 0);
             double rinv = rsqrt_cubic(d0);
 #pragma unroll
@@ -800,19 +815,37 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
                 if (ALL16 || p < npiv) {
                     a[p] *= rinv;
                     badacc = fma(0.0, rinv, badacc);
+                    const int i0 = p + 1 + RL;                       // first row whose multiplier comes from LDS
+                    double* const mrow = mrows + 16 * (p & 1);
+                    if (i0 < 16) {
+                        mrow[mw] = a[p];
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                    }
+                    double mm[16];
+#pragma unroll
+                    for (int i = i0; i < 16; ++i) {
+                        if ((i & 1) == 0) {
+                            const d2 v = *(const d2*)(mrow + i);
+                            mm[i] = v[0];
+                            mm[i + 1] = v[1];
+                        } else if (i == i0) {
+                            mm[i] = mrow[i];
+                        }
+                    }
                     double rinv_next = 1.0;
                     if (p + 1 < 16) {
-                        const double s1 = readlane_d(a[p], p + 1);
-                        a[p + 1] = fma(-s1, a[p], a[p + 1]);
-                        double dn = readlane_d(a[p + 1], p + 1);
+                        double dn = fma(-a[p], a[p], a[p + 1]);      // lane p+1: the next diagonal element
                         if (!ALL16) dn = (p + 1 < npiv) ? dn : 1.0;
-                        rinv_next = rsqrt_cubic(dn);
+                        rinv_next = readlane_d(rsqrt_cubic(dn), p + 1);
                     }
 #pragma unroll
-                    for (int i = p + 2; i < 16; ++i) {
+                    for (int i = p + 1; i < i0 && i < 16; ++i) {
                         const double sI = readlane_d(a[p], i);
                         a[i] = fma(-sI, a[p], a[i]);
                     }
+#pragma unroll
+                    for (int i = i0; i < 16; ++i) a[i] = fma(-mm[i], a[p], a[i]);
                     rinv = rinv_next;
                     __builtin_amdgcn_sched_barrier(0);
                 }
