@@ -361,11 +361,35 @@ int tp_batch_download_prior_sweep(tp_batch_t b, double* weights, int32_t* status
 int tp_batch_size_sweep(tp_batch_t b, int32_t n_size, const int32_t* sizes /* [n_size] */,
                         int32_t n_prior, const double* n0 /* [W x n_prior] */,
                         const double* w0 /* [W x n_prior x n_size x k] */);
+/* tp_batch_size_sweep above tp_sweep_max_assets(), on the large-k tiled pipeline: the same definition, arguments, validation
+ * and result buffers (tp_batch_download_size_sweep serves both calls), every (window, prior) factorised ONCE at k by the tiled
+ * MFMA factorisation with the n_size right-hand sides riding along as columns k .. k+n_size-1 of the arena, then one prefix
+ * back substitution per size.  Individual sizes may be anything within [1, k], sizes <= tp_sweep_max_assets() included.
+ * TP_ERR_UNSUPPORTED: k <= tp_sweep_max_assets() (tp_batch_size_sweep serves those); k + n_size > tp_max_assets() + 1.
+ * How it runs: per sub-range of windows the batch's own tiled Gram stage stores the matrices - conjugate: twice, steered by its
+ * arguments, as in tp_batch_prior_sweep_tiled, so C is RAW-MOMENT centred (exact to rounding for returns, it loses digits under
+ * a large common offset of the intraday panel); Jeffreys: once, the batch's real strategy and centring flag - never from the
+ * shared daily or intraday sums.  The (window, prior) entries live in the tiled solve sweep's own workspace at R = n_size,
+ * KP = 64 ceil((k+n_size)/64): the batch's run workspace is neither grown nor re-shaped.
+ * Prefix isolation differs from tp_batch_size_sweep in one case.  A FINITE degenerate column j (a duplicate, a zero column)
+ * leaves every size k_s <= j intact; the sizes beyond it are TP_STATUS_NOT_PD.  A NON-FINITE column j leaves the sizes
+ * k_s <= 64 floor(j/64) intact; the sizes in (64 floor(j/64), j] may come back flagged (TP_STATUS_NONFINITE or _NOT_PD) - the
+ * block steps multiply whole 64-row blocks with MFMAs, where a structural zero times a NaN is a NaN - and the sizes > j are
+ * flagged.  No size is TP_STATUS_OK with numbers that are not its own.
+ * A (window, prior, size) result does not depend on W, n_prior, the window's position, the sub-ranges or the arena's size;
+ * across different size lists it is promised to the solve's rounding only (n_size sets the arena's side).
+ * Device memory: that of tp_batch_size_sweep (no Gram-pass outputs) plus, per entry of the sweep's workspace,
+ * KP^2 + 4096 ceil(k/64) doubles and, conjugate, 64 n_size ceil(k/64)^2 doubles of prior products - as many entries as the
+ * arena budget allows ("tiled_arena_gib" / "tiled_arena_mib"), shared with tp_batch_solve_sweep_tiled, whose downloads are
+ * left alone.  Streams, the entry drain, timing and the gather hand-over are as for tp_batch_size_sweep. */
+int tp_batch_size_sweep_tiled(tp_batch_t b, int32_t n_size, const int32_t* sizes /* [n_size] */,
+                              int32_t n_prior, const double* n0 /* [W x n_prior] */,
+                              const double* w0 /* [W x n_prior x n_size x k] */);
 /* Waits for the size sweep and copies out weights [W x P x n_size x k] (P = n_prior, 1 for a Jeffreys batch), status
  * [W x P x n_size] - per size: TP_STATUS_NOT_PD when a pivot j < k_s is <= 0 or no larger than k_s 2^-52 times its diagonal
  * element of S1 (of M); TP_STATUS_NONFINITE; TP_STATUS_BAD_DENOM (conjugate): n1 - w1'S1 w1 <= 0 - and aux
  * [W x P x n_size x TP_AUX_STRIDE] (the slots of tp_batch_download's aux: for a Jeffreys batch 0 except slot 4, t'M^-1 t over
- * the prefix); each may be NULL.  Without a size sweep before it: TP_ERR_INVALID. */
+ * the prefix); each may be NULL.  Without a size sweep (of either kind) before it: TP_ERR_INVALID. */
 int tp_batch_download_size_sweep(tp_batch_t b, double* weights /* [W x P x n_size x k] */,
                                  int32_t* status /* [W x P x n_size] */,
                                  double* aux /* [W x P x n_size x TP_AUX_STRIDE] */);

@@ -46,7 +46,7 @@ EXPORTS = [
     "tp_batch_download_rhs", "tp_batch_keep_posterior", "tp_batch_download_posterior", "tp_batch_run", "tp_batch_download", "tp_batch_download_S1", "tp_batch_download_matrix",
     "tp_batch_solve_sweep", "tp_batch_solve_sweep_tiled", "tp_batch_download_sweep", "tp_batch_download_sweep_rhs",
     "tp_batch_prior_sweep", "tp_batch_prior_sweep_tiled", "tp_batch_download_prior_sweep",
-    "tp_batch_size_sweep", "tp_batch_download_size_sweep",
+    "tp_batch_size_sweep", "tp_batch_size_sweep_tiled", "tp_batch_download_size_sweep",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
     "tp_comm_count", "tp_comm_init_all", "tp_group_gather",
@@ -119,6 +119,7 @@ def _load():
     lib.tp_batch_prior_sweep_tiled.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     lib.tp_batch_download_prior_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_size_sweep.argtypes = [c_void_p, c_int32, POINTER(c_int32), c_int32, POINTER(c_double), POINTER(c_double)]
+    lib.tp_batch_size_sweep_tiled.argtypes = [c_void_p, c_int32, POINTER(c_int32), c_int32, POINTER(c_double), POINTER(c_double)]
     lib.tp_batch_download_size_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download_S1.argtypes = [c_void_p, c_int64, POINTER(c_double)]
@@ -658,6 +659,17 @@ class Batch:
         prior).  Conjugate batch: `n0` [W x P] (> 0), `w0` [W x P x S x k] (only the first sizes[s] entries of a vector are
         read).  Jeffreys batch: no priors, P = 1.  Returns (weights [W, P, S, k] - zero beyond sizes[s] -, status [W, P, S],
         aux [W, P, S, 8] or None).  The batch's results, settings and kept arrays are left alone."""
+        return self._size_sweep(lib.tp_batch_size_sweep, sizes, n0, w0, want_aux)
+
+    def size_sweep_tiled(self, sizes, n0=None, w0=None, want_aux=True):
+        """`tp_batch_size_sweep_tiled` + `tp_batch_download_size_sweep`: `size_sweep` for k above `sweep_max_assets()`, every
+        (window, prior) factorised once at k by the large-k tiled pipeline with the S right-hand sides riding along as
+        columns k .. k+S-1 of the arena (smaller k, or k + S > max_assets() + 1: TP_ERR_UNSUPPORTED).  Same arguments, shape
+        checks and return values; single sizes may lie below `sweep_max_assets()`.  A non-finite column j also spoils the
+        sizes in (64 floor(j/64), j], which come back flagged; the intraday scatter is centred through the raw moments."""
+        return self._size_sweep(lib.tp_batch_size_sweep_tiled, sizes, n0, w0, want_aux)
+
+    def _size_sweep(self, call, sizes, n0, w0, want_aux):
         W, k = self.W, self.k
         if sizes is None or np.asarray(sizes).dtype.kind not in "iu":
             raise ValueError("sizes: a sequence of integers is expected")
@@ -685,12 +697,12 @@ class Batch:
         status = np.empty((W, P, S), dtype=np.int32)
         aux = np.empty((W, P, S, AUX_STRIDE), dtype=np.float64) if want_aux else None
         if n0 is None:
-            self.dev._check(lib.tp_batch_size_sweep(self._b, S, _ptr(sz, c_int32), 0, None, None))
+            self.dev._check(call(self._b, S, _ptr(sz, c_int32), 0, None, None))
         else:
             # (W = 0: the library still wants non-NULL prior arrays)
             n0p = n0 if n0.size else np.ones(1)
             w0p = w0 if w0.size else np.zeros(1)
-            self.dev._check(lib.tp_batch_size_sweep(self._b, S, _ptr(sz, c_int32), P, _ptr(n0p, c_double), _ptr(w0p, c_double)))
+            self.dev._check(call(self._b, S, _ptr(sz, c_int32), P, _ptr(n0p, c_double), _ptr(w0p, c_double)))
         self.dev._check(lib.tp_batch_download_size_sweep(self._b, _ptr(weights if weights.size else None, c_double),
                                                          _ptr(status if status.size else None, c_int32),
                                                          _ptr(aux if aux is not None and aux.size else None, c_double)))

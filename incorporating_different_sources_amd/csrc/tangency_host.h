@@ -14,6 +14,7 @@
 #include "posterior_kernels.h"
 #include "posterior_prior_sweep.h"
 #include "posterior_size_sweep.h"
+#include "posterior_size_sweep_tiled.h"
 #include "posterior_solve_sweep_tiled.h"
 
 #define TP_REGION_MAX_STEPS 512
@@ -72,6 +73,7 @@ struct SolveSweepWs {
     // tp_batch_solve_sweep_tiled: its own workspace of (window, shift) entries at the sweep's geometry (KP from k + R) - the
     // batch's run workspace keeps the size and shape tp_batch_run gives it
     DevBuf arena, rinv, flags;
+    DevBuf part;                    // tp_batch_size_sweep_tiled borrows that workspace (R = n_size): pieces of its prior products
     int S = 0, R = 0;               // shape of the last sweep (0: none yet)
 };
 
@@ -96,7 +98,7 @@ struct tp_batch_s {
     DevBuf post;                                              // kept posterior matrices [post_count x k x k] (tp_batch_keep_posterior)
     int64_t post_w0 = 0, post_count = 0;
     SolveSweepWs sw;                                          // tp_batch_solve_sweep / _solve_sweep_tiled
-    PriorSweepWs ps, zs;                                      // tp_batch_prior_sweep / _prior_sweep_tiled; tp_batch_size_sweep
+    PriorSweepWs ps, zs;                                      // tp_batch_prior_sweep / _prior_sweep_tiled; tp_batch_size_sweep / _size_sweep_tiled
     PriceStaging fe, fe_hf;                                   // daily and intraday (freed after a synchronous upload)
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)

@@ -1,5 +1,5 @@
 // tangency_sweep.cpp - the sweeps of the C-ABI of libtangency.so (include/tangency_posterior.h): many solves per window
-// from one Gram pass - tp_batch_solve_sweep, _prior_sweep, _size_sweep, the two tiled forms above tp_sweep_max_assets(), and
+// from one Gram pass - tp_batch_solve_sweep, _prior_sweep, _size_sweep, the three tiled forms above tp_sweep_max_assets(), and
 // their downloads.  Every sweep is: checks, a drain of the handle's stream, its workspace (SolveSweepWs / PriorSweepWs,
 // tangency_host.h), then per sub-range of windows a Gram stage and a solve stage inside one timed span.
 #include <cmath>
@@ -17,7 +17,7 @@ using namespace tp_host;
 
 namespace {
 
-// ---- what the five sweeps share ---------------------------------------------------------------------------------------
+// ---- what the six sweeps share ---------------------------------------------------------------------------------------
 
 // the sweep kernels serve k <= tp_sweep_max_assets(), the tiled forms (`partner`: the sweep below them) the universes above
 int check_sweep_k(tp_handle_t h, bool tiled, const char* name, const char* partner, int k) {
@@ -179,21 +179,24 @@ int solve_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_sh
 
 // The sweep's own tiled workspace (arena, inverse diagonal blocks, flags) at the sweep's geometry, KP from k + R: as many
 // (window, shift) entries as the large-k arena budget allows (tiled_arena_entries, the rule ensure_tiled_ws sizes by; what this
-// workspace already holds counts as free), at most `entries`.  The batch's run workspace is left as it is.
-int ensure_sweep_tiled_ws(tp_batch_t b, int R, int64_t entries, tp_tiled_ws_t* ws, int64_t* cap_out) {
+// workspace already holds counts as free), at most `entries`.  The batch's run workspace is left as it is.  `part_doubles` > 0
+// (the tiled size sweep): that many doubles of ws->part per entry, inside the same budget.
+int ensure_sweep_tiled_ws(tp_batch_t b, int R, int64_t entries, tp_tiled_ws_t* ws, int64_t* cap_out, size_t part_doubles = 0) {
     tp_handle_t h = b->h;
     SolveSweepWs& sw = b->sw;
     int KP, NS, NSB;
     tp_solve_sweep_tiled_geometry(b->p.k, R, &KP, &NS, &NSB);
-    const size_t per_entry = sizeof(double) * ((size_t)KP * KP + (size_t)NSB * 64 * 64) + sizeof(int);
-    int64_t G = tiled_arena_entries(h, per_entry, sw.arena.bytes + sw.rinv.bytes + sw.flags.bytes);
+    const size_t per_entry = sizeof(double) * ((size_t)KP * KP + (size_t)NSB * 64 * 64 + part_doubles) + sizeof(int);
+    int64_t G = tiled_arena_entries(h, per_entry, sw.arena.bytes + sw.rinv.bytes + sw.flags.bytes + sw.part.bytes);
     if (G > entries) G = entries;
     int rc = ensure(h, sw.arena, sizeof(double) * (size_t)G * KP * KP, "tp_batch_solve_sweep_tiled: arena");
     if (rc == TP_OK) rc = ensure(h, sw.rinv, sizeof(double) * (size_t)G * NSB * 64 * 64, "tp_batch_solve_sweep_tiled: inverse diagonal blocks");
     if (rc == TP_OK) rc = ensure(h, sw.flags, sizeof(int) * (size_t)G, "tp_batch_solve_sweep_tiled: flags");
+    if (rc == TP_OK && part_doubles > 0) rc = ensure(h, sw.part, sizeof(double) * (size_t)G * part_doubles, "tp_batch_size_sweep_tiled: prior products");
     if (rc != TP_OK) return rc;
     memset(ws, 0, sizeof *ws);
     ws->arena = (double*)sw.arena.p; ws->rinv = (double*)sw.rinv.p; ws->flags = (int*)sw.flags.p;
+    if (part_doubles > 0) ws->part = (double*)sw.part.p;
     ws->KP = KP; ws->NS = NS; ws->NSB = NSB;
     *cap_out = G;
     return TP_OK;
@@ -202,8 +205,9 @@ int ensure_sweep_tiled_ws(tp_batch_t b, int R, int64_t entries, tp_tiled_ws_t* w
 // ---- prior sweeps and the size sweep ------------------------------------------------------------------------------------
 
 // What the prior sweeps and the size sweep share - tp_batch_prior_sweep (`tiled` = false, k <= tp_sweep_max_assets()),
-// tp_batch_prior_sweep_tiled (above it) and tp_batch_size_sweep (`sz` given: n_size universes per (window, prior), a Jeffreys
-// batch allowed - without priors), each on the workspace `ws` of its own: the argument checks, the drain, the windows per
+// tp_batch_prior_sweep_tiled (above it), tp_batch_size_sweep and tp_batch_size_sweep_tiled (`sz` given: n_size universes per
+// (window, prior), a Jeffreys batch allowed - without priors; the two share `zs`), each on the workspace `ws` of its own: the
+// argument checks, the k range, the drain, the windows per
 // sub-range (C and T: two k x k matrices per window), the sweep's buffers and the copies of the caller's arrays.
 // *chunk_out = 0: W = 0, nothing to launch (the sweep's shape is set).
 struct SizeAxis { int32_t n_size; const int32_t* sizes; };
@@ -240,8 +244,11 @@ int prior_sweep_prepare(tp_batch_t b, PriorSweepWs& ws, const char* name, bool t
                 if (!std::isfinite(w0[e * k + i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)(e * k + i));
         }
     }
-    rc = check_sweep_k(h, tiled, name, "tp_batch_prior_sweep", k);
-    if (rc == TP_OK) rc = drain_for_sweep(b);
+    rc = check_sweep_k(h, tiled, name, sz ? "tp_batch_size_sweep" : "tp_batch_prior_sweep", k);
+    if (rc != TP_OK) return rc;
+    if (tiled && sz && k + S > tp_max_assets() + 1)
+        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d with %d sizes exceeds the arena side %d", name, k, S, tp_max_assets() + 1);
+    rc = drain_for_sweep(b);
     if (rc != TP_OK) return rc;
     ws.P = 0; ws.S = 0;
     if (W == 0) { ws.P = P; ws.S = S; return TP_OK; }
@@ -259,7 +266,7 @@ int prior_sweep_prepare(tp_batch_t b, PriorSweepWs& ws, const char* name, bool t
     if (rc == TP_OK) rc = ensure(h, ws.status, sizeof(int32_t) * WPS, (what + "statuses").c_str());
     if (rc == TP_OK) rc = ensure(h, ws.aux, sizeof(double) * WPS * TP_AUX_STRIDE, (what + "aux").c_str());
     if (rc == TP_OK && sz) rc = ensure(h, ws.sizes, sizeof(int32_t) * (size_t)S, (what + "sizes").c_str());
-    if (rc == TP_OK && sz && !conj) {                      // outputs of the run kernel that serves as the Gram pass
+    if (rc == TP_OK && sz && !conj && !tiled) {            // outputs of the run kernel that serves as the Gram pass
         rc = ensure(h, ws.gw, sizeof(double) * (size_t)W * k, (what + "weights of the Gram pass").c_str());
         if (rc == TP_OK) rc = ensure(h, ws.gs, sizeof(int32_t) * (size_t)W, (what + "statuses of the Gram pass").c_str());
         if (rc == TP_OK) rc = ensure(h, ws.ga, sizeof(double) * (size_t)W * TP_AUX_STRIDE, (what + "aux of the Gram pass").c_str());
@@ -294,6 +301,30 @@ tp_gram_kargs_t gram_pass_kargs(tp_batch_t b, const PriorSweepWs& ws) {
     ga.in.w0 = nullptr; ga.in.n0 = nullptr;
     ga.C = (double*)ws.C.p; ga.T = (double*)ws.T.p; ga.t = (double*)ws.t.p;
     return ga;
+}
+
+// The two passes of the batch's tiled Gram stage that give a conjugate tiled sweep its matrices, steered by their arguments: T
+// and t into `ps` as a Jeffreys batch without centring over the daily rows, C as a Jeffreys batch centred by the window's row
+// count over the INTRADAY rows
+void tiled_conjugate_gram_kargs(tp_batch_t b, const PriorSweepWs& ps, tp_kargs_t* ta_out, tp_kargs_t* ca_out) {
+    // T and t: the daily rows as a plain run reads them, uncentred and without the prior
+    tp_kargs_t ta = neutral_kargs(b);
+    ta.strategy = TP_STRATEGY_JEFFREYS;
+    ta.center_rows = 2;
+    ta.w0 = nullptr; ta.n0 = nullptr;
+    ta.out_rhs = (double*)ps.t.p;
+    ta.out_post = (double*)ps.T.p;
+    // C: the same stage over the intraday rows - the daily-panel fields name the intraday panel (its own 32-bit offset flags:
+    // make_kargs formed hf_off32 from that panel's bytes, leading dimension and m), centred by the window's row count
+    tp_kargs_t ca = ta;
+    ca.panel = ta.hf_panel; ca.start = ta.hf_start; ca.row_idx = ta.hf_row_idx; ca.n_rows = ta.hf_count;
+    ca.n_r = b->p.m; ca.rf_adj = nullptr;
+    ca.panel_ld = ta.hf_ld; ca.panel_off32 = ta.hf_off32;
+    ca.center_rows = 1;
+    ca.out_rhs = nullptr;
+    ca.out_post = (double*)ps.C.p;
+    for (tp_kargs_t* g : {&ta, &ca}) { g->hf_panel = nullptr; g->hf_start = nullptr; g->hf_row_idx = nullptr; g->hf_count = nullptr; g->hf_off32 = 0; }
+    *ta_out = ta; *ca_out = ca;
 }
 
 // the results of the last sweep on `ws`: [W x P x S] weight vectors, statuses and aux rows (W = 0: nothing to copy)
@@ -472,23 +503,8 @@ int tp_batch_prior_sweep_tiled(tp_batch_t b, int32_t n_prior, const double* n0, 
     if (rc != TP_OK) return rc;
     ws.part = (double*)b->t_part.p;
 
-    // T and t: the daily rows as a plain run reads them, uncentred and without the prior
-    tp_kargs_t ta = neutral_kargs(b);
-    ta.strategy = TP_STRATEGY_JEFFREYS;
-    ta.center_rows = 2;
-    ta.w0 = nullptr; ta.n0 = nullptr;
-    ta.out_rhs = (double*)ps.t.p;
-    ta.out_post = (double*)ps.T.p;
-    // C: the same stage over the intraday rows - the daily-panel fields name the intraday panel (its own 32-bit offset flags:
-    // make_kargs formed hf_off32 from that panel's bytes, leading dimension and m), centred by the window's row count
-    tp_kargs_t ca = ta;
-    ca.panel = ta.hf_panel; ca.start = ta.hf_start; ca.row_idx = ta.hf_row_idx; ca.n_rows = ta.hf_count;
-    ca.n_r = b->p.m; ca.rf_adj = nullptr;
-    ca.panel_ld = ta.hf_ld; ca.panel_off32 = ta.hf_off32;
-    ca.center_rows = 1;
-    ca.out_rhs = nullptr;
-    ca.out_post = (double*)ps.C.p;
-    for (tp_kargs_t* g : {&ta, &ca}) { g->hf_panel = nullptr; g->hf_start = nullptr; g->hf_row_idx = nullptr; g->hf_count = nullptr; g->hf_off32 = 0; }
+    tp_kargs_t ta, ca;
+    tiled_conjugate_gram_kargs(b, ps, &ta, &ca);
     tp_prior_sweep_tiled_kargs_t sa;
     memset(&sa, 0, sizeof sa);
     sa.C = (const double*)ps.C.p; sa.T = (const double*)ps.T.p; sa.t = (const double*)ps.t.p;
@@ -559,6 +575,65 @@ int tp_batch_size_sweep(tp_batch_t b, int32_t n_size, const int32_t* sizes, int3
         sa.w_first = wf; sa.w_count = n;
         return launched(h, tp_size_sweep_launch(sa, h->stream), "size sweep kernel");
     }, [&] { ws.P = P; ws.S = n_size; });
+}
+
+// Size sweep above tp_sweep_max_assets(), on the large-k tiled pipeline.  Per sub-range the batch's own tiled Gram stage stores
+// the matrices - conjugate: the two passes of the tiled prior sweep (T, t, raw-moment-centred C); Jeffreys: the batch's real
+// strategy and centring flag (M into zs.T, t into zs.t) - through the batch's run workspace, neither grown nor re-shaped.  Then
+// the sub-range's (window, prior) pairs go through the SWEEP's workspace (the tiled solve sweep's, at R = n_size) in groups of
+// its capacity: posterior_size_sweep_tiled.hip fills them, the block steps factorise them ONCE at k and forward-substitute the
+// n_size columns, and the sweep's own kernel back-substitutes every size over its prefix.
+int tp_batch_size_sweep_tiled(tp_batch_t b, int32_t n_size, const int32_t* sizes, int32_t n_prior, const double* n0, const double* w0) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    PriorSweepWs& zs = b->zs;
+    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
+    const int P = conj ? n_prior : 1;
+    const SizeAxis sz{n_size, sizes};
+    int64_t chunk = 0;
+    int rc = prior_sweep_prepare(b, zs, "tp_batch_size_sweep_tiled", true, n_prior, n0, w0, &chunk, &sz);
+    if (rc != TP_OK || chunk == 0) return rc;
+    tp_tiled_ws_t gws;
+    rc = ensure_tiled_ws(b, &gws);
+    if (rc != TP_OK) return rc;
+    const int64_t gcap = b->tiled_capacity;
+    tp_tiled_ws_t ws;
+    int64_t cap = 0;
+    rc = ensure_sweep_tiled_ws(b, n_size, chunk * P, &ws, &cap, conj ? tp_size_sweep_tiled_part_doubles(b->p.k, n_size) : 0);
+    if (rc != TP_OK) return rc;
+    tp_kargs_t ta, ca;                                 // conjugate
+    tiled_conjugate_gram_kargs(b, zs, &ta, &ca);
+    tp_kargs_t ja = neutral_kargs(b);                  // Jeffreys
+    ja.out_rhs = (double*)zs.t.p; ja.out_post = (double*)zs.T.p;
+    tp_size_sweep_tiled_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.C = conj ? (const double*)zs.C.p : nullptr;
+    sa.T = (const double*)zs.T.p; sa.t = (const double*)zs.t.p;
+    sa.n0 = conj ? (const double*)zs.n0.p : nullptr; sa.w0 = conj ? (const double*)zs.w0.p : nullptr;
+    sa.hf_count = (const int*)b->hf_count.p;
+    sa.sizes = (const int*)zs.sizes.p;
+    sa.weights = (double*)zs.weights.p; sa.status = (int*)zs.status.p; sa.aux = (double*)zs.aux.p;
+    sa.k = b->p.k; sa.P = P; sa.S = n_size; sa.N = b->p.N; sa.m = b->p.m;
+    sa.gamma = b->p.gamma;
+    // the block steps read k, w_count (set per group below) and the kernel choices; everything else stays zero
+    tp_kargs_t fa;
+    memset(&fa, 0, sizeof fa);
+    fa.k = b->p.k;
+    fa.opts = h->opts;
+    return run_sweep(b, chunk, [&](int64_t wf, int64_t n) {
+        const int rcg = conj ? tiled_gram_stage(b, "tiled size sweep Gram", {&ta, &ca}, gws, gcap, wf, n)
+                             : tiled_gram_stage(b, "tiled size sweep Gram", {&ja}, gws, gcap, wf, n);
+        if (rcg != TP_OK) return rcg;
+        return in_groups(n * P, cap, [&](int64_t e0, int64_t ne) {
+            sa.wc_first = wf;
+            sa.e_first = wf * P + e0; sa.e_count = ne;
+            int rce = launched(h, tp_size_sweep_tiled_fill_launch(sa, ws, h->stream), "tiled size sweep fill");
+            fa.w_count = ne;
+            if (rce == TP_OK) rce = launched(h, tp_tiled_block_steps_launch(fa, ws, h->stream), "tiled size sweep factor");
+            if (rce == TP_OK) rce = launched(h, tp_size_sweep_tiled_solve_launch(sa, ws, h->stream), "tiled size sweep solve");
+            return rce;
+        });
+    }, [&] { zs.P = P; zs.S = n_size; });
 }
 
 int tp_batch_download_size_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux) {

@@ -989,6 +989,13 @@ def calculate_weights_for_specs(trading_dates, portfolio_specs_list, market_data
     return _fill_spec_cache(specs, trading_dates, market_data, weights, n_dates, same_gamma, labels, kw["col_idx"], caps)
 
 
+# `calculate_weights_for_sizes` with a largest size above `_native.sweep_max_assets()`: True packs every requested size once at
+# the largest and takes one tiled size sweep (`Batch.size_sweep_tiled`) - the sizes below that bound are then prefixes of the
+# same sweep - instead of one `_weights_for_dates` per size above it.  Off: DESIGN.md section 4k holds the timings a later
+# change decides the default from.
+SIZE_SWEEP_TILED = False
+
+
 def _size_family(portfolio_spec):
     """Specs with equal (window, frequencies) see the same dates' rows; `size` picks a prefix of the cap-ordered universe."""
     return tuple(portfolio_spec.get(name) for name in ("rebalancing_frequency", "rolling_window", "rolling_window_frequency"))
@@ -999,7 +1006,9 @@ def calculate_weights_for_sizes(trading_dates, portfolio_specs_list, market_data
     same dates with ONE host pack at the largest size (`batch.pack_windows_nested`), ONE upload and ONE size sweep
     (`Batch.size_sweep`): every (window, prior) is factorised once and each size solved over its prefix of the cap-ordered
     universe.  Conjugate specs only, or Jeffreys specs only, of one (window, frequencies) family.  (date, size) pairs the pack
-    cannot serve (its mask) and sizes above `_native.sweep_max_assets()` go through `_weights_for_dates` for that spec.
+    cannot serve (its mask) and sizes above `_native.sweep_max_assets()` go through `_weights_for_dates` for that spec - unless
+    SIZE_SWEEP_TILED is set: then, when the largest size exceeds that bound (and the sizes fit one tiled sweep), ALL sizes are
+    packed once at the largest and swept with `Batch.size_sweep_tiled`.
     Returns one (weights, labels, cols, caps) per spec, each at its own size - equal to `_weights_for_dates` spec by spec
     within the solve's rounding - and remembers the conjugate ones in the cache slots `calculate_weights_for_specs` fills.
     When the pack at the largest swept size raises a ValueError - a date with fewer eligible stocks than that size, incomplete
@@ -1019,7 +1028,11 @@ def calculate_weights_for_sizes(trading_dates, portfolio_specs_list, market_data
     N = specs[0]["rolling_window"]
     gammas = [sp["risk_aversion"] for sp in specs]
     same_gamma = all(g == gammas[0] for g in gammas)
-    sizes = sorted({int(sp["size"]) for sp in specs if sp["size"] <= _native.sweep_max_assets()})
+    sizes = sorted({int(sp["size"]) for sp in specs})
+    tiled = bool(SIZE_SWEEP_TILED and sizes[-1] > _native.sweep_max_assets() and len(sizes) <= _native.SWEEP_MAX_RHS
+                 and sizes[-1] + len(sizes) <= _native.max_assets() + 1)
+    if not tiled:
+        sizes = [ks for ks in sizes if ks <= _native.sweep_max_assets()]
     swept = None
     packed = None
     if sizes:
@@ -1050,7 +1063,7 @@ def calculate_weights_for_sizes(trading_dates, portfolio_specs_list, market_data
         try:
             b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m", "w0", "n0")},
                      **(dict(w0=kw["w0"], n0=kw["n0"]) if conj else {}))
-            weights, status, _ = b.size_sweep(sizes, n0, w0, want_aux=False)
+            weights, status, _ = (b.size_sweep_tiled if tiled else b.size_sweep)(sizes, n0, w0, want_aux=False)
         finally:
             b.close()
         swept = (weights, status, labels, kw["col_idx"], caps, mask, prior_keys)
