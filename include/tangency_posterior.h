@@ -393,6 +393,56 @@ int tp_batch_size_sweep_tiled(tp_batch_t b, int32_t n_size, const int32_t* sizes
 int tp_batch_download_size_sweep(tp_batch_t b, double* weights /* [W x P x n_size x k] */,
                                  int32_t* status /* [W x P x n_size] */,
                                  double* aux /* [W x P x n_size x TP_AUX_STRIDE] */);
+/* Window sweep: n_len nested window lengths per window - the `rolling_window` axis of a spec grid - from ONE pack, ONE upload
+ * and ONE pass over the rows of the longest window.  It rests on the window of length N' < N that ends at a date being the
+ * tail of the longer one (ref:159) and on the intraday window not depending on the length at all (ref:299-314); the caller
+ * vouches for the universe being the same at every length (batch.pack_windows_lengths checks it).
+ * Window w has n_w daily rows (n_rows[w], else n_r) at positions 0 .. n_w-1 as uploaded, oldest first.  Length l uses the last
+ * rows[w][l] of them, positions r in [n_w - rows[w][l], n_w).  With x_r the batch's own row (panel - rf_adj), the row of
+ * length l is x_r - delta[w][l][r] 1 (delta == NULL: zero) - the per-row risk-free adjustment (ref:48) depends on the mean
+ * calendar gap of the length's own labels -, T_l = sum x x' and t_l = sum x over that suffix, and N_l = N[l] replaces
+ * tp_params_t.N wherever the definitions of tp_batch_prior_sweep / tp_batch_run read it:
+ *   conjugate batch, prior p: C, m, a = n0_wpl m/(m-1) as in tp_batch_prior_sweep, C and w0_wp shared by all lengths;
+ *     S1 = a C + T_l ;  q0 = a w0_wp'C w0_wp ;  c = 2 n0_wpl / (g + sqrt(g^2 + 4 n0_wpl q0)),  g = n0_wpl + k + 2
+ *     w1 = S1^-1 (c a C w0_wp + t_l) ;  n1 = n0_wpl + N_l ;  weights[w][p][l] = (n1 + k + 2) w1 / (n1 - w1'S1 w1) / gamma
+ *   Jeffreys batch: n_prior = 0, n0 = w0 = NULL, the outputs have P = 1: weights[w][0][l] = M^-1 t_l / gamma with
+ *     M = T_l - t_l t_l'/N_l (TP_FLAG_CENTER_BY_ROWS: / rows[w][l]; TP_FLAG_NO_CENTER: M = T_l).
+ * The batch's own uploaded w0 / n0, its tp_batch_set_rhs and tp_batch_set_shift are not used.
+ * TP_ERR_INVALID: a batch that was not uploaded; n_len outside [1, TP_SWEEP_MAX_RHS]; N NULL, not strictly increasing or < 1;
+ * rows NULL; a rows[w][l] < 1, > n_w or decreasing in l (ties are allowed: an early date truncates several lengths to the same
+ * rows); a non-finite delta at a position some length reads; conjugate: n_prior < 1, n0 or w0 NULL, an n0 that is not finite
+ * and > 0, a non-finite w0; Jeffreys: n_prior != 0 or a non-NULL n0 / w0.  TP_ERR_UNSUPPORTED: k > tp_sweep_max_assets() (also:
+ * index-layout windows of more than about 10,000 rows).  TP_ERR_HIP: an allocation failed (the message names the byte count).
+ * A call refused with TP_ERR_INVALID leaves the results of the last window sweep in place.
+ * How it runs: sub-ranges of windows as in tp_batch_prior_sweep ("sweep_chunk_windows"), holding n_len (conjugate: + 1) k x k
+ * matrices per window inside 256 MiB.  Per sub-range one Gram pass - one wavefront per window - stores C once, then takes the
+ * daily rows through the MFMAs from the newest backwards in n_len segments and stores a snapshot (T_l, t_l) after each: a
+ * snapshot is a store, not more flops.  With a delta, one more kernel forms v = sum delta_r x_r, s1 = sum delta_r and
+ * s2 = sum delta_r^2 per (window, length); the solve kernel - one workgroup per (window, prior, length) - applies
+ * T = G - v 1' - 1 v' + s2 1 1', t = g - s1 1 exactly while it loads the matrix, factorises in LDS and solves.
+ * Promises.  A (window, prior, length) result depends on the rows of its own suffix, its delta, its prior, N_l and k.  It does
+ * not depend on W, n_prior, the window's position or the sub-ranges: bit for bit.  It depends on the OTHER lengths of the list
+ * to rounding only: the list sets where the partial sums of the Gram are cut.  A row older than a length's suffix - NaN, Inf or
+ * an outlier - never reaches that length.
+ * Device memory: W x P x n_len x (k + 10) doubles of priors and results, W x P x k of w0, W x n_len x k of t, with a delta
+ * W x n_len x (n_r + k + 2) more - the copy of delta and its sums; 10,000 dates x 4 lengths x 499 rows: 160 MB, outside the
+ * 256 MiB rule -, and the sub-range's matrices; kept until tp_batch_destroy.  Streams, the entry
+ * drain, timing (kernel_ms covers every launch; one step of tp_region_steps), the gather hand-over and what the call leaves
+ * alone are as for tp_batch_size_sweep; it has result buffers of its own: every other download returns what it returned
+ * before. */
+int tp_batch_window_sweep(tp_batch_t b, int32_t n_len, const int32_t* N /* [n_len] */,
+                          const int32_t* rows /* [W x n_len] */,
+                          const double* delta /* [W x n_len x n_r] or NULL */,
+                          int32_t n_prior, const double* n0 /* [W x n_prior x n_len] */,
+                          const double* w0 /* [W x n_prior x k] */);
+/* Waits for the window sweep and copies out weights [W x P x n_len x k] (P = n_prior, 1 for a Jeffreys batch), status
+ * [W x P x n_len] (TP_STATUS_OK; TP_STATUS_NOT_PD: a pivot <= 0 or no larger than k 2^-52 times its diagonal element, e.g. a
+ * Jeffreys length of fewer rows than columns; TP_STATUS_NONFINITE; TP_STATUS_BAD_DENOM (conjugate): n1 - w1'S1 w1 <= 0) and aux
+ * [W x P x n_len x TP_AUX_STRIDE] (the slots of tp_batch_download's aux: for a Jeffreys batch 0 except slot 4, t'M^-1 t); each
+ * may be NULL.  Without a window sweep before it: TP_ERR_INVALID. */
+int tp_batch_download_window_sweep(tp_batch_t b, double* weights /* [W x P x n_len x k] */,
+                                   int32_t* status /* [W x P x n_len] */,
+                                   double* aux /* [W x P x n_len x TP_AUX_STRIDE] */);
 int tp_batch_download(tp_batch_t b, double* weights /* [W x k] */, int32_t* status /* [W] */,
                       double* aux /* optional [W x TP_AUX_STRIDE] */); /* waits for the stream, D2H */
 int tp_batch_download_S1(tp_batch_t b, int64_t w, double* S1 /* [k x k] */); /* posterior scale matrix

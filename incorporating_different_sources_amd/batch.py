@@ -447,6 +447,83 @@ def pack_windows_nested(trading_dates, portfolio_spec, sizes, market_data, membe
     return kw, labels, caps, mask
 
 
+def pack_windows_lengths(trading_dates, portfolio_spec, windows, market_data, members_of=None):
+    """`pack_windows` at max(windows) for a window sweep (`_native.Batch.window_sweep`):
+    (kw, labels, caps [W x k], rows [W x L], delta [W x L x n_r], mask [W x L]).
+    The window of length N' < N that ends at a date is the tail of the longer one (ref:159), so length l uses the last
+    rows[w, l] rows of the pack.  `delta[w, l]` is, at those positions, the length's own per-row risk-free adjustment (ref:48:
+    `rf_at_label` and the mean calendar gap of ITS labels) minus the pack's; zero elsewhere.  mask[w, l] says whether the window
+    of length windows[l] at date w can be served from the pack:
+      * `select_universe` at that length's `window_days` returns the pack's columns in the pack's order (verified, not assumed:
+        the eligibility threshold `valid_run >= need` is looser for a shorter window, so a late-listed large cap can enter), and
+        the completeness check of ref:986-988 holds at that length;
+      * the gap assertion `gaps.max() <= mean_gap + 4` holds for that length's labels;
+      * the suffix has at least one row.
+    rows and delta are valid arguments of the sweep for the masked-out pairs too (their results are not to be read).
+    `portfolio_spec["rolling_window"]` is not read.  Raises what `pack_windows` raises at the longest window."""
+    windows = [int(n) for n in windows]
+    if not windows or any(b <= a for a, b in zip(windows, windows[1:])) or windows[0] < 1:
+        raise ValueError(f"windows: a strictly increasing list of positive window lengths expected, got {windows}")
+    spec = dict(portfolio_spec, rolling_window=windows[-1])
+    kw, labels, caps = pack_windows(trading_dates, spec, market_data, members_of=members_of, return_caps=True)
+    freq = spec["rolling_window_frequency"]
+    k = spec["size"]
+    mp = panels_for(market_data, freq)
+    W, L, n_r = len(trading_dates), len(windows), kw["n_r"]
+    all_members = np.ones(len(mp.tickers), dtype=bool)
+    rows = np.ones((W, L), dtype=np.int32)
+    delta = np.zeros((W, L, n_r), dtype=np.float64)
+    mask = np.ones((W, L), dtype=bool)
+    for w, ts in enumerate(trading_dates):
+        pos, members = _date_position_and_members(mp, ts, members_of, all_members)
+        cols = kw["col_idx"][w]
+        n_w = int(kw["n_rows"][w])
+        # the candidate rows of the longest window - one per label lab0+1 .. lab1 - and which of them dropna keeps, as
+        # pack_windows forms them
+        if freq == "daily":
+            lab1 = pos
+            lab0 = max(0, lab1 - windows[-1] + 1)
+            if (mp.L_nan_cum[lab1 + 1, cols] != mp.L_nan_cum[lab0 + 1, cols]).any():
+                vals_nan = mp.L_nan[np.arange(lab0 + 1, lab1 + 1, dtype=np.int64)][:, cols].any(axis=1)
+            else:                                        # no NaN return of a selected asset in the window: nothing to gather
+                vals_nan = np.zeros(lab1 - lab0, dtype=bool)
+        else:
+            lab1 = int(mp.bin_of[pos])
+            lab0 = max(0, lab1 - windows[-1] + 1)
+            block = mp.L_nan[np.arange(lab0 + 1, lab1, dtype=np.int64)][:, cols]
+            if lab1 > lab0:
+                block = np.vstack([block, _return_is_nan(mp.P[pos], mp.R[lab1 - 1])[cols][None, :]])
+            vals_nan = block.any(axis=1)
+        keep = ~vals_nan & ~np.isnan(mp.rf_at_label[lab0 + 1:lab1 + 1])
+        assert int(keep.sum()) == n_w
+        run = mp.valid_run[pos]
+        eligible_long = run >= min(windows[-1] * _TRADING_DAYS[freq], pos + 1)
+        for l, N in enumerate(windows):
+            first = max(0, lab1 - N + 1)                                        # first label of this length
+            cand = lab1 - first                                                  # its candidate rows: a suffix of the pack's
+            kept = keep[len(keep) - cand:] if cand > 0 else keep[:0]
+            r = int(kept.sum())
+            rows[w, l] = max(r, 1)
+            window_days = N * _TRADING_DAYS[freq]
+            # the window length enters select_universe through the eligibility threshold alone: where no stock's run of
+            # prices falls between the two thresholds the universe is the pack's, otherwise it is selected again and compared
+            ok = r >= 1
+            if ok and not np.array_equal(run >= min(window_days, pos + 1), eligible_long):
+                sub, _ = select_universe(mp, pos, k, window_days, spec["rebalancing_frequency"], members)
+                ok = len(sub) == k and np.array_equal(sub, cols)
+            ok = ok and not (mp.valid_run[pos, cols] < pos + 1 - max(0, pos + 1 - window_days)).any()      # ref:986-988
+            if ok:
+                gaps = mp.label_gap_days[first:lab1]
+                mean_gap = gaps.mean()
+                ok = bool(gaps.max() <= mean_gap + 4)
+                if ok:
+                    adj = (1 + mp.rf_at_label[first + 1:lab1 + 1]) ** (mean_gap / 365) - 1           # ref:48
+                    delta[w, l, n_w - r:n_w] = adj[kept] - kw["rf_adj"][w, n_w - r:n_w]
+            mask[w, l] = ok
+        rows[w] = np.maximum.accumulate(rows[w])
+    return kw, labels, caps, rows, delta, mask
+
+
 def _prior_strength(mp, mcm, d, ts, N, scaling):
     """n0 = N * max(cur/avg, avg/cur) * mcm_scaling (ref:90-114, 247-267) from the cached MCM arrays."""
     pos = int(np.searchsorted(mcm["ns"], d, side="right")) - 1

@@ -16,6 +16,7 @@
 #include "posterior_size_sweep.h"
 #include "posterior_size_sweep_tiled.h"
 #include "posterior_solve_sweep_tiled.h"
+#include "posterior_window_sweep.h"
 
 #define TP_REGION_MAX_STEPS 512
 
@@ -48,7 +49,7 @@ struct tp_handle_s {
     int hf_share_min_blocks = 6;    // "hf_share_min_blocks": whole intraday blocks per window from which the large-k path shares them
     int tiled_arena_gib = 0;        // TP_TILED_ARENA_GIB / "tiled_arena_gib" (0: default)
     int tiled_arena_mib = 0;        // TP_TILED_ARENA_MIB / "tiled_arena_mib": a sub-GiB arena (tests: many sub-batches from few windows)
-    int sweep_chunk_windows = 0;    // "sweep_chunk_windows": windows per sub-range of tp_batch_solve_sweep / _prior_sweep / _size_sweep (0: automatic)
+    int sweep_chunk_windows = 0;    // "sweep_chunk_windows": windows per sub-range of tp_batch_solve_sweep / _prior_sweep / _size_sweep / _window_sweep (0: automatic)
     int phase_limit = 0;            // TP_PHASE_LIMIT (diagnostic builds only)
     std::vector<tp_batch_t> batches;   // live batches of this handle (destroyed with it if the caller forgot them)
     // per-step kernel times inside a tp_region_begin / tp_region_end bracket: every timed launch of the region records
@@ -88,6 +89,16 @@ struct PriorSweepWs {
     int P = 0, S = 0;               // shape of the last sweep (0: none yet; a prior sweep has S = 1)
 };
 
+// Window sweep (`wn`).  C / T hold the matrices of ONE sub-range at a time: one intraday scatter (conjugate) and L snapshots
+// of the daily Gram per window; t, the delta sums and the results cover the batch.
+struct WindowSweepWs {
+    DevBuf C, T, t, n0, w0;
+    DevBuf N, rows;                 // the lengths' N [L] and row counts [W x L]
+    DevBuf delta, dv, ds;           // the caller's row offsets [W x L x n_r]; their sums v [W x L x k] and (s1, s2) [W x L x 2]
+    DevBuf weights, status, aux;
+    int P = 0, L = 0;               // shape of the last sweep (0: none yet)
+};
+
 struct tp_batch_s {
     tp_handle_t h = nullptr;
     tp_params_t p{};
@@ -99,6 +110,7 @@ struct tp_batch_s {
     int64_t post_w0 = 0, post_count = 0;
     SolveSweepWs sw;                                          // tp_batch_solve_sweep / _solve_sweep_tiled
     PriorSweepWs ps, zs;                                      // tp_batch_prior_sweep / _prior_sweep_tiled; tp_batch_size_sweep / _size_sweep_tiled
+    WindowSweepWs wn;                                         // tp_batch_window_sweep
     PriceStaging fe, fe_hf;                                   // daily and intraday (freed after a synchronous upload)
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)

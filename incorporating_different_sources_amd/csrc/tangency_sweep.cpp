@@ -6,6 +6,7 @@
 #include <cstring>
 #include <algorithm>
 #include <string>
+#include <vector>
 
 #include "tangency_host.h"
 
@@ -17,7 +18,7 @@ using namespace tp_host;
 
 namespace {
 
-// ---- what the six sweeps share ---------------------------------------------------------------------------------------
+// ---- what the sweeps share ---------------------------------------------------------------------------------------------
 
 // the sweep kernels serve k <= tp_sweep_max_assets(), the tiled forms (`partner`: the sweep below them) the universes above
 int check_sweep_k(tp_handle_t h, bool tiled, const char* name, const char* partner, int k) {
@@ -640,6 +641,140 @@ int tp_batch_download_size_sweep(tp_batch_t b, double* weights, int32_t* status,
     if (!b) return TP_ERR_INVALID;
     if (b->zs.P < 1 || b->zs.S < 1) return fail(b->h, TP_ERR_INVALID, "tp_batch_download_size_sweep: no tp_batch_size_sweep before it");
     return download_prior_ws(b, b->zs, weights, status, aux);
+}
+
+// Window sweep.  Sub-ranges hold L snapshots (conjugate: and C) per window.  Per sub-range the segmented Gram pass
+// (posterior_window_gram_nt.hip) stores C once and T_l, t_l after every segment, the delta kernel - with a delta only - forms
+// the sums of the rank-two correction, and posterior_window_sweep_kernel solves every (window, prior, length).
+int tp_batch_window_sweep(tp_batch_t b, int32_t n_len, const int32_t* N, const int32_t* rows, const double* delta,
+                          int32_t n_prior, const double* n0, const double* w0) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    WindowSweepWs& ws = b->wn;
+    const char* name = "tp_batch_window_sweep";
+    const int k = b->p.k, n_r = b->p.n_r;
+    const int64_t W = b->W;
+    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
+    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
+    if (n_len < 1 || n_len > TP_SWEEP_MAX_RHS)
+        return fail(h, TP_ERR_INVALID, "%s: n_len=%d outside [1, %d]", name, n_len, TP_SWEEP_MAX_RHS);
+    if (!N) return fail(h, TP_ERR_INVALID, "%s: N is NULL", name);
+    for (int l = 0; l < n_len; ++l)
+        if (N[l] < 1 || (l > 0 && N[l] <= N[l - 1]))
+            return fail(h, TP_ERR_INVALID, "%s: N[%d]=%d: strictly increasing lengths >= 1 expected", name, l, N[l]);
+    if (!rows) return fail(h, TP_ERR_INVALID, "%s: rows is NULL", name);
+    const int L = n_len;
+    const int P = conj ? n_prior : 1;
+    int rc = TP_OK;
+    if (conj) {
+        if (n_prior < 1) return fail(h, TP_ERR_INVALID, "%s: n_prior=%d < 1", name, n_prior);
+        if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "%s: %s is NULL", name, !n0 ? "n0" : "w0");
+        rc = check_finite_sign(h, name, "n0", n0, W * P * L, true);
+        if (rc != TP_OK) return rc;
+        for (int64_t i = 0; i < W * P * k; ++i)
+            if (!std::isfinite(w0[i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)i);
+    } else if (n_prior != 0 || n0 || w0) {
+        return fail(h, TP_ERR_INVALID, "%s: a Jeffreys batch takes no priors (n_prior = 0, n0 = w0 = NULL)", name);
+    }
+    rc = check_sweep_k(h, false, name, name, k);
+    if (rc != TP_OK) return rc;
+    rc = drain_for_sweep(b);
+    if (rc != TP_OK) return rc;
+    if (W == 0) { ws.P = P; ws.L = L; return TP_OK; }
+    // the windows' own row counts (the device copy is the one the kernels read), then the checks that need them
+    std::vector<int32_t> nw((size_t)W, n_r);
+    if (b->n_rows.p) HIP_TRY(h, hipMemcpy(nw.data(), b->n_rows.p, sizeof(int32_t) * (size_t)W, hipMemcpyDeviceToHost));
+    for (int64_t w = 0; w < W; ++w)
+        for (int l = 0; l < L; ++l) {
+            const int32_t r = rows[w * L + l];
+            if (r < 1 || r > nw[(size_t)w] || (l > 0 && r < rows[w * L + l - 1]))
+                return fail(h, TP_ERR_INVALID, "%s: rows[%lld][%d]=%d: non-decreasing row counts within [1, %d] expected", name,
+                            (long long)w, l, r, nw[(size_t)w]);
+            if (delta) {
+                const double* d = delta + (w * L + l) * (int64_t)n_r;
+                for (int i = nw[(size_t)w] - r; i < nw[(size_t)w]; ++i)
+                    if (!std::isfinite(d[i]))
+                        return fail(h, TP_ERR_INVALID, "%s: delta[%lld][%d][%d] must be finite", name, (long long)w, l, i);
+            }
+        }
+    ws.P = 0; ws.L = 0;                                // every argument check is behind us: a refused call keeps the last results
+    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
+    const int64_t chunk = sweep_chunk(h, (size_t)(L + (conj ? 1 : 0)) * mat_bytes, (int64_t)P * L, W, true);
+    const size_t WL = (size_t)W * (size_t)L, WPL = WL * (size_t)P;
+    const std::string what = std::string(name) + ": ";
+    if (conj) rc = ensure(h, ws.C, mat_bytes * (size_t)chunk, (what + "intraday scatters of one sub-range").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.T, mat_bytes * (size_t)chunk * L, (what + "daily Gram snapshots of one sub-range").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.t, sizeof(double) * WL * k, (what + "daily column sums").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.N, sizeof(int32_t) * (size_t)L, (what + "lengths").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.rows, sizeof(int32_t) * WL, (what + "row counts").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, ws.n0, sizeof(double) * WPL, (what + "prior strengths").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, ws.w0, sizeof(double) * (size_t)W * P * k, (what + "prior weights").c_str());
+    if (rc == TP_OK && delta) rc = ensure(h, ws.delta, sizeof(double) * WL * n_r, (what + "row offsets").c_str());
+    if (rc == TP_OK && delta) rc = ensure(h, ws.dv, sizeof(double) * WL * k, (what + "offset-weighted column sums").c_str());
+    if (rc == TP_OK && delta) rc = ensure(h, ws.ds, sizeof(double) * WL * 2, (what + "offset sums").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.weights, sizeof(double) * WPL * k, (what + "weights").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.status, sizeof(int32_t) * WPL, (what + "statuses").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.aux, sizeof(double) * WPL * TP_AUX_STRIDE, (what + "aux").c_str());
+    if (rc != TP_OK) return rc;
+    // the caller's arrays: copied here, no host pointer is kept
+    HIP_TRY(h, hipMemcpyAsync(ws.N.p, N, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(ws.rows.p, rows, sizeof(int32_t) * WL, hipMemcpyHostToDevice, h->stream));
+    if (conj) {
+        HIP_TRY(h, hipMemcpyAsync(ws.n0.p, n0, sizeof(double) * WPL, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(ws.w0.p, w0, sizeof(double) * (size_t)W * P * k, hipMemcpyHostToDevice, h->stream));
+    }
+    if (delta) HIP_TRY(h, hipMemcpyAsync(ws.delta.p, delta, sizeof(double) * WL * n_r, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
+
+    tp_window_gram_kargs_t ga;
+    memset(&ga, 0, sizeof ga);
+    ga.in = neutral_kargs(b);
+    ga.in.w0 = nullptr; ga.in.n0 = nullptr;
+    ga.C = conj ? (double*)ws.C.p : nullptr;
+    ga.T = (double*)ws.T.p; ga.t = (double*)ws.t.p;
+    ga.rows = (const int*)ws.rows.p; ga.L = L;
+    tp_window_delta_kargs_t da;
+    memset(&da, 0, sizeof da);
+    da.in = ga.in;
+    da.delta = (const double*)ws.delta.p; da.rows = ga.rows;
+    da.dv = (double*)ws.dv.p; da.ds = (double*)ws.ds.p; da.L = L;
+    tp_window_sweep_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.C = conj ? (const double*)ws.C.p : nullptr;
+    sa.T = (const double*)ws.T.p; sa.t = (const double*)ws.t.p;
+    sa.dv = delta ? (const double*)ws.dv.p : nullptr; sa.ds = delta ? (const double*)ws.ds.p : nullptr;
+    sa.n0 = conj ? (const double*)ws.n0.p : nullptr; sa.w0 = conj ? (const double*)ws.w0.p : nullptr;
+    sa.hf_count = (const int*)b->hf_count.p;
+    sa.rows = ga.rows; sa.N = (const int*)ws.N.p;
+    sa.weights = (double*)ws.weights.p; sa.status = (int*)ws.status.p; sa.aux = (double*)ws.aux.p;
+    sa.k = k; sa.P = P; sa.L = L; sa.m = b->p.m; sa.center_rows = ga.in.center_rows;
+    sa.gamma = b->p.gamma;
+    return run_sweep(b, chunk, [&](int64_t wf, int64_t n) {
+        ga.in.w_first = wf; ga.in.w_count = n;
+        const hipError_t e = tp_window_gram_launch(ga, h->stream);
+        if (e == hipErrorNotSupported)
+            return fail(h, TP_ERR_UNSUPPORTED, "%s: windows of %d daily / %d intraday rows in the index layout are too long "
+                                               "for the Gram pass", name, n_r, b->p.m);
+        int rcl = launched(h, e, "window sweep Gram");
+        if (rcl == TP_OK && delta) {
+            da.in.w_first = wf; da.in.w_count = n;
+            rcl = launched(h, tp_window_delta_launch(da, h->stream), "window sweep delta kernel");
+        }
+        if (rcl != TP_OK) return rcl;
+        sa.w_first = wf; sa.w_count = n;
+        return launched(h, tp_window_sweep_launch(sa, h->stream), "window sweep kernel");
+    }, [&] { ws.P = P; ws.L = L; });
+}
+
+int tp_batch_download_window_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    const WindowSweepWs& ws = b->wn;
+    if (ws.P < 1 || ws.L < 1) return fail(h, TP_ERR_INVALID, "tp_batch_download_window_sweep: no tp_batch_window_sweep before it");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)b->W * ws.P * ws.L;
+    return download(h, {{weights, ws.weights.p, sizeof(double) * n * b->p.k}, {status, ws.status.p, sizeof(int32_t) * n},
+                        {aux, ws.aux.p, sizeof(double) * n * TP_AUX_STRIDE}});
 }
 
 }  // extern "C"

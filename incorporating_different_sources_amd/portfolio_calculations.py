@@ -1094,6 +1094,91 @@ def calculate_weights_for_sizes(trading_dates, portfolio_specs_list, market_data
     return out
 
 
+def _window_family(portfolio_spec):
+    """Specs with equal (rebalancing frequency, size, window frequency) see the same universe candidates at a date;
+    `rolling_window` picks a tail of the longest window's rows."""
+    return tuple(portfolio_spec.get(name) for name in ("rebalancing_frequency", "size", "rolling_window_frequency"))
+
+
+def calculate_weights_for_windows(trading_dates, portfolio_specs_list, market_data):
+    """Weights of specs that differ in `rolling_window` (conjugate specs: also in the prior - vw / ew, VIX / EPU, mcm_scaling)
+    for the same dates with ONE host pack at the longest window (`batch.pack_windows_lengths`), ONE upload and ONE window sweep
+    (`Batch.window_sweep`): every daily row passes the device once, the intraday scatter is formed once per date, and each
+    length is solved from a snapshot of the running Gram with its own N, n0 and risk-free offsets.  Conjugate specs only, or
+    Jeffreys specs only, of one (rebalancing frequency, size, window frequency) family.  (date, length) pairs the pack cannot
+    serve (its mask), a pack that raises, more than `_native.SWEEP_MAX_RHS` lengths and sizes above
+    `_native.sweep_max_assets()` go through `_weights_for_dates` spec by spec, so the reference's exceptions surface where the
+    reference raises them.
+    Returns one (weights, labels, cols, caps) per spec - equal to `_weights_for_dates` spec by spec within the solve's rounding -
+    and remembers the conjugate ones in the cache slots `calculate_weights_for_specs` fills.
+    Opt-in: nothing calls it by default."""
+    specs = list(portfolio_specs_list)
+    if not specs:
+        return []
+    conj = specs[0]["weighting_strategy"] in _CONJUGATE
+    if (any((sp["weighting_strategy"] in _CONJUGATE) != conj or (not conj and sp["weighting_strategy"] != "jeffreys") for sp in specs)
+            or len({_window_family(sp) for sp in specs}) != 1):
+        raise ValueError("calculate_weights_for_windows: conjugate specs, or Jeffreys specs, of equal size and frequencies expected")
+    trading_dates = list(trading_dates)
+    n_dates = len(trading_dates)
+    members_of = _members_provider(market_data)
+    k = int(specs[0]["size"])
+    gammas = [sp["risk_aversion"] for sp in specs]
+    same_gamma = all(g == gammas[0] for g in gammas)
+    windows = sorted({int(sp["rolling_window"]) for sp in specs})
+    packed = None
+    if k <= _native.sweep_max_assets() and len(windows) <= _native.SWEEP_MAX_RHS:
+        try:
+            packed = batch.pack_windows_lengths(trading_dates, specs[0], windows, market_data, members_of=members_of)
+        except (ValueError, AssertionError) as exc:      # the specs decide one by one what the caller sees
+            logger.warning(f"window sweep dropped ({exc}); solving the {len(specs)} specs one by one")
+    swept = None
+    if packed is not None:
+        kw, labels, caps, rows, delta, mask = packed
+        n0 = w0 = None
+        prior_keys = []
+        if conj:
+            prior_of = lambda sp: (sp["weighting_strategy"], sp["mcm_scaling"])
+            prior_keys = list(dict.fromkeys(prior_of(sp) for sp in specs))
+            n0 = np.empty((n_dates, len(prior_keys), len(windows)))
+            w0 = np.empty((n_dates, len(prior_keys), k))
+            for p, key in enumerate(prior_keys):
+                sp = next(sp for sp in specs if prior_of(sp) == key)
+                for l, N in enumerate(windows):          # n0 reads the length (ref:112, 265); w0 does not
+                    w0[:, p], n0[:, p, l] = batch.prior_inputs(trading_dates, dict(sp, rolling_window=N), market_data, caps)
+        b = _native.Batch(_native.default_device(), "conjugate" if conj else "jeffreys", k, windows[-1], kw["n_r"],
+                          gammas[0] if same_gamma else 1.0, n_dates, kw.get("m") or 0)
+        try:
+            b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m")})
+            weights, status, _ = b.window_sweep(windows, rows, n0, w0, delta=delta if delta.any() else None, want_aux=False)
+        finally:
+            b.close()
+        swept = (weights, status, labels, kw["col_idx"], caps, mask, prior_keys)
+    out = []
+    for sp in specs:
+        if swept is None:
+            res = _weights_for_dates(trading_dates, sp, market_data)
+        else:
+            weights, status, labels, cols, caps, mask, prior_keys = swept
+            l = windows.index(int(sp["rolling_window"]))
+            p = prior_keys.index((sp["weighting_strategy"], sp["mcm_scaling"])) if conj else 0
+            ok = mask[:, l]
+            _raise_on_status(status[ok, p, l])
+            w = np.ascontiguousarray(weights[:, p, l])
+            if not same_gamma:
+                w = 1.0 / sp["risk_aversion"] * w
+            res = (w, [list(row) for row in labels], cols.copy(), caps.copy())
+            if not ok.all():                             # these dates' shorter window has another universe, or trips a check
+                miss = np.flatnonzero(~ok)
+                alone = _weights_for_dates([trading_dates[i] for i in miss], sp, market_data)
+                for j, i in enumerate(miss):
+                    res[0][i], res[1][i], res[2][i], res[3][i] = alone[0][j], alone[1][j], alone[2][j], alone[3][j]
+        if conj:
+            res = _fill_spec_cache([sp], trading_dates, market_data, res[0], n_dates, True, res[1], res[2], res[3])[0]
+        out.append(res)
+    return out
+
+
 def _replicated_weights(kw, priors, n_specs, k, N, gamma):
     """Every window once per spec in ONE device batch of n_specs x n_dates windows."""
     per_window = ("row_idx", "n_rows", "col_idx", "rf_adj", "hf_row_idx", "hf_count")
