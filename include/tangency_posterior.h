@@ -435,11 +435,47 @@ int tp_batch_window_sweep(tp_batch_t b, int32_t n_len, const int32_t* N /* [n_le
                           const double* delta /* [W x n_len x n_r] or NULL */,
                           int32_t n_prior, const double* n0 /* [W x n_prior x n_len] */,
                           const double* w0 /* [W x n_prior x k] */);
+/* tp_batch_window_sweep above tp_sweep_max_assets(), on the large-k tiled pipeline: the same definition, arguments,
+ * validation and result buffers (tp_batch_download_window_sweep serves both calls; a call refused with TP_ERR_INVALID leaves
+ * the results of the last window sweep of either kind in place).
+ * TP_ERR_UNSUPPORTED: k <= tp_sweep_max_assets() (tp_batch_window_sweep serves those).  No limit on the rows of an index-layout
+ * window: the rows are not staged.
+ * How it runs: sub-ranges of windows under the same rule ("sweep_chunk_windows", n_len (conjugate: + 1) k x k matrices per
+ * window, at least one window) inside 4 GiB, not 256 MiB: the entries are factorised in groups of one length, and the
+ * sub-range decides how full those launches run.  Per sub-range, conjugate: the batch's own tiled Gram stage runs ONCE per window
+ * over the intraday rows, steered by its arguments as in tp_batch_prior_sweep_tiled, so C is RAW-MOMENT centred (exact to
+ * rounding for returns, it loses digits under a large common offset of the intraday panel) and never comes from the shared
+ * intraday sums.  Then a segmented Gram - one wavefront per (window, 64 x 64 super-tile), 16 tiles in registers, cleared once -
+ * takes the daily rows through the MFMAs from the newest backwards in n_len segments and stores its part of (T_l, t_l) after
+ * each: max rows[w][l] rows pass the MFMAs, not their sum, and never the shared daily sums.  With a delta the delta kernel of
+ * tp_batch_window_sweep forms v, s1 and s2.  C w0_wp and w0_wp'C w0_wp are formed once per (window, prior).  The
+ * (window, prior, length) entries then go through the batch's RUN workspace (borrowed as by tp_batch_prior_sweep_tiled, and
+ * grown to hold up to the sub-range's window x prior pairs where the arena budget allows) in groups of ONE length: a fill kernel
+ * applies T = G - v 1' - 1 v' + s2 1 1', t = g - s1 1 from left to right (a zero delta gives the bits of delta == NULL), the
+ * tiled factorisation and solve of tp_batch_run run with N = N[l], and the results are copied to their slots.
+ * Statuses are those of tp_batch_run on the large-k path: TP_STATUS_NOT_PD is a pivot that is not > 0 - there is no relative
+ * floor, so a Jeffreys length of fewer rows than columns gets whatever tp_batch_run gives a batch of that suffix -,
+ * TP_STATUS_NONFINITE and (conjugate) TP_STATUS_BAD_DENOM come from the solve.  Aux as in tp_batch_download_window_sweep.
+ * Promises.  A (window, prior, length) result depends on the rows of its own suffix, its delta, its prior, N_l and k.  It does
+ * not depend on W, n_prior, the window's position, the sub-ranges or the arena's size ("tiled_arena_mib"): bit for bit.  It
+ * depends on the OTHER lengths of the list to rounding only.  A row older than a length's suffix - NaN, Inf or an outlier -
+ * never reaches that length: its snapshot has left the registers before that row is loaded.
+ * Device memory: that of tp_batch_window_sweep plus, conjugate, (k + 1) doubles per (window, prior) of a sub-range, k + 9
+ * doubles per entry of one group, and the run workspace - which stays grown afterwards, as after tp_batch_prior_sweep_tiled;
+ * kept until tp_batch_destroy.  Streams, the entry drain, timing (kernel_ms covers every launch; one step of tp_region_steps),
+ * the gather hand-over and what the call leaves alone are as for tp_batch_prior_sweep_tiled; every other download returns what
+ * it returned before. */
+int tp_batch_window_sweep_tiled(tp_batch_t b, int32_t n_len, const int32_t* N /* [n_len] */,
+                                const int32_t* rows /* [W x n_len] */,
+                                const double* delta /* [W x n_len x n_r] or NULL */,
+                                int32_t n_prior, const double* n0 /* [W x n_prior x n_len] */,
+                                const double* w0 /* [W x n_prior x k] */);
 /* Waits for the window sweep and copies out weights [W x P x n_len x k] (P = n_prior, 1 for a Jeffreys batch), status
  * [W x P x n_len] (TP_STATUS_OK; TP_STATUS_NOT_PD: a pivot <= 0 or no larger than k 2^-52 times its diagonal element, e.g. a
  * Jeffreys length of fewer rows than columns; TP_STATUS_NONFINITE; TP_STATUS_BAD_DENOM (conjugate): n1 - w1'S1 w1 <= 0) and aux
  * [W x P x n_len x TP_AUX_STRIDE] (the slots of tp_batch_download's aux: for a Jeffreys batch 0 except slot 4, t'M^-1 t); each
- * may be NULL.  Without a window sweep before it: TP_ERR_INVALID. */
+ * may be NULL.  After tp_batch_window_sweep_tiled the statuses are those of the large-k path (no relative pivot floor).  Without
+ * a window sweep (of either kind) before it: TP_ERR_INVALID. */
 int tp_batch_download_window_sweep(tp_batch_t b, double* weights /* [W x P x n_len x k] */,
                                    int32_t* status /* [W x P x n_len] */,
                                    double* aux /* [W x P x n_len x TP_AUX_STRIDE] */);

@@ -47,7 +47,7 @@ EXPORTS = [
     "tp_batch_solve_sweep", "tp_batch_solve_sweep_tiled", "tp_batch_download_sweep", "tp_batch_download_sweep_rhs",
     "tp_batch_prior_sweep", "tp_batch_prior_sweep_tiled", "tp_batch_download_prior_sweep",
     "tp_batch_size_sweep", "tp_batch_size_sweep_tiled", "tp_batch_download_size_sweep",
-    "tp_batch_window_sweep", "tp_batch_download_window_sweep",
+    "tp_batch_window_sweep", "tp_batch_window_sweep_tiled", "tp_batch_download_window_sweep",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
     "tp_comm_count", "tp_comm_init_all", "tp_group_gather",
@@ -124,6 +124,7 @@ def _load():
     lib.tp_batch_download_size_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_window_sweep.argtypes = [c_void_p, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), c_int32,
                                           POINTER(c_double), POINTER(c_double)]
+    lib.tp_batch_window_sweep_tiled.argtypes = lib.tp_batch_window_sweep.argtypes
     lib.tp_batch_download_window_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download_S1.argtypes = [c_void_p, c_int64, POINTER(c_double)]
@@ -713,6 +714,15 @@ class Batch:
         return weights, status, aux
 
     def window_sweep(self, N, rows, n0=None, w0=None, delta=None, want_aux=True):
+        return self._window_sweep(lib.tp_batch_window_sweep, N, rows, n0, w0, delta, want_aux)
+
+    def window_sweep_tiled(self, N, rows, n0=None, w0=None, delta=None, want_aux=True):
+        """`tp_batch_window_sweep_tiled` + `tp_batch_download_window_sweep`: `window_sweep` for k > `sweep_max_assets()`, on the
+        large-k tiled pipeline - the same arguments, checks (before any device call) and results; statuses as `run` gives
+        them on the large-k path."""
+        return self._window_sweep(lib.tp_batch_window_sweep_tiled, N, rows, n0, w0, delta, want_aux)
+
+    def _window_sweep(self, call, N, rows, n0, w0, delta, want_aux):
         """`tp_batch_window_sweep` + `tp_batch_download_window_sweep`: L nested window lengths per window - length l uses the
         last `rows[w, l]` daily rows of the window as uploaded - from ONE pass over the rows.  `N` [L]: strictly increasing,
         replaces the batch's N per length; `rows` [W x L]: non-decreasing in l within [1, n_w]; `delta` [W x L x n_r] or None:
@@ -759,12 +769,12 @@ class Batch:
         rwp = rw if rw.size else np.ones(1, dtype=np.int32)
         dp = None if delta is None or not delta.size else delta
         if n0 is None:
-            self.dev._check(lib.tp_batch_window_sweep(self._b, L, _ptr(Nl, c_int32), _ptr(rwp, c_int32), _ptr(dp, c_double), 0, None, None))
+            self.dev._check(call(self._b, L, _ptr(Nl, c_int32), _ptr(rwp, c_int32), _ptr(dp, c_double), 0, None, None))
         else:
             n0p = n0 if n0.size else np.ones(1)
             w0p = w0 if w0.size else np.zeros(1)
-            self.dev._check(lib.tp_batch_window_sweep(self._b, L, _ptr(Nl, c_int32), _ptr(rwp, c_int32), _ptr(dp, c_double), P,
-                                                      _ptr(n0p, c_double), _ptr(w0p, c_double)))
+            self.dev._check(call(self._b, L, _ptr(Nl, c_int32), _ptr(rwp, c_int32), _ptr(dp, c_double), P, _ptr(n0p, c_double),
+                                 _ptr(w0p, c_double)))
         self.dev._check(lib.tp_batch_download_window_sweep(self._b, _ptr(weights if weights.size else None, c_double),
                                                            _ptr(status if status.size else None, c_int32),
                                                            _ptr(aux if aux is not None and aux.size else None, c_double)))

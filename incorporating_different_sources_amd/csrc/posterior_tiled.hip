@@ -912,6 +912,7 @@ __global__ void __launch_bounds__(NTHREADS) tile64_syrk_trsm_kernel(const tp_kar
 }
 
 #include "posterior_tiled_wave.h"
+#include "posterior_tiled_window_wave.h"
 
 size_t tp_tiled_slot_doubles(int k) {
     int KP, NS, NSB;

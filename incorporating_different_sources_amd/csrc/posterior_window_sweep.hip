@@ -29,7 +29,7 @@
 namespace {
 
 constexpr int WINDOW_WREGS = 5;         // w0 registers per lane of a 32-lane row group: k <= 32 * 5
-constexpr int DELTA_THREADS = 192;      // one thread per column: k <= 143
+constexpr int DELTA_THREADS = 192;      // one thread per column at k <= 143; a column loop above (the tiled window sweep)
 
 __global__ void __launch_bounds__(DELTA_THREADS) posterior_window_delta_kernel(const tp_window_delta_kargs_t D) {
     const tp_kargs_t& A = D.in;
@@ -38,29 +38,31 @@ __global__ void __launch_bounds__(DELTA_THREADS) posterior_window_delta_kernel(c
     const int l = (int)((long long)blockIdx.x - wl * L);
     if (wl >= A.w_count) return;
     const long long w = A.w_first + wl;
-    const int j = threadIdx.x;
-    if (j >= k) return;                                  // (no barrier below)
     const int n_w = A.n_rows ? A.n_rows[w] : A.n_r;
     const int rl = D.rows[w * L + l];
-    const long long col = A.col_idx ? (long long)A.col_idx[w * k + j] : (long long)j;
     const int* ridx = A.row_idx ? A.row_idx + w * (long long)A.n_r : nullptr;
     const long long first = A.start ? A.start[w] : 0;
     const double* sub = A.rf_adj ? A.rf_adj + w * (long long)A.n_r : nullptr;
     const double* dl = D.delta + (w * L + l) * (long long)A.n_r;
-    double v = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int r = n_w - rl; r < n_w; ++r) {
-        const long long row = ridx ? (long long)ridx[r] : first + r;
-        double x = A.panel[row * (long long)A.panel_ld + col];
-        if (sub) x -= sub[r];                            // ref:57, as the Gram pass forms the row
-        const double d = dl[r];
-        v = fma(d, x, v);
-        s1 += d;
-        s2 = fma(d, d, s2);
-    }
-    D.dv[(w * L + l) * (long long)k + j] = v;
-    if (j == 0) {
-        D.ds[(w * L + l) * 2] = s1;
-        D.ds[(w * L + l) * 2 + 1] = s2;
+    // (no barrier below) k <= DELTA_THREADS: one column per thread; above it - the tiled window sweep - a thread takes the columns
+    // j, j + DELTA_THREADS, ..., each over the same rows in the same order
+    for (int j = threadIdx.x; j < k; j += DELTA_THREADS) {
+        const long long col = A.col_idx ? (long long)A.col_idx[w * k + j] : (long long)j;
+        double v = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int r = n_w - rl; r < n_w; ++r) {
+            const long long row = ridx ? (long long)ridx[r] : first + r;
+            double x = A.panel[row * (long long)A.panel_ld + col];
+            if (sub) x -= sub[r];                            // ref:57, as the Gram pass forms the row
+            const double d = dl[r];
+            v = fma(d, x, v);
+            s1 += d;
+            s2 = fma(d, d, s2);
+        }
+        D.dv[(w * L + l) * (long long)k + j] = v;
+        if (j == 0) {
+            D.ds[(w * L + l) * 2] = s1;
+            D.ds[(w * L + l) * 2 + 1] = s2;
+        }
     }
 }
 
@@ -239,7 +241,7 @@ hipError_t tp_window_sweep_launch(const tp_window_sweep_kargs_t& a, hipStream_t 
 }
 
 hipError_t tp_window_delta_launch(const tp_window_delta_kargs_t& a, hipStream_t stream) {
-    if (a.in.k < 1 || a.in.k > DELTA_THREADS || a.L < 1 || a.in.w_count < 1) return hipErrorInvalidValue;
+    if (a.in.k < 1 || a.L < 1 || a.in.w_count < 1) return hipErrorInvalidValue;
     const long long grid = a.in.w_count * (long long)a.L;
     if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(posterior_window_delta_kernel, dim3((unsigned)grid), dim3(DELTA_THREADS), 0, stream, a);

@@ -96,6 +96,9 @@ struct WindowSweepWs {
     DevBuf N, rows;                 // the lengths' N [L] and row counts [W x L]
     DevBuf delta, dv, ds;           // the caller's row offsets [W x L x n_r]; their sums v [W x L x k] and (s1, s2) [W x L x 2]
     DevBuf weights, status, aux;
+    // tp_batch_window_sweep_tiled: C w0 [chunk x P x k] and w0'C w0 [chunk x P] of one sub-range; the results of one group of
+    // arena entries (one length) as tp_tiled_factor_launch writes them, before they go to their slots
+    DevBuf cw, cq, stage_w, stage_s, stage_a;
     int P = 0, L = 0;               // shape of the last sweep (0: none yet)
 };
 
@@ -110,7 +113,7 @@ struct tp_batch_s {
     int64_t post_w0 = 0, post_count = 0;
     SolveSweepWs sw;                                          // tp_batch_solve_sweep / _solve_sweep_tiled
     PriorSweepWs ps, zs;                                      // tp_batch_prior_sweep / _prior_sweep_tiled; tp_batch_size_sweep / _size_sweep_tiled
-    WindowSweepWs wn;                                         // tp_batch_window_sweep
+    WindowSweepWs wn;                                         // tp_batch_window_sweep / _window_sweep_tiled
     PriceStaging fe, fe_hf;                                   // daily and intraday (freed after a synchronous upload)
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)

@@ -1,6 +1,6 @@
 // tangency_sweep.cpp - the sweeps of the C-ABI of libtangency.so (include/tangency_posterior.h): many solves per window
-// from one Gram pass - tp_batch_solve_sweep, _prior_sweep, _size_sweep, the three tiled forms above tp_sweep_max_assets(), and
-// their downloads.  Every sweep is: checks, a drain of the handle's stream, its workspace (SolveSweepWs / PriorSweepWs,
+// from one Gram pass - tp_batch_solve_sweep, _prior_sweep, _size_sweep, _window_sweep, the four tiled forms above
+// tp_sweep_max_assets(), and their downloads.  Every sweep is: checks, a drain of the handle's stream, its workspace (SolveSweepWs / PriorSweepWs,
 // tangency_host.h), then per sub-range of windows a Gram stage and a solve stage inside one timed span.
 #include <cmath>
 #include <cstring>
@@ -15,6 +15,11 @@ using namespace tp_host;
 // Bound of the matrices one sub-range of windows keeps: 256 MiB, the size of the Infinity Cache (the solve kernel reads what
 // the Gram pass has just written).
 #define TP_SWEEP_WORKSPACE_BYTES (256ull << 20)
+// tp_batch_window_sweep_tiled alone: 4 GiB.  Its entries are factorised in groups of ONE length, each a chain of some 3 NS small
+// launches over the sub-range's windows x priors, so the sub-range - not the cache - decides how full the chip runs: at 256 MiB
+// (25 windows at k = 500, L = 4) the sweep took 1.6 - 3.6x the device time of one batch per length, at 4 GiB 1.3 - 2.5x less
+// (DESIGN.md section 4m).
+#define TP_WINDOW_SWEEP_TILED_WORKSPACE_BYTES (4096ull << 20)
 
 namespace {
 
@@ -48,12 +53,13 @@ int drain_for_sweep(tp_batch_t b) {
     return harvest_kernel_time(h);
 }
 
-// Windows per sub-range: the "sweep_chunk_windows" option, else as many as TP_SWEEP_WORKSPACE_BYTES hold at `bytes_per_window`
+// Windows per sub-range: the "sweep_chunk_windows" option, else as many as `budget` bytes hold at `bytes_per_window`
 // of kept matrices; never more than 2^30 (window, shift) or (window, prior) pairs per launch; within [1, W].
 // clamp_option_to_workspace = false, the plain solve sweep only: its option is documented as overriding the workspace bound
 // (tp_set_option in the header); the later sweeps honour it below the bound.
-int64_t sweep_chunk(tp_handle_t h, size_t bytes_per_window, int64_t pairs_per_window, int64_t W, bool clamp_option_to_workspace) {
-    const int64_t fit = (int64_t)(TP_SWEEP_WORKSPACE_BYTES / bytes_per_window);
+int64_t sweep_chunk(tp_handle_t h, size_t bytes_per_window, int64_t pairs_per_window, int64_t W, bool clamp_option_to_workspace,
+                    size_t budget = TP_SWEEP_WORKSPACE_BYTES) {
+    const int64_t fit = (int64_t)(budget / bytes_per_window);
     int64_t chunk = h->sweep_chunk_windows > 0 ? h->sweep_chunk_windows : fit;
     if (clamp_option_to_workspace) chunk = std::min(chunk, fit);
     chunk = std::min(chunk, ((int64_t)1 << 30) / pairs_per_window);
@@ -305,16 +311,16 @@ tp_gram_kargs_t gram_pass_kargs(tp_batch_t b, const PriorSweepWs& ws) {
 }
 
 // The two passes of the batch's tiled Gram stage that give a conjugate tiled sweep its matrices, steered by their arguments: T
-// and t into `ps` as a Jeffreys batch without centring over the daily rows, C as a Jeffreys batch centred by the window's row
+// and t (into the stores `T`, `t`) as a Jeffreys batch without centring over the daily rows, C as a Jeffreys batch centred by the window's row
 // count over the INTRADAY rows
-void tiled_conjugate_gram_kargs(tp_batch_t b, const PriorSweepWs& ps, tp_kargs_t* ta_out, tp_kargs_t* ca_out) {
+void tiled_conjugate_gram_kargs(tp_batch_t b, const DevBuf& T, const DevBuf& t, const DevBuf& C, tp_kargs_t* ta_out, tp_kargs_t* ca_out) {
     // T and t: the daily rows as a plain run reads them, uncentred and without the prior
     tp_kargs_t ta = neutral_kargs(b);
     ta.strategy = TP_STRATEGY_JEFFREYS;
     ta.center_rows = 2;
     ta.w0 = nullptr; ta.n0 = nullptr;
-    ta.out_rhs = (double*)ps.t.p;
-    ta.out_post = (double*)ps.T.p;
+    ta.out_rhs = (double*)t.p;
+    ta.out_post = (double*)T.p;
     // C: the same stage over the intraday rows - the daily-panel fields name the intraday panel (its own 32-bit offset flags:
     // make_kargs formed hf_off32 from that panel's bytes, leading dimension and m), centred by the window's row count
     tp_kargs_t ca = ta;
@@ -323,7 +329,7 @@ void tiled_conjugate_gram_kargs(tp_batch_t b, const PriorSweepWs& ps, tp_kargs_t
     ca.panel_ld = ta.hf_ld; ca.panel_off32 = ta.hf_off32;
     ca.center_rows = 1;
     ca.out_rhs = nullptr;
-    ca.out_post = (double*)ps.C.p;
+    ca.out_post = (double*)C.p;
     for (tp_kargs_t* g : {&ta, &ca}) { g->hf_panel = nullptr; g->hf_start = nullptr; g->hf_row_idx = nullptr; g->hf_count = nullptr; g->hf_off32 = 0; }
     *ta_out = ta; *ca_out = ca;
 }
@@ -334,6 +340,114 @@ int download_prior_ws(tp_batch_t b, const PriorSweepWs& ws, double* weights, int
     const size_t n = (size_t)b->W * ws.P * ws.S;
     return download(b->h, {{weights, ws.weights.p, sizeof(double) * n * b->p.k}, {status, ws.status.p, sizeof(int32_t) * n},
                            {aux, ws.aux.p, sizeof(double) * n * TP_AUX_STRIDE}});
+}
+
+// ---- window sweeps ---------------------------------------------------------------------------------------------------
+
+// What the two window sweeps share - tp_batch_window_sweep (`tiled` = false, k <= tp_sweep_max_assets()) and
+// tp_batch_window_sweep_tiled (above it): the argument checks, the k range, the drain, the checks against the windows' own row
+// counts, the windows per sub-range (L snapshots - conjugate: and C - per window), the sweep's buffers and the copies of the
+// caller's arrays.  A call refused for its arguments leaves the last sweep's shape and results in place.
+// *chunk_out = 0: W = 0, nothing to launch (the sweep's shape is set).
+int window_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_len, const int32_t* N, const int32_t* rows,
+                         const double* delta, int32_t n_prior, const double* n0, const double* w0, int64_t* chunk_out) {
+    tp_handle_t h = b->h;
+    WindowSweepWs& ws = b->wn;
+    const int k = b->p.k, n_r = b->p.n_r;
+    const int64_t W = b->W;
+    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
+    *chunk_out = 0;
+    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
+    if (n_len < 1 || n_len > TP_SWEEP_MAX_RHS)
+        return fail(h, TP_ERR_INVALID, "%s: n_len=%d outside [1, %d]", name, n_len, TP_SWEEP_MAX_RHS);
+    if (!N) return fail(h, TP_ERR_INVALID, "%s: N is NULL", name);
+    for (int l = 0; l < n_len; ++l)
+        if (N[l] < 1 || (l > 0 && N[l] <= N[l - 1]))
+            return fail(h, TP_ERR_INVALID, "%s: N[%d]=%d: strictly increasing lengths >= 1 expected", name, l, N[l]);
+    if (!rows) return fail(h, TP_ERR_INVALID, "%s: rows is NULL", name);
+    const int L = n_len;
+    const int P = conj ? n_prior : 1;
+    int rc = TP_OK;
+    if (conj) {
+        if (n_prior < 1) return fail(h, TP_ERR_INVALID, "%s: n_prior=%d < 1", name, n_prior);
+        if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "%s: %s is NULL", name, !n0 ? "n0" : "w0");
+        rc = check_finite_sign(h, name, "n0", n0, W * P * L, true);
+        if (rc != TP_OK) return rc;
+        for (int64_t i = 0; i < W * P * k; ++i)
+            if (!std::isfinite(w0[i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)i);
+    } else if (n_prior != 0 || n0 || w0) {
+        return fail(h, TP_ERR_INVALID, "%s: a Jeffreys batch takes no priors (n_prior = 0, n0 = w0 = NULL)", name);
+    }
+    rc = check_sweep_k(h, tiled, name, "tp_batch_window_sweep", k);
+    if (rc != TP_OK) return rc;
+    rc = drain_for_sweep(b);
+    if (rc != TP_OK) return rc;
+    if (W == 0) { ws.P = P; ws.L = L; return TP_OK; }      // (*chunk_out = 0: nothing to launch, the shape is set)
+    // the windows' own row counts (the device copy is the one the kernels read), then the checks that need them
+    std::vector<int32_t> nw((size_t)W, n_r);
+    if (b->n_rows.p) HIP_TRY(h, hipMemcpy(nw.data(), b->n_rows.p, sizeof(int32_t) * (size_t)W, hipMemcpyDeviceToHost));
+    for (int64_t w = 0; w < W; ++w)
+        for (int l = 0; l < L; ++l) {
+            const int32_t r = rows[w * L + l];
+            if (r < 1 || r > nw[(size_t)w] || (l > 0 && r < rows[w * L + l - 1]))
+                return fail(h, TP_ERR_INVALID, "%s: rows[%lld][%d]=%d: non-decreasing row counts within [1, %d] expected", name,
+                            (long long)w, l, r, nw[(size_t)w]);
+            if (delta) {
+                const double* d = delta + (w * L + l) * (int64_t)n_r;
+                for (int i = nw[(size_t)w] - r; i < nw[(size_t)w]; ++i)
+                    if (!std::isfinite(d[i]))
+                        return fail(h, TP_ERR_INVALID, "%s: delta[%lld][%d][%d] must be finite", name, (long long)w, l, i);
+            }
+        }
+    ws.P = 0; ws.L = 0;                                // every argument check is behind us: a refused call keeps the last results
+    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
+    const int64_t chunk = sweep_chunk(h, (size_t)(L + (conj ? 1 : 0)) * mat_bytes, (int64_t)P * L, W, true,
+                                      tiled ? TP_WINDOW_SWEEP_TILED_WORKSPACE_BYTES : TP_SWEEP_WORKSPACE_BYTES);
+    const size_t WL = (size_t)W * (size_t)L, WPL = WL * (size_t)P;
+    const std::string what = std::string(name) + ": ";
+    if (conj) rc = ensure(h, ws.C, mat_bytes * (size_t)chunk, (what + "intraday scatters of one sub-range").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.T, mat_bytes * (size_t)chunk * L, (what + "daily Gram snapshots of one sub-range").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.t, sizeof(double) * WL * k, (what + "daily column sums").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.N, sizeof(int32_t) * (size_t)L, (what + "lengths").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.rows, sizeof(int32_t) * WL, (what + "row counts").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, ws.n0, sizeof(double) * WPL, (what + "prior strengths").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, ws.w0, sizeof(double) * (size_t)W * P * k, (what + "prior weights").c_str());
+    if (rc == TP_OK && delta) rc = ensure(h, ws.delta, sizeof(double) * WL * n_r, (what + "row offsets").c_str());
+    if (rc == TP_OK && delta) rc = ensure(h, ws.dv, sizeof(double) * WL * k, (what + "offset-weighted column sums").c_str());
+    if (rc == TP_OK && delta) rc = ensure(h, ws.ds, sizeof(double) * WL * 2, (what + "offset sums").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.weights, sizeof(double) * WPL * k, (what + "weights").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.status, sizeof(int32_t) * WPL, (what + "statuses").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.aux, sizeof(double) * WPL * TP_AUX_STRIDE, (what + "aux").c_str());
+    if (rc != TP_OK) return rc;
+    // the caller's arrays: copied here, no host pointer is kept
+    HIP_TRY(h, hipMemcpyAsync(ws.N.p, N, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(ws.rows.p, rows, sizeof(int32_t) * WL, hipMemcpyHostToDevice, h->stream));
+    if (conj) {
+        HIP_TRY(h, hipMemcpyAsync(ws.n0.p, n0, sizeof(double) * WPL, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(ws.w0.p, w0, sizeof(double) * (size_t)W * P * k, hipMemcpyHostToDevice, h->stream));
+    }
+    if (delta) HIP_TRY(h, hipMemcpyAsync(ws.delta.p, delta, sizeof(double) * WL * n_r, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
+    *chunk_out = chunk;
+    return TP_OK;
+}
+
+// the segmented Gram's and the delta kernel's arguments, the same for both window sweeps
+void window_gram_delta_kargs(tp_batch_t b, int L, tp_window_gram_kargs_t* ga_out, tp_window_delta_kargs_t* da_out) {
+    const WindowSweepWs& ws = b->wn;
+    tp_window_gram_kargs_t ga;
+    memset(&ga, 0, sizeof ga);
+    ga.in = neutral_kargs(b);
+    ga.in.w0 = nullptr; ga.in.n0 = nullptr;
+    ga.C = b->p.strategy == TP_STRATEGY_CONJUGATE ? (double*)ws.C.p : nullptr;
+    ga.T = (double*)ws.T.p; ga.t = (double*)ws.t.p;
+    ga.rows = (const int*)ws.rows.p; ga.L = L;
+    tp_window_delta_kargs_t da;
+    memset(&da, 0, sizeof da);
+    da.in = ga.in;
+    da.delta = (const double*)ws.delta.p; da.rows = ga.rows;
+    da.dv = (double*)ws.dv.p; da.ds = (double*)ws.ds.p; da.L = L;
+    *ga_out = ga; *da_out = da;
 }
 
 }  // namespace
@@ -505,7 +619,7 @@ int tp_batch_prior_sweep_tiled(tp_batch_t b, int32_t n_prior, const double* n0, 
     ws.part = (double*)b->t_part.p;
 
     tp_kargs_t ta, ca;
-    tiled_conjugate_gram_kargs(b, ps, &ta, &ca);
+    tiled_conjugate_gram_kargs(b, ps.T, ps.t, ps.C, &ta, &ca);
     tp_prior_sweep_tiled_kargs_t sa;
     memset(&sa, 0, sizeof sa);
     sa.C = (const double*)ps.C.p; sa.T = (const double*)ps.T.p; sa.t = (const double*)ps.t.p;
@@ -603,7 +717,7 @@ int tp_batch_size_sweep_tiled(tp_batch_t b, int32_t n_size, const int32_t* sizes
     rc = ensure_sweep_tiled_ws(b, n_size, chunk * P, &ws, &cap, conj ? tp_size_sweep_tiled_part_doubles(b->p.k, n_size) : 0);
     if (rc != TP_OK) return rc;
     tp_kargs_t ta, ca;                                 // conjugate
-    tiled_conjugate_gram_kargs(b, zs, &ta, &ca);
+    tiled_conjugate_gram_kargs(b, zs.T, zs.t, zs.C, &ta, &ca);
     tp_kargs_t ja = neutral_kargs(b);                  // Jeffreys
     ja.out_rhs = (double*)zs.t.p; ja.out_post = (double*)zs.T.p;
     tp_size_sweep_tiled_kargs_t sa;
@@ -653,91 +767,15 @@ int tp_batch_window_sweep(tp_batch_t b, int32_t n_len, const int32_t* N, const i
     WindowSweepWs& ws = b->wn;
     const char* name = "tp_batch_window_sweep";
     const int k = b->p.k, n_r = b->p.n_r;
-    const int64_t W = b->W;
     const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
-    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
-    if (n_len < 1 || n_len > TP_SWEEP_MAX_RHS)
-        return fail(h, TP_ERR_INVALID, "%s: n_len=%d outside [1, %d]", name, n_len, TP_SWEEP_MAX_RHS);
-    if (!N) return fail(h, TP_ERR_INVALID, "%s: N is NULL", name);
-    for (int l = 0; l < n_len; ++l)
-        if (N[l] < 1 || (l > 0 && N[l] <= N[l - 1]))
-            return fail(h, TP_ERR_INVALID, "%s: N[%d]=%d: strictly increasing lengths >= 1 expected", name, l, N[l]);
-    if (!rows) return fail(h, TP_ERR_INVALID, "%s: rows is NULL", name);
     const int L = n_len;
     const int P = conj ? n_prior : 1;
-    int rc = TP_OK;
-    if (conj) {
-        if (n_prior < 1) return fail(h, TP_ERR_INVALID, "%s: n_prior=%d < 1", name, n_prior);
-        if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "%s: %s is NULL", name, !n0 ? "n0" : "w0");
-        rc = check_finite_sign(h, name, "n0", n0, W * P * L, true);
-        if (rc != TP_OK) return rc;
-        for (int64_t i = 0; i < W * P * k; ++i)
-            if (!std::isfinite(w0[i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)i);
-    } else if (n_prior != 0 || n0 || w0) {
-        return fail(h, TP_ERR_INVALID, "%s: a Jeffreys batch takes no priors (n_prior = 0, n0 = w0 = NULL)", name);
-    }
-    rc = check_sweep_k(h, false, name, name, k);
-    if (rc != TP_OK) return rc;
-    rc = drain_for_sweep(b);
-    if (rc != TP_OK) return rc;
-    if (W == 0) { ws.P = P; ws.L = L; return TP_OK; }
-    // the windows' own row counts (the device copy is the one the kernels read), then the checks that need them
-    std::vector<int32_t> nw((size_t)W, n_r);
-    if (b->n_rows.p) HIP_TRY(h, hipMemcpy(nw.data(), b->n_rows.p, sizeof(int32_t) * (size_t)W, hipMemcpyDeviceToHost));
-    for (int64_t w = 0; w < W; ++w)
-        for (int l = 0; l < L; ++l) {
-            const int32_t r = rows[w * L + l];
-            if (r < 1 || r > nw[(size_t)w] || (l > 0 && r < rows[w * L + l - 1]))
-                return fail(h, TP_ERR_INVALID, "%s: rows[%lld][%d]=%d: non-decreasing row counts within [1, %d] expected", name,
-                            (long long)w, l, r, nw[(size_t)w]);
-            if (delta) {
-                const double* d = delta + (w * L + l) * (int64_t)n_r;
-                for (int i = nw[(size_t)w] - r; i < nw[(size_t)w]; ++i)
-                    if (!std::isfinite(d[i]))
-                        return fail(h, TP_ERR_INVALID, "%s: delta[%lld][%d][%d] must be finite", name, (long long)w, l, i);
-            }
-        }
-    ws.P = 0; ws.L = 0;                                // every argument check is behind us: a refused call keeps the last results
-    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
-    const int64_t chunk = sweep_chunk(h, (size_t)(L + (conj ? 1 : 0)) * mat_bytes, (int64_t)P * L, W, true);
-    const size_t WL = (size_t)W * (size_t)L, WPL = WL * (size_t)P;
-    const std::string what = std::string(name) + ": ";
-    if (conj) rc = ensure(h, ws.C, mat_bytes * (size_t)chunk, (what + "intraday scatters of one sub-range").c_str());
-    if (rc == TP_OK) rc = ensure(h, ws.T, mat_bytes * (size_t)chunk * L, (what + "daily Gram snapshots of one sub-range").c_str());
-    if (rc == TP_OK) rc = ensure(h, ws.t, sizeof(double) * WL * k, (what + "daily column sums").c_str());
-    if (rc == TP_OK) rc = ensure(h, ws.N, sizeof(int32_t) * (size_t)L, (what + "lengths").c_str());
-    if (rc == TP_OK) rc = ensure(h, ws.rows, sizeof(int32_t) * WL, (what + "row counts").c_str());
-    if (rc == TP_OK && conj) rc = ensure(h, ws.n0, sizeof(double) * WPL, (what + "prior strengths").c_str());
-    if (rc == TP_OK && conj) rc = ensure(h, ws.w0, sizeof(double) * (size_t)W * P * k, (what + "prior weights").c_str());
-    if (rc == TP_OK && delta) rc = ensure(h, ws.delta, sizeof(double) * WL * n_r, (what + "row offsets").c_str());
-    if (rc == TP_OK && delta) rc = ensure(h, ws.dv, sizeof(double) * WL * k, (what + "offset-weighted column sums").c_str());
-    if (rc == TP_OK && delta) rc = ensure(h, ws.ds, sizeof(double) * WL * 2, (what + "offset sums").c_str());
-    if (rc == TP_OK) rc = ensure(h, ws.weights, sizeof(double) * WPL * k, (what + "weights").c_str());
-    if (rc == TP_OK) rc = ensure(h, ws.status, sizeof(int32_t) * WPL, (what + "statuses").c_str());
-    if (rc == TP_OK) rc = ensure(h, ws.aux, sizeof(double) * WPL * TP_AUX_STRIDE, (what + "aux").c_str());
-    if (rc != TP_OK) return rc;
-    // the caller's arrays: copied here, no host pointer is kept
-    HIP_TRY(h, hipMemcpyAsync(ws.N.p, N, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(ws.rows.p, rows, sizeof(int32_t) * WL, hipMemcpyHostToDevice, h->stream));
-    if (conj) {
-        HIP_TRY(h, hipMemcpyAsync(ws.n0.p, n0, sizeof(double) * WPL, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(ws.w0.p, w0, sizeof(double) * (size_t)W * P * k, hipMemcpyHostToDevice, h->stream));
-    }
-    if (delta) HIP_TRY(h, hipMemcpyAsync(ws.delta.p, delta, sizeof(double) * WL * n_r, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
-
+    int64_t chunk = 0;
+    const int rc = window_sweep_prepare(b, name, false, n_len, N, rows, delta, n_prior, n0, w0, &chunk);
+    if (rc != TP_OK || chunk == 0) return rc;
     tp_window_gram_kargs_t ga;
-    memset(&ga, 0, sizeof ga);
-    ga.in = neutral_kargs(b);
-    ga.in.w0 = nullptr; ga.in.n0 = nullptr;
-    ga.C = conj ? (double*)ws.C.p : nullptr;
-    ga.T = (double*)ws.T.p; ga.t = (double*)ws.t.p;
-    ga.rows = (const int*)ws.rows.p; ga.L = L;
     tp_window_delta_kargs_t da;
-    memset(&da, 0, sizeof da);
-    da.in = ga.in;
-    da.delta = (const double*)ws.delta.p; da.rows = ga.rows;
-    da.dv = (double*)ws.dv.p; da.ds = (double*)ws.ds.p; da.L = L;
+    window_gram_delta_kargs(b, L, &ga, &da);
     tp_window_sweep_kargs_t sa;
     memset(&sa, 0, sizeof sa);
     sa.C = conj ? (const double*)ws.C.p : nullptr;
@@ -764,6 +802,101 @@ int tp_batch_window_sweep(tp_batch_t b, int32_t n_len, const int32_t* N, const i
         sa.w_first = wf; sa.w_count = n;
         return launched(h, tp_window_sweep_launch(sa, h->stream), "window sweep kernel");
     }, [&] { ws.P = P; ws.L = L; });
+}
+
+// Window sweep above tp_sweep_max_assets(), on the large-k tiled pipeline.  Per sub-range: conjugate, the batch's own tiled Gram
+// stage over the INTRADAY rows, steered by its arguments as for tp_batch_prior_sweep_tiled, leaves the raw-moment-centred C in
+// wn.C (once per window, not once per length); the segmented one-wave Gram (posterior_tiled_window_wave.h) stores the snapshots
+// T_l, t_l of every length from ONE pass over the daily rows; the delta kernel - with a delta only - forms the sums of the
+// rank-two correction.  Then the sub-range's (window, prior, length) entries go through the batch's run workspace - borrowed,
+// and grown to hold them - in groups of ONE length and at most tiled_capacity entries: posterior_window_sweep_tiled.hip fills
+// them, tp_tiled_factor_launch factorises and solves them with N = N[l] into staging rows, and the scatter kernel puts those
+// into the sweep's result slots.
+int tp_batch_window_sweep_tiled(tp_batch_t b, int32_t n_len, const int32_t* N, const int32_t* rows, const double* delta,
+                                int32_t n_prior, const double* n0, const double* w0) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    WindowSweepWs& wn = b->wn;
+    const char* name = "tp_batch_window_sweep_tiled";
+    const int k = b->p.k;
+    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
+    const int L = n_len;
+    const int P = conj ? n_prior : 1;
+    int64_t chunk = 0;
+    int rc = window_sweep_prepare(b, name, true, n_len, N, rows, delta, n_prior, n0, w0, &chunk);
+    if (rc != TP_OK || chunk == 0) return rc;
+    // the batch's own tiled workspace: the Gram stage of C, then the entries; staging rows for one group of entries
+    tp_tiled_ws_t ws;
+    rc = ensure_tiled_ws(b, &ws, chunk * P);
+    if (rc != TP_OK) return rc;
+    const int64_t cap = b->tiled_capacity;
+    const int64_t gmax = std::min<int64_t>(cap, chunk * P);
+    const std::string what = std::string(name) + ": ";
+    rc = ensure(h, wn.stage_w, sizeof(double) * (size_t)gmax * k, (what + "weights of one group of entries").c_str());
+    if (rc == TP_OK) rc = ensure(h, wn.stage_s, sizeof(int32_t) * (size_t)gmax, (what + "statuses of one group of entries").c_str());
+    if (rc == TP_OK) rc = ensure(h, wn.stage_a, sizeof(double) * (size_t)gmax * TP_AUX_STRIDE, (what + "aux of one group of entries").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, wn.cw, sizeof(double) * (size_t)chunk * P * k, (what + "prior products of one sub-range").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, wn.cq, sizeof(double) * (size_t)chunk * P, (what + "prior quadratic forms of one sub-range").c_str());
+    if (rc != TP_OK) return rc;
+
+    tp_kargs_t ta, ca;                                 // conjugate: `ca`, the pass over the intraday rows, alone (T_l, t_l: the segmented Gram)
+    tiled_conjugate_gram_kargs(b, wn.T, wn.t, wn.C, &ta, &ca);
+    (void)ta;
+    tp_window_gram_kargs_t ga;
+    tp_window_delta_kargs_t da;
+    window_gram_delta_kargs(b, L, &ga, &da);
+    tp_window_sweep_tiled_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.C = conj ? (const double*)wn.C.p : nullptr;
+    sa.T = (const double*)wn.T.p; sa.t = (const double*)wn.t.p;
+    sa.dv = delta ? (const double*)wn.dv.p : nullptr; sa.ds = delta ? (const double*)wn.ds.p : nullptr;
+    sa.n0 = conj ? (const double*)wn.n0.p : nullptr; sa.w0 = conj ? (const double*)wn.w0.p : nullptr;
+    sa.hf_count = (const int*)b->hf_count.p;
+    sa.rows = ga.rows;
+    sa.cw = (double*)wn.cw.p; sa.cq = (double*)wn.cq.p;
+    sa.stage_w = (const double*)wn.stage_w.p; sa.stage_s = (const int*)wn.stage_s.p; sa.stage_a = (const double*)wn.stage_a.p;
+    sa.weights = (double*)wn.weights.p; sa.status = (int*)wn.status.p; sa.aux = (double*)wn.aux.p;
+    sa.k = k; sa.P = P; sa.L = L; sa.m = b->p.m; sa.center_rows = ga.in.center_rows;
+    // factorisation and solve of one group of entries: a "batch" of (window, prior) pairs at ONE length, N = N[l], writing the
+    // staging rows (entry e -> row e); n0 travels through ws.scal
+    tp_kargs_t fa;
+    memset(&fa, 0, sizeof fa);
+    fa.strategy = b->p.strategy;
+    fa.k = k; fa.n_r = b->p.n_r; fa.m = b->p.m; fa.gamma = b->p.gamma;
+    fa.opts = h->opts;
+    fa.weights = (double*)wn.stage_w.p; fa.status = (int*)wn.stage_s.p; fa.aux = (double*)wn.stage_a.p;
+    fa.dbg_w = -1;
+    return run_sweep(b, chunk, [&](int64_t wf, int64_t n) {
+        int rcg = conj ? tiled_gram_stage(b, "tiled window sweep Gram", {&ca}, ws, cap, wf, n) : TP_OK;
+        if (rcg != TP_OK) return rcg;
+        ga.in.w_first = wf; ga.in.w_count = n;
+        rcg = launched(h, tp_tiled_window_gram_launch(ga, h->stream), "tiled window sweep segmented Gram");
+        if (rcg == TP_OK && delta) {
+            da.in.w_first = wf; da.in.w_count = n;
+            rcg = launched(h, tp_window_delta_launch(da, h->stream), "window sweep delta kernel");
+        }
+        if (rcg != TP_OK) return rcg;
+        sa.wc_first = wf;
+        if (conj) {
+            sa.l = 0; sa.wp_first = wf * P; sa.e_count = n * P;
+            rcg = launched(h, tp_window_sweep_tiled_cw_launch(sa, h->stream), "tiled window sweep prior products");
+            if (rcg != TP_OK) return rcg;
+        }
+        for (int l = 0; l < L; ++l) {
+            sa.l = l; sa.N = N[l];
+            fa.N = N[l];
+            const int rcl = in_groups(n * P, cap, [&](int64_t e0, int64_t ne) {
+                sa.wp_first = wf * P + e0; sa.e_count = ne;
+                int rce = launched(h, tp_window_sweep_tiled_fill_launch(sa, ws, h->stream), "tiled window sweep fill");
+                fa.w_first = 0; fa.w_count = ne;
+                if (rce == TP_OK) rce = launched(h, tp_tiled_factor_launch(fa, ws, h->stream), "tiled window sweep factor");
+                if (rce == TP_OK) rce = launched(h, tp_window_sweep_tiled_scatter_launch(sa, h->stream), "tiled window sweep scatter");
+                return rce;
+            });
+            if (rcl != TP_OK) return rcl;
+        }
+        return TP_OK;
+    }, [&] { wn.P = P; wn.L = L; });
 }
 
 int tp_batch_download_window_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux) {

@@ -1094,6 +1094,12 @@ def calculate_weights_for_sizes(trading_dates, portfolio_specs_list, market_data
     return out
 
 
+# `calculate_weights_for_windows` with a size above `_native.sweep_max_assets()`: True packs once at the longest window and
+# takes one tiled window sweep (`Batch.window_sweep_tiled`) instead of one `_weights_for_dates` per spec.  Off: DESIGN.md
+# section 4m holds the timings a later change decides the default from.
+WINDOW_SWEEP_TILED = False
+
+
 def _window_family(portfolio_spec):
     """Specs with equal (rebalancing frequency, size, window frequency) see the same universe candidates at a date;
     `rolling_window` picks a tail of the longest window's rows."""
@@ -1108,7 +1114,8 @@ def calculate_weights_for_windows(trading_dates, portfolio_specs_list, market_da
     Jeffreys specs only, of one (rebalancing frequency, size, window frequency) family.  (date, length) pairs the pack cannot
     serve (its mask), a pack that raises, more than `_native.SWEEP_MAX_RHS` lengths and sizes above
     `_native.sweep_max_assets()` go through `_weights_for_dates` spec by spec, so the reference's exceptions surface where the
-    reference raises them.
+    reference raises them - unless WINDOW_SWEEP_TILED is set: then a size above that bound is packed the same way and swept
+    with `Batch.window_sweep_tiled`.
     Returns one (weights, labels, cols, caps) per spec - equal to `_weights_for_dates` spec by spec within the solve's rounding -
     and remembers the conjugate ones in the cache slots `calculate_weights_for_specs` fills.
     Opt-in: nothing calls it by default."""
@@ -1127,7 +1134,8 @@ def calculate_weights_for_windows(trading_dates, portfolio_specs_list, market_da
     same_gamma = all(g == gammas[0] for g in gammas)
     windows = sorted({int(sp["rolling_window"]) for sp in specs})
     packed = None
-    if k <= _native.sweep_max_assets() and len(windows) <= _native.SWEEP_MAX_RHS:
+    tiled = bool(WINDOW_SWEEP_TILED and k > _native.sweep_max_assets())
+    if (tiled or k <= _native.sweep_max_assets()) and len(windows) <= _native.SWEEP_MAX_RHS:
         try:
             packed = batch.pack_windows_lengths(trading_dates, specs[0], windows, market_data, members_of=members_of)
         except (ValueError, AssertionError) as exc:      # the specs decide one by one what the caller sees
@@ -1150,7 +1158,8 @@ def calculate_weights_for_windows(trading_dates, portfolio_specs_list, market_da
                           gammas[0] if same_gamma else 1.0, n_dates, kw.get("m") or 0)
         try:
             b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m")})
-            weights, status, _ = b.window_sweep(windows, rows, n0, w0, delta=delta if delta.any() else None, want_aux=False)
+            weights, status, _ = (b.window_sweep_tiled if tiled else b.window_sweep)(
+                windows, rows, n0, w0, delta=delta if delta.any() else None, want_aux=False)
         finally:
             b.close()
         swept = (weights, status, labels, kw["col_idx"], caps, mask, prior_keys)
