@@ -18,11 +18,11 @@
 //                                    (rows of I from the columns of J and, I < J, rows of J from the columns of I)
 //   size_sweep_tiled_border_kernel   conjugate, one workgroup per (entry, size): v_s from the pieces of the ceil(k_s/64)
 //                                    column blocks in their order, q0_s, c_s, c_s a v_s + t into rows < k_s of column k + s
-//   size_sweep_tiled_solve_kernel    one workgroup per entry, sizes in groups of up to 4 (solve_sweep_tiled_solve_kernel's
-//                                    scheme): q1_s, blocked back substitution over block rows ceil(k_s/64)-1 .. 0 with the dot
-//                                    products cut at column k_s and, in the last block, the leading p = k_s - 64 Jb rows and
-//                                    columns of the stored inverse block (the leading block of a triangular inverse is the
-//                                    inverse of the leading block); rescale, aux, status
+//   size_sweep_tiled_solve_kernel    one workgroup per entry, sizes in groups of up to 4: q1_s, the blocked back substitution
+//                                    of the prefix systems (back_substitute<G, true>), rescale, aux, status
+//
+// The grid decode, the conjugate scalars, the tile products, the piece sums, the back substitution with its group dispatch and
+// LDS size, and the pivot floor are posterior_tiled_sweep_prims.h's.
 //
 // Whatever lies at or beyond a prefix is excluded by a SELECT, never by a multiplication with zero: w0 and C beyond k_s, the
 // factor's columns >= k_s and the inverse block's entries at or beyond p (which may be Inf or NaN) do not reach size s through
@@ -40,21 +40,16 @@
 // Plain C++, workgroup barriers only, each reached by every thread of its workgroup.  A (window, prior, size) result depends on
 // the window's matrices, on its own prior and on k, k_s and the workspace's geometry alone: every sum below runs in an order
 // fixed by k and k_s, and a size's arithmetic does not depend on which other sizes share its group.
-#include "posterior_device_prims.h"
+#include "posterior_tiled_sweep_prims.h"
 #include "posterior_size_sweep_tiled.h"
 
 namespace {
 
-constexpr int SB = 64;
-constexpr int NTHREADS = 256;
-constexpr int NG = 4;                          // sizes per group of the back substitution
 constexpr int MAXS = TP_SWEEP_KMAX_RHS;        // sizes per sweep
 
-// a = n0 m/(m-1) of the flat (window, prior) index f (ref:333, as the run kernels form it)
-__device__ __forceinline__ double prior_scale(const tp_size_sweep_tiled_kargs_t& A, const long long f) {
-    const long long w = f / A.P;
-    const double mm = (double)(A.hf_count != nullptr ? A.hf_count[w] : A.m);
-    return A.n0[f] * (mm / (mm - 1.0));
+// a = n0 m/(m-1) of the flat (window, prior) index f
+__device__ __forceinline__ double entry_scale(const tp_size_sweep_tiled_kargs_t& A, const long long f) {
+    return prior_scale(A.n0[f], hf_rows(A, f / A.P));
 }
 
 template <bool CONJ>
@@ -63,24 +58,15 @@ __global__ void __launch_bounds__(NTHREADS) size_sweep_tiled_fill_kernel(const t
     __shared__ double wI[CONJ ? MAXS : 1][SB], wJ[CONJ ? MAXS : 1][SB];     // w0_s of the tile's rows / columns (zero beyond k_s)
     const int tid = threadIdx.x;
     const int k = A.k, S = A.S, KP = ws.KP, NS = ws.NS, NSB = ws.NSB;
-    const int NT = NS * (NS + 1) / 2;
-    // The tiled path's grid decode (workgroup id -> XCD = id % 8, slot = id / 8; tiles of an entry consecutive on one XCD),
-    // with the entries dealt to the XCDs in eight contiguous runs: the P entries of a window follow each other on ONE XCD,
-    // whose L2 then serves their reads of the window's C and T.
-    const long long id = blockIdx.x;
-    const long long slot = id >> 3;
-    const long long per_xcd = (A.e_count + 7) / 8;
-    const long long e = (id & 7) * per_xcd + slot / NT;
-    if (e >= A.e_count) return;                 // (uniform per workgroup, in front of every barrier)
-    const int tile = (int)(slot % NT);
+    long long e;
     int I, J;
-    pair_decode(tile, NS, I, J);
+    if (!xcd_entry_tile(NS, A.e_count, e, I, J)) return;
     const long long f = A.e_first + e;         // flat (window, prior) index
     const long long w = f / A.P;
     const long long wl = w - A.wc_first;
     const double* __restrict__ T = A.T + wl * (long long)k * k;
     const double* __restrict__ C = CONJ ? A.C + wl * (long long)k * k : nullptr;
-    const double ap = CONJ ? prior_scale(A, f) : 0.0;
+    const double ap = CONJ ? entry_scale(A, f) : 0.0;
     double* M = ws.arena + e * (long long)KP * KP;
     const int c = tid & (SB - 1), q = tid >> 6;
     const int gj = SB * J + c;                  // < KP
@@ -101,7 +87,7 @@ __global__ void __launch_bounds__(NTHREADS) size_sweep_tiled_fill_kernel(const t
         }
         M[(long long)gi * KP + gj] = v;
     }
-    if (tile == 0 && tid == 0) ws.flags[e] = 0;
+    if (J == 0 && tid == 0) ws.flags[e] = 0;       // (super-tile (0, 0))
     if constexpr (CONJ) {
         const double* __restrict__ w0 = A.w0 + f * (long long)S * k;
         for (int x = tid; x < 2 * SB * S; x += NTHREADS) {
@@ -113,57 +99,37 @@ __global__ void __launch_bounds__(NTHREADS) size_sweep_tiled_fill_kernel(const t
         }
         __syncthreads();
         // wavefront q takes sizes q, q + 4, ...; lane c: row c's product with the columns' w0_s and column c's with the rows'.
-        // Terms at or beyond k_s are selected out, not multiplied by zero.  Four 16-term partial sums, met in a fixed order.
+        // Terms at or beyond k_s are selected out, not multiplied by zero (tile_products16<true>).
         double* part = ws.part + e * (long long)S * NSB * NSB * SB;
         for (int s = q; s < S; s += NTHREADS / SB) {
             const int ks = A.sizes[s];
             if (SB * J >= ks) continue;         // (no barrier below) the tile lies outside the prefix: the border reads none of it
             double pr[4], pc[4];
 #pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                double sr = 0.0, sc = 0.0;
-#pragma unroll
-                for (int i = 16 * h; i < 16 * h + 16; ++i) {
-                    sr = SB * J + i < ks ? fma(tc[c][i], wJ[s][i], sr) : sr;
-                    sc = SB * I + i < ks ? fma(tc[i][c], wI[s][i], sc) : sc;
-                }
-                pr[h] = sr; pc[h] = sc;
-            }
-            part[(((long long)s * NSB + I) * NSB + J) * SB + c] = ((pr[0] + pr[1]) + pr[2]) + pr[3];
-            if (I < J) part[(((long long)s * NSB + J) * NSB + I) * SB + c] = ((pc[0] + pc[1]) + pc[2]) + pc[3];
+            for (int h = 0; h < 4; ++h) tile_products16<true>(tc, wI[s], wJ[s], c, h, I, J, ks, pr[h], pc[h]);
+            part[(((long long)s * NSB + I) * NSB + J) * SB + c] = sum4(pr);
+            if (I < J) part[(((long long)s * NSB + J) * NSB + I) * SB + c] = sum4(pc);
         }
     }
 }
 
 __global__ void __launch_bounds__(NTHREADS) size_sweep_tiled_border_kernel(const tp_size_sweep_tiled_kargs_t A, const tp_tiled_ws_t ws) {
-    __shared__ double red[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const int k = A.k, S = A.S, KP = ws.KP, NSB = ws.NSB;
     const long long e = blockIdx.x / S;
     const int s = (int)(blockIdx.x - e * S);
     const long long f = A.e_first + e;
     const long long w = f / A.P;
     const int ks = A.sizes[s];
-    const int nb = (ks + SB - 1) / SB;
     const double* __restrict__ w0 = A.w0 + (f * S + s) * (long long)k;
     const double* part = ws.part + ((e * S + s) * (long long)NSB * NSB) * SB;
     double* col = ws.arena + e * (long long)KP * KP + (k + s);
-    double qq = 0.0;
-    for (int i = tid; i < ks; i += NTHREADS) {
-        const double* pp = part + ((long long)(i >> 6) * NSB) * SB + (i & 63);
-        double v = 0.0;
-        for (int src = 0; src < nb; ++src) v += pp[src * SB];
-        col[(long long)i * KP] = v;             // (rewritten below by the thread that wrote it)
-        qq = fma(w0[i], v, qq);
-    }
-    qq = wave_sum64(qq);
-    if (lane == 0) red[wv] = qq;
-    __syncthreads();
+    // v_s into the column (rewritten below by the thread that wrote it) from the ceil(k_s/64) column blocks' pieces
+    const double wv = pieces_dot(part, NSB, (ks + SB - 1) / SB, ks, w0, col, KP);
     const double n0 = A.n0[f];
-    const double ap = prior_scale(A, f);
-    const double q0 = ap * (((red[0] + red[1]) + red[2]) + red[3]);
-    const double g = n0 + ks + 2;
-    const double cc = (2 * n0) / (g + sqrt(g * g + 4 * n0 * q0));       // ref:415-418
+    const double ap = entry_scale(A, f);
+    const double q0 = ap * wv;
+    const double cc = shrink_c(n0, ks, q0);
     const double ca = cc * ap;
     for (int i = tid; i < ks; i += NTHREADS) col[(long long)i * KP] = fma(ca, col[(long long)i * KP], A.t[w * k + i]);
     if (tid == 0) {
@@ -183,7 +149,6 @@ __device__ __forceinline__ void solve_group(const tp_size_sweep_tiled_kargs_t& A
     int ks[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) ks[g] = A.sizes[g0 + g];
-    const int kmax = ks[G - 1];                    // (the sizes increase)
     if (tid < G) { lowm[tid] = 0; badm[tid] = 0; }
     // q1_s = y'y over the prefix, y = the forward-substituted column
 #pragma unroll
@@ -194,59 +159,10 @@ __device__ __forceinline__ void solve_group(const tp_size_sweep_tiled_kargs_t& A
         if (lane == 0) qs[g][wv] = qv;
     }
     __syncthreads();
-    const int srow = tid >> 4, cb = tid & 15;      // 16 lanes per row, 16 rows per pass
-    for (int Jb = (kmax + SB - 1) / SB - 1; Jb >= 0; --Jb) {
-        int np[G];                                  // rows of the block inside the member's prefix (<= 0: the member rests)
-#pragma unroll
-        for (int g = 0; g < G; ++g) np[g] = ks[g] - 64 * Jb < SB ? ks[g] - 64 * Jb : SB;
-        const int npmax = np[G - 1];
-        // z = y_Jb - sum_{64 (Jb+1) <= c < k_s} R[row][c] w[c]
-        for (int ps = 0; ps < 4; ++ps) {
-            const int i = 16 * ps + srow;                 // local row
-            const long long gi = 64 * Jb + i;
-            double s[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) s[g] = 0.0;
-            if (i < npmax)
-                for (int c = 64 * (Jb + 1) + cb; c < kmax; c += 16) {
-                    const double m = M[gi * KP + c];
-#pragma unroll
-                    for (int g = 0; g < G; ++g) s[g] = c < ks[g] ? fma(m, wvec[g * KP + c], s[g]) : s[g];
-                }
-#pragma unroll
-            for (int g = 0; g < G; ++g) s[g] = rowgroup_sum16(s[g]);
-            if (cb == 0) {
-#pragma unroll
-                for (int g = 0; g < G; ++g) zv[g * SB + i] = (i < np[g]) ? M[gi * KP + k + g0 + g] - s[g] : 0.0;
-            }
-        }
-        __syncthreads();
-        // w_Jb = R_jj^-1 z over the leading np rows and columns of the inverse block
-        const double* rinv = ws.rinv + (e * NSB + Jb) * (long long)(SB * SB);
-        for (int ps = 0; ps < 4; ++ps) {
-            const int i = 16 * ps + srow;
-            double s[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) s[g] = 0.0;
-            if (i < npmax)
-                for (int c = cb; c < SB; c += 16) {
-                    const double rv = rinv[i * SB + c];
-#pragma unroll
-                    for (int g = 0; g < G; ++g) s[g] = c < np[g] ? fma(rv, zv[g * SB + c], s[g]) : s[g];
-                }
-#pragma unroll
-            for (int g = 0; g < G; ++g) s[g] = rowgroup_sum16(s[g]);
-            if (cb == 0) {
-#pragma unroll
-                for (int g = 0; g < G; ++g)
-                    if (i < np[g]) wvec[g * KP + 64 * Jb + i] = s[g];
-            }
-        }
-        __syncthreads();
-    }
+    back_substitute<G, true>(M, KP, k, NSB, k + g0, ws.rinv, e * NSB, ks, wvec, zv);
     // the floor of the pivots inside the prefix, the rescale and the weights
     const double n0 = CONJ ? A.n0[f] : 0.0;
-    const double ap = CONJ ? prior_scale(A, f) : 0.0;
+    const double ap = CONJ ? entry_scale(A, f) : 0.0;
     const double n1 = n0 + (double)A.N;
     const double inv_gamma = 1.0 / A.gamma;
     const long long wl = f / A.P - A.wc_first;
@@ -256,16 +172,13 @@ __device__ __forceinline__ void solve_group(const tp_size_sweep_tiled_kargs_t& A
     double denom[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-        const double q1 = ((qs[g][0] + qs[g][1]) + qs[g][2]) + qs[g][3];
+        const double q1 = sum4(qs[g]);
         denom[g] = n1 - q1;
-        const double rel = (double)ks[g] * 0x1p-52;
-        bool low = false, bad = false;
-        for (int i = tid; i < ks[g]; i += NTHREADS) {
-            const double ri = rinv0[(long long)(i >> 6) * (SB * SB) + (i & 63) * (SB + 1)];
+        bool bad = false;
+        const bool low = low_pivot(rinv0, ks[g], [&](const int i) {
             const long long ii = (long long)i * k + i;
-            const double mii = CONJ ? fma(ap, C[ii], T[ii]) : T[ii];
-            if (!(1.0 > rel * mii * (ri * ri))) low = true;        // d_i <= k_s 2^-52 M_ii (a NaN ends here too)
-        }
+            return CONJ ? fma(ap, C[ii], T[ii]) : T[ii];
+        });
         double* out = A.weights + ((f * S + g0 + g) * (long long)k);
         for (int i = tid; i < k; i += NTHREADS) {
             double v = 0.0;                                          // exact zeros beyond the prefix
@@ -282,7 +195,7 @@ __device__ __forceinline__ void solve_group(const tp_size_sweep_tiled_kargs_t& A
     __syncthreads();
     if (tid < G) {
         const int g = tid;
-        const double q1 = ((qs[g][0] + qs[g][1]) + qs[g][2]) + qs[g][3];
+        const double q1 = sum4(qs[g]);
         const double den = n1 - q1;
         int st = TP_KSTATUS_OK;
         if (lowm[g]) st = TP_KSTATUS_NOT_PD;
@@ -306,13 +219,7 @@ __global__ void __launch_bounds__(NTHREADS) size_sweep_tiled_solve_kernel(const 
     const int S = A.S;
     double* wvec = sm;
     double* zv = sm + (S < NG ? S : NG) * ws.KP;
-    for (int g0 = 0; g0 < S; g0 += NG) {           // (uniform: every thread reaches every barrier of every group)
-        const int g = S - g0 < NG ? S - g0 : NG;
-        if (g == 4) solve_group<4, CONJ>(A, ws, e, g0, wvec, zv, qs, lowm, badm);
-        else if (g == 3) solve_group<3, CONJ>(A, ws, e, g0, wvec, zv, qs, lowm, badm);
-        else if (g == 2) solve_group<2, CONJ>(A, ws, e, g0, wvec, zv, qs, lowm, badm);
-        else solve_group<1, CONJ>(A, ws, e, g0, wvec, zv, qs, lowm, badm);
-    }
+    for_each_group(S, [&](auto G, const int g0) { solve_group<decltype(G)::value, CONJ>(A, ws, e, g0, wvec, zv, qs, lowm, badm); });
 }
 
 bool args_fit(const tp_size_sweep_tiled_kargs_t& a, const tp_tiled_ws_t& ws) {
@@ -330,29 +237,26 @@ size_t tp_size_sweep_tiled_part_doubles(int k, int S) {
 
 hipError_t tp_size_sweep_tiled_fill_launch(const tp_size_sweep_tiled_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream) {
     if (!args_fit(a, ws)) return hipErrorInvalidValue;
-    const long long NT = (long long)ws.NS * (ws.NS + 1) / 2;
-    const long long grid = ((a.e_count + 7) / 8) * 8 * NT;
+    const dim3 grid = xcd_entry_grid(ws.NS, a.e_count);
     if (a.C != nullptr) {
-        hipLaunchKernelGGL(size_sweep_tiled_fill_kernel<true>, dim3((unsigned)grid), dim3(NTHREADS), 0, stream, a, ws);
+        hipLaunchKernelGGL(size_sweep_tiled_fill_kernel<true>, grid, dim3(NTHREADS), 0, stream, a, ws);
         hipLaunchKernelGGL(size_sweep_tiled_border_kernel, dim3((unsigned)(a.e_count * a.S)), dim3(NTHREADS), 0, stream, a, ws);
     } else {
-        hipLaunchKernelGGL(size_sweep_tiled_fill_kernel<false>, dim3((unsigned)grid), dim3(NTHREADS), 0, stream, a, ws);
+        hipLaunchKernelGGL(size_sweep_tiled_fill_kernel<false>, grid, dim3(NTHREADS), 0, stream, a, ws);
     }
     return hipGetLastError();
 }
 
 hipError_t tp_size_sweep_tiled_solve_launch(const tp_size_sweep_tiled_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream) {
     if (!args_fit(a, ws)) return hipErrorInvalidValue;
-    const int max_lds = (int)(sizeof(double) * (size_t)(NG * SB * 32 + NG * SB));       // KP <= 2048
-    const size_t smem = sizeof(double) * ((size_t)(a.S < NG ? a.S : NG) * ws.KP + NG * SB);
-    if (smem > (size_t)max_lds) return hipErrorInvalidValue;
+    size_t smem;
     static std::atomic<unsigned long long> attr_done[2];      // one bit per device (tp_allow_dynamic_lds), one word per kernel
     if (a.C != nullptr) {
-        const hipError_t e = tp_allow_dynamic_lds(attr_done[0], size_sweep_tiled_solve_kernel<true>, max_lds);
+        const hipError_t e = group_solve_lds(attr_done[0], size_sweep_tiled_solve_kernel<true>, a.S, ws.KP, &smem);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(size_sweep_tiled_solve_kernel<true>, dim3((unsigned)a.e_count), dim3(NTHREADS), smem, stream, a, ws);
     } else {
-        const hipError_t e = tp_allow_dynamic_lds(attr_done[1], size_sweep_tiled_solve_kernel<false>, max_lds);
+        const hipError_t e = group_solve_lds(attr_done[1], size_sweep_tiled_solve_kernel<false>, a.S, ws.KP, &smem);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(size_sweep_tiled_solve_kernel<false>, dim3((unsigned)a.e_count), dim3(NTHREADS), smem, stream, a, ws);
     }

@@ -10,37 +10,27 @@
 //
 //   solve_sweep_tiled_fill_kernel     one workgroup per (entry, super-tile (I, J), I <= J): M_w + e (+ d on the diagonal)
 //                                     inside k x k, right-hand side r into column k + r, zero elsewhere; the entry's flag cleared
-//   solve_sweep_tiled_solve_kernel    one workgroup per entry: blocked back substitution (tiled_solve_kernel's scheme) of the R
-//                                     columns in groups of up to 4 - the solution image of a group is at most 64 KiB of LDS and
-//                                     every element of R read feeds up to 4 accumulators - x / gamma and the status
+//   solve_sweep_tiled_solve_kernel    one workgroup per entry: blocked back substitution (back_substitute, as tiled_solve_kernel)
+//                                     of the R columns in groups of up to 4 - the solution image of a group is at most 64 KiB
+//                                     of LDS - x / gamma and the status
+//
+// The grid decode, the back substitution with its group dispatch and LDS size, and the pivot floor are
+// posterior_tiled_sweep_prims.h's.
 //
 // Plain C++, workgroup barriers only, each reached by every thread of its workgroup.  A (window, shift) result depends on the
 // window's M_w, on its own shift and right-hand sides and on k alone: every sum below runs in an order fixed by k, and a
 // column's arithmetic does not depend on which other columns share its group.
-#include "posterior_device_prims.h"
+#include "posterior_tiled_sweep_prims.h"
 #include "posterior_solve_sweep_tiled.h"
 
 namespace {
 
-constexpr int SB = 64;
-constexpr int NTHREADS = 256;
-constexpr int NG = 4;                          // right-hand sides per group of the back substitution
-
 __global__ void __launch_bounds__(NTHREADS) solve_sweep_tiled_fill_kernel(const tp_solve_sweep_tiled_kargs_t A, const tp_tiled_ws_t ws) {
     const int tid = threadIdx.x;
     const int k = A.k, KP = ws.KP, NS = ws.NS;
-    const int NT = NS * (NS + 1) / 2;
-    // The tiled path's grid decode (workgroup id -> XCD = id % 8, slot = id / 8; tiles of an entry consecutive on one XCD),
-    // with the entries dealt to the XCDs in eight contiguous runs: the S entries of a window follow each other on ONE XCD,
-    // whose L2 then serves their reads of the window's M_w.
-    const long long id = blockIdx.x;
-    const long long slot = id >> 3;
-    const long long per_xcd = (A.e_count + 7) / 8;
-    const long long e = (id & 7) * per_xcd + slot / NT;
-    if (e >= A.e_count) return;                 // (uniform per workgroup; the kernel has no barrier)
-    const int tile = (int)(slot % NT);
+    long long e;
     int I, J;
-    pair_decode(tile, NS, I, J);
+    if (!xcd_entry_tile(NS, A.e_count, e, I, J)) return;
     const long long f = A.e_first + e;         // flat (window, shift) index
     const long long w = f / A.S;
     const double* __restrict__ P = A.post + (w - A.wc_first) * (long long)k * k;
@@ -65,61 +55,16 @@ __global__ void __launch_bounds__(NTHREADS) solve_sweep_tiled_fill_kernel(const 
         }
         M[(long long)gi * KP + gj] = v;
     }
-    if (tile == 0 && tid == 0) ws.flags[e] = 0;
+    if (J == 0 && tid == 0) ws.flags[e] = 0;       // (super-tile (0, 0))
 }
 
-// back substitution of columns k + g0 .. k + g0 + G - 1 of one entry; wvec [G][KP] | zv [G][64]
+// back substitution of columns k + g0 .. k + g0 + G - 1 of one entry and x = w / gamma; wvec [G][KP] | zv [G][64]
 template <int G>
 __device__ __forceinline__ bool solve_group(const tp_solve_sweep_tiled_kargs_t& A, const tp_tiled_ws_t& ws, const long long e,
                                             const int g0, double* wvec, double* zv) {
     const int tid = threadIdx.x;
-    const int k = A.k, KP = ws.KP, NSB = ws.NSB;
-    const double* M = ws.arena + e * (long long)KP * KP;
-    const int srow = tid >> 4, cb = tid & 15;      // 16 lanes per row, 16 rows per pass
-    for (int Jb = NSB - 1; Jb >= 0; --Jb) {
-        const int npiv = (k - 64 * Jb < SB) ? (k - 64 * Jb) : SB;
-        // z = y_Jb - sum_{c >= 64 (Jb+1)} R[row][c] w[c], y = the forward-substituted columns
-        for (int ps = 0; ps < 4; ++ps) {
-            const int i = 16 * ps + srow;                 // local row
-            const long long gi = 64 * Jb + i;
-            double s[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) s[g] = 0.0;
-            if (i < npiv)
-                for (int c = 64 * (Jb + 1) + cb; c < k; c += 16) {
-                    const double m = M[gi * KP + c];
-#pragma unroll
-                    for (int g = 0; g < G; ++g) s[g] = fma(m, wvec[g * KP + c], s[g]);
-                }
-#pragma unroll
-            for (int g = 0; g < G; ++g) s[g] = rowgroup_sum16(s[g]);
-            if (cb == 0) {
-#pragma unroll
-                for (int g = 0; g < G; ++g) zv[g * SB + i] = (i < npiv) ? M[gi * KP + k + g0 + g] - s[g] : 0.0;
-            }
-        }
-        __syncthreads();
-        // w_Jb = R_jj^-1 z
-        const double* rinv = ws.rinv + (e * NSB + Jb) * (long long)(SB * SB);
-        for (int ps = 0; ps < 4; ++ps) {
-            const int i = 16 * ps + srow;
-            double s[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) s[g] = 0.0;
-            for (int c = cb; c < SB; c += 16) {
-                const double rv = rinv[i * SB + c];
-#pragma unroll
-                for (int g = 0; g < G; ++g) s[g] = fma(rv, zv[g * SB + c], s[g]);
-            }
-#pragma unroll
-            for (int g = 0; g < G; ++g) s[g] = rowgroup_sum16(s[g]);
-            if (cb == 0 && i < npiv) {
-#pragma unroll
-                for (int g = 0; g < G; ++g) wvec[g * KP + 64 * Jb + i] = s[g];
-            }
-        }
-        __syncthreads();
-    }
+    const int k = A.k, KP = ws.KP;
+    back_substitute<G, false>(ws.arena + e * (long long)KP * KP, KP, k, ws.NSB, k + g0, ws.rinv, e * ws.NSB, nullptr, wvec, zv);
     const long long f = A.e_first + e;
     bool bad = false;
 #pragma unroll
@@ -145,30 +90,15 @@ __global__ void __launch_bounds__(NTHREADS) solve_sweep_tiled_solve_kernel(const
     if (threadIdx.x == 0) { anybad = 0; anylow = 0; }
     __syncthreads();
     bool bad = false;
-    for (int g0 = 0; g0 < R; g0 += NG) {           // (uniform: every thread reaches every barrier of every group)
-        const int g = R - g0 < NG ? R - g0 : NG;
-        if (g == 4) bad |= solve_group<4>(A, ws, e, g0, wvec, zv);
-        else if (g == 3) bad |= solve_group<3>(A, ws, e, g0, wvec, zv);
-        else if (g == 2) bad |= solve_group<2>(A, ws, e, g0, wvec, zv);
-        else bad |= solve_group<1>(A, ws, e, g0, wvec, zv);
-    }
+    for_each_group(R, [&](auto G, const int g0) { bad |= solve_group<decltype(G)::value>(A, ws, e, g0, wvec, zv); });
     if (bad) anybad = 1;
-    // A pivot at the rounding noise of its own diagonal element is not positive definite either: d_i <= k 2^-52 M_ii, the floor
-    // of the LDS prior sweep.  An exactly repeated column has a pivot that is zero in exact arithmetic and of either sign in
-    // floating point; "not > 0" alone let the positive ones through as finite garbage with status OK.  d_i = 1 / (R^-1)_ii^2
-    // from the inverse diagonal blocks the back substitution has just used, M_ii from the kept matrix and the entry's shift.
+    // the pivots' noise floor (low_pivot), M_ii from the kept matrix and the entry's shift
     {
         const int k = A.k;
         const long long f = A.e_first + e;
         const double* __restrict__ P = A.post + (f / A.S - A.wc_first) * (long long)k * k;
         const double sh = A.shift ? A.shift[2 * f] + A.shift[2 * f + 1] : 0.0;
-        const double* rinv = ws.rinv + e * ws.NSB * (long long)(SB * SB);
-        bool low = false;
-        for (int i = threadIdx.x; i < k; i += NTHREADS) {
-            const double ri = rinv[(long long)(i >> 6) * (SB * SB) + (i & 63) * (SB + 1)];
-            if (!(1.0 > (k * 0x1p-52) * (P[(long long)i * k + i] + sh) * (ri * ri))) low = true;     // (a NaN ends here too)
-        }
-        if (low) anylow = 1;
+        if (low_pivot(ws.rinv + e * ws.NSB * (long long)(SB * SB), k, [&](const int i) { return P[(long long)i * k + i] + sh; })) anylow = 1;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -191,20 +121,16 @@ hipError_t tp_solve_sweep_tiled_fill_launch(const tp_solve_sweep_tiled_kargs_t& 
         ws.KP != SB * ws.NS || ws.NSB != (a.k + SB - 1) / SB || (a.n_rhs > 0 && a.rhs == nullptr) ||
         a.R != (a.default_rhs != nullptr ? 1 : 0) + a.n_rhs)
         return hipErrorInvalidValue;
-    const long long NT = (long long)ws.NS * (ws.NS + 1) / 2;
-    const long long grid = ((a.e_count + 7) / 8) * 8 * NT;
-    hipLaunchKernelGGL(solve_sweep_tiled_fill_kernel, dim3((unsigned)grid), dim3(NTHREADS), 0, stream, a, ws);
+    hipLaunchKernelGGL(solve_sweep_tiled_fill_kernel, xcd_entry_grid(ws.NS, a.e_count), dim3(NTHREADS), 0, stream, a, ws);
     return hipGetLastError();
 }
 
 hipError_t tp_solve_sweep_tiled_solve_launch(const tp_solve_sweep_tiled_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream) {
     if (a.k < 1 || a.R < 1 || a.R > TP_SWEEP_KMAX_RHS || a.e_count < 1 || a.e_count > 65535 || a.k + a.R > ws.KP)
         return hipErrorInvalidValue;
-    const int max_lds = (int)(sizeof(double) * (size_t)(NG * SB * 32 + NG * SB));       // KP <= 2048
     static std::atomic<unsigned long long> attr_done{0};      // one bit per device (tp_allow_dynamic_lds)
-    { hipError_t e = tp_allow_dynamic_lds(attr_done, solve_sweep_tiled_solve_kernel, max_lds); if (e != hipSuccess) return e; }
-    const size_t smem = sizeof(double) * ((size_t)(a.R < NG ? a.R : NG) * ws.KP + NG * SB);
-    if (smem > (size_t)max_lds) return hipErrorInvalidValue;
+    size_t smem;
+    { hipError_t e = group_solve_lds(attr_done, solve_sweep_tiled_solve_kernel, a.R, ws.KP, &smem); if (e != hipSuccess) return e; }
     hipLaunchKernelGGL(solve_sweep_tiled_solve_kernel, dim3((unsigned)a.e_count), dim3(NTHREADS), smem, stream, a, ws);
     return hipGetLastError();
 }

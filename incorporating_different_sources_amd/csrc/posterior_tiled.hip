@@ -20,36 +20,22 @@
 //
 // Jeffreys (ref:600-606): J = T - t t'/N is applied as a rank-one correction by tile64_kernel<RANK1>
 // after the Gram pass (t is the border column).
+//
+// The grid decode, the conjugate scalars, the border of a conjugate entry (tiled_clear_kernel's shared-intraday branch) and the
+// blocked back substitution (tiled_solve_kernel: one column) are posterior_tiled_sweep_prims.h's, shared with the tiled sweeps.
 #include <stdlib.h>
 
-#include "posterior_device_prims.h"
+#include "posterior_tiled_sweep_prims.h"
 
 namespace {
 
-constexpr int SB = 64;                 // super-block edge
 constexpr int CH = 16;                 // staged rows per chunk
 constexpr int LDX = 2 * SB + 16;       // LDS row stride of a staged chunk (A cols | B cols), 144 = 16 mod 32
-constexpr int NTHREADS = 256;
 
 enum { MODE_GRAM = 0, MODE_TRSM = 1, MODE_SYRK = 2, MODE_SYRK_DIAG = 3 };   // SYRK_DIAG: the update of tile (j, j) alone
 
 // inverse of pair_decode: row-major number of the upper-triangle pair (a, b), a <= b < n
 __device__ __forceinline__ long long pair_index(int a, int b, int n) { return (long long)a * n - (long long)a * (a - 1) / 2 + (b - a); }
-
-// XCD-aware mapping of a 1-D grid to (window, tile) for the kernels that run SEVERAL workgroups per window.
-// MI355X deals consecutive workgroup ids round-robin to its 8 XCDs, each with its own 4 MB L2.  With
-// (window, tile) = (blockIdx.x, blockIdx.y) the tiles of one window ran on one XCD but thousands of workgroups
-// apart, so every tile re-read the window's rows (or arena tiles) from HBM / Infinity Cache: the Gram kernel
-// moved 48 GB per launch at k = 500.  Here id -> xcd = id % 8, slot = id / 8, window = 8 (slot / NT) + xcd,
-// tile = slot % NT: the NT tiles of a window are consecutive ON ONE XCD, whose L2 then serves the re-reads.
-__device__ __forceinline__ bool xcd_window_tile(int NT, long long G, long long& wl, int& tile) {
-    const long long id = blockIdx.x;
-    const long long slot = id >> 3;
-    wl = 8 * (slot / NT) + (id & 7);
-    tile = (int)(slot % NT);
-    return wl < G;
-}
-inline dim3 xcd_grid(int NT, long long G) { return dim3((unsigned)(((G + 7) / 8) * 8 * NT)); }
 
 // ------------------------------------------------------------------------------------------------
 // ONE pass over the intraday window (the kernel is HBM-bound: the window is 1.5 MB at k=500, 13.7 MB at k=1000,
@@ -123,10 +109,9 @@ __global__ void __launch_bounds__(NTHREADS) tiled_prior_kernel(const tp_kargs_t 
     __syncthreads();
     if (tid == 0) {
         const double n0 = A.n0[w];
-        const double s = n0 * ((double)mm / ((double)mm - 1.0));
-        const double q0 = s * (((red[0] + red[1]) + red[2]) + red[3]);
-        const double a = n0 + k + 2;
-        const double c = (2 * n0) / (a + sqrt(a * a + 4 * n0 * q0));
+        const double s = prior_scale(n0, (double)mm);
+        const double q0 = s * sum4(red);
+        const double c = shrink_c(n0, k, q0);
         double* o = ws.scal + wl * 8;
         o[0] = s; o[1] = sqrt(s); o[2] = c; o[3] = q0; o[4] = n0;
         sc[0] = c * sqrt(s);
@@ -657,31 +642,7 @@ __global__ void __launch_bounds__(NTHREADS) tiled_solve_kernel(const tp_kargs_t 
     __syncthreads();
     const double q1 = qs[0] + qs[1] + qs[2] + qs[3];
 
-    const int srow = tid >> 4, cb = tid & 15;      // 16 lanes per row, 16 rows per pass
-    for (int Jb = NSB - 1; Jb >= 0; --Jb) {
-        const int npiv = (k - 64 * Jb < SB) ? (k - 64 * Jb) : SB;
-        // z = y_Jb - sum_{c >= 64 (Jb+1)} R[row][c] w[c]
-        for (int ps = 0; ps < 4; ++ps) {
-            const int i = 16 * ps + srow;                 // local row
-            const long long gi = 64 * Jb + i;
-            double s = 0.0;
-            if (i < npiv)
-                for (int c = 64 * (Jb + 1) + cb; c < k; c += 16) s = fma(M[gi * KP + c], wvec[c], s);
-            s = rowgroup_sum16(s);
-            if (cb == 0) zv[i] = (i < npiv) ? M[gi * KP + k] - s : 0.0;
-        }
-        __syncthreads();
-        // w_Jb = R_jj^-1 z
-        const double* rinv = ws.rinv + (wl * ws.NSB + Jb) * (long long)(SB * SB);
-        for (int ps = 0; ps < 4; ++ps) {
-            const int i = 16 * ps + srow;
-            double s = 0.0;
-            for (int c = cb; c < SB; c += 16) s = fma(rinv[i * SB + c], zv[c], s);
-            s = rowgroup_sum16(s);
-            if (cb == 0 && i < npiv) wvec[64 * Jb + i] = s;
-        }
-        __syncthreads();
-    }
+    back_substitute<1, false>(M, KP, k, NSB, k, ws.rinv, wl * ws.NSB, nullptr, wvec, zv);
     const bool conj = A.strategy == 0;
     const double n0 = conj ? ws.scal[wl * 8 + 4] : 0.0;
     const double n1 = n0 + (double)A.N;
@@ -716,39 +677,14 @@ __global__ void __launch_bounds__(NTHREADS) tiled_clear_kernel(const tp_kargs_t 
     const int k = A.k, KP = ws.KP;
     double* M = ws.arena + wl * (long long)KP * KP;
     if (A.strategy == 0 && A.hf_winsum != nullptr) {
-        // shared intraday sums (posterior_tiled_wave.h): S0 w0 from the super-tiles' pieces in a fixed order, then
-        // q0 = w0' S0 w0, c (ref:415-418) and c S0 w0 into the border column, where the two-pass form's Gram puts it
-        __shared__ double red[4];
-        const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+        // shared intraday sums (posterior_tiled_wave.h): S0 w0 from the super-tiles' pieces in a fixed order, then q0 = w0' S0 w0,
+        // c and c S0 w0 into the border column, where the two-pass form's Gram puts it
         const long long w = A.w_first + wl;
-        const int NS = ws.NS;
-        const double* part = ws.part + (wl * NS * NS) * 64;
-        double* v0 = ws.ybar + wl * KP;
-        double qq = 0.0;
-        for (int i = tid; i < k; i += NTHREADS) {
-            const double* pp = part + ((long long)(i >> 6) * NS) * 64 + (i & 63);
-            double v = 0.0;
-            for (int src = 0; src < NS; ++src) v += pp[src * 64];
-            v0[i] = v;
-            qq = fma(A.w0[w * k + i], v, qq);
-        }
-        qq = wave_sum64(qq);
-        if (lane == 0) red[wv] = qq;
-        __syncthreads();
-        const double q0 = ((red[0] + red[1]) + red[2]) + red[3];
-        const double n0 = A.n0[w];
-        const double mm = (double)A.m;
-        const double s = n0 * (mm / (mm - 1.0));
-        const double a = n0 + k + 2;
-        const double c = (2 * n0) / (a + sqrt(a * a + 4 * n0 * q0));
-        for (int i = tid; i < k; i += NTHREADS) M[(long long)i * KP + k] += c * v0[i];
-        if (tid == 0) {
-            double* o = ws.scal + wl * 8;
-            o[0] = s; o[1] = sqrt(s); o[2] = c; o[3] = q0; o[4] = n0;
-        }
+        const EntryScal sc = conj_border(ws, wl, k, ws.part + (wl * ws.NS * ws.NS) * 64, A.w0 + w * k, A.n0 + w, (double)A.m, ws.ybar + wl * KP);
+        if (threadIdx.x == 0) write_scal(ws, wl, sc);
         __syncthreads();
     }
-    for (int e = threadIdx.x; e < (KP - k) * KP; e += NTHREADS) M[(long long)k * KP + e] = 0.0;
+    zero_border_rows(ws, wl, k);
     if (A.rhs != nullptr)     // caller-supplied right-hand side in place of the border column
         for (int i = threadIdx.x; i < k; i += NTHREADS) M[(long long)i * KP + k] = A.rhs[(A.w_first + wl) * k + i];
     if (A.out_rhs != nullptr)
@@ -947,6 +883,7 @@ hipError_t tp_tiled_gram_launch(const tp_kargs_t& a_in, const tp_tiled_ws_t& ws,
     tp_kargs_t a = a_in;
     const int G = (int)a.w_count;
     if (G <= 0) return hipSuccess;
+    if (a.k < 1) return hipErrorInvalidValue;     // (k >= 1: what conj_border assumes of tiled_clear_kernel's k)
     const int NS = ws.NS;
     const bool conj = a.strategy == 0;
     // 32-bit offsets for both panels in the layout they come in (explicit rows: bit 0, contiguous: bit 1)?

@@ -501,7 +501,7 @@ __device__ __forceinline__ void gram64_wave_hfs_body(const tp_kargs_t& A, const 
     // ---- S0 = s (Q + edge - t t'/m) in registers, and this super-tile's pieces of S0 w0
     {
         const double n0 = A.n0[w];
-        const double sc = n0 * ((double)mm / ((double)mm - 1.0));
+        const double sc = prior_scale(n0, (double)mm);
         const double minv = 1.0 / (double)mm;
         const double* w0 = A.w0 + w * k;
         double colp[NB];

@@ -17,19 +17,20 @@
 //                                     and c as in ref:415-418 with g = n0_wpl + k + 2;  Jeffreys T - t t'/N_l (TP_FLAG_CENTER_BY_ROWS:
 //                                     / rows_wl, TP_FLAG_NO_CENTER: no term), column k = t
 //   window_sweep_tiled_border_kernel  one workgroup per entry: ws.scal = (s, sqrt s, c, q0, n0), rows >= k and the flag zeroed
+//                                     (close_entry)
 //   window_sweep_tiled_scatter_kernel one workgroup per entry, behind the factorisation: weights, status and aux from the
 //                                     launch's staging rows to slot (w P + p) L + l of the sweep's results
+//
+// The grid decode, the conjugate scalars and the closing of an entry are posterior_tiled_sweep_prims.h's.
 //
 // C is RAW-MOMENT centred as in the tiled prior sweep.  Plain C++, workgroup barriers only, each reached
 // by every thread of its workgroup; every loop is bounded by k, KP or the launch's arguments.  A (window, prior, length) result
 // depends on the window's C, its own snapshot and delta sums, its prior, N_l and k alone: every sum runs in an order fixed by k.
-#include "posterior_device_prims.h"
+#include "posterior_tiled_sweep_prims.h"
 #include "posterior_window_sweep.h"
 
 namespace {
 
-constexpr int SB = 64;
-constexpr int NTHREADS = 256;
 constexpr int CW_MAX_K = 2048;
 
 __global__ void __launch_bounds__(NTHREADS) window_sweep_tiled_cw_kernel(const tp_window_sweep_tiled_kargs_t A) {
@@ -60,21 +61,17 @@ __global__ void __launch_bounds__(NTHREADS) window_sweep_tiled_cw_kernel(const t
     q = wave_sum64(q);
     if (lane == 0) red[wv] = q;
     __syncthreads();
-    if (tid == 0) A.cq[wpl] = ((red[0] + red[1]) + red[2]) + red[3];
+    if (tid == 0) A.cq[wpl] = sum4(red);
 }
 
-struct EntryScalars { double n0, ap, cc, q0; };
-
 // the scalars of entry `wp`, length A.l (conjugate): every workgroup of the entry forms them from the same numbers in the same way
-__device__ __forceinline__ EntryScalars entry_scalars(const tp_window_sweep_tiled_kargs_t& A, const long long wp, const long long w) {
-    EntryScalars s;
-    s.n0 = A.n0[wp * A.L + A.l];
-    const double mm = (double)(A.hf_count != nullptr ? A.hf_count[w] : A.m);
-    s.ap = s.n0 * (mm / (mm - 1.0));                           // ref:333, as the run kernels form it
-    s.q0 = s.ap * A.cq[wp - A.wc_first * A.P];
-    const double g = s.n0 + A.k + 2;
-    s.cc = (2 * s.n0) / (g + sqrt(g * g + 4 * s.n0 * s.q0));   // ref:415-418
-    return s;
+__device__ __forceinline__ EntryScal entry_scalars(const tp_window_sweep_tiled_kargs_t& A, const long long wp, const long long w) {
+    EntryScal sc;
+    sc.n0 = A.n0[wp * A.L + A.l];
+    sc.s = prior_scale(sc.n0, hf_rows(A, w));
+    sc.q0 = sc.s * A.cq[wp - A.wc_first * A.P];
+    sc.c = shrink_c(sc.n0, A.k, sc.q0);
+    return sc;
 }
 
 template <bool CONJ>
@@ -82,17 +79,9 @@ __global__ void __launch_bounds__(NTHREADS) window_sweep_tiled_fill_kernel(const
     __shared__ double tI[SB], tJ[SB], dI[SB], dJ[SB];          // t = g_l - s1 and the delta kernel's v of the tile's rows / columns
     const int tid = threadIdx.x;
     const int k = A.k, KP = ws.KP, NS = ws.NS, L = A.L;
-    const int NT = NS * (NS + 1) / 2;
-    // the tiled prior sweep's grid decode: the tiles of an entry consecutive on ONE XCD, the entries dealt to the XCDs in eight
-    // contiguous runs (the P entries of a window read the same C and snapshot)
-    const long long id = blockIdx.x;
-    const long long slot = id >> 3;
-    const long long per_xcd = (A.e_count + 7) / 8;
-    const long long e = (id & 7) * per_xcd + slot / NT;
-    if (slot / NT >= per_xcd || e >= A.e_count) return;         // (uniform per workgroup, in front of every barrier)
-    const int tile = (int)(slot % NT);
+    long long e;
     int I, J;
-    pair_decode(tile, NS, I, J);
+    if (!xcd_entry_tile(NS, A.e_count, e, I, J)) return;
     const long long wp = A.wp_first + e;
     const long long w = wp / A.P;
     const long long wl = w - A.wc_first;
@@ -111,7 +100,7 @@ __global__ void __launch_bounds__(NTHREADS) window_sweep_tiled_fill_kernel(const
         if (tid < SB) { tI[x] = tv; dI[x] = dv; } else { tJ[x] = tv; dJ[x] = dv; }
     }
     __syncthreads();
-    EntryScalars es{0.0, 0.0, 0.0, 0.0};
+    EntryScal es{0.0, 0.0, 0.0, 0.0};
     const double* __restrict__ C = nullptr;
     const double* __restrict__ cw = nullptr;
     double rinv = 0.0;
@@ -134,13 +123,13 @@ __global__ void __launch_bounds__(NTHREADS) window_sweep_tiled_fill_kernel(const
             const double dlo = up ? dI[r] : dJ[c], dhi = up ? dJ[c] : dI[r];
             const double tv = T[(long long)lo * k + hi] - dlo - dhi + s2;      // G - v 1' - 1 v' + s2 1 1'
             if constexpr (CONJ) {
-                out = fma(es.ap, C[(long long)gi * k + gj], tv);
+                out = fma(es.s, C[(long long)gi * k + gj], tv);
             } else {
                 const double tlo = up ? tI[r] : tJ[c], thi = up ? tJ[c] : tI[r];
                 out = A.center_rows == 2 ? tv : fma(-(tlo * rinv), thi, tv);
             }
         } else if (gj == k && gi < k) {
-            out = CONJ ? fma(es.cc * es.ap, cw[gi], tI[r]) : tI[r];
+            out = CONJ ? fma(es.c * es.s, cw[gi], tI[r]) : tI[r];
         }
         M[(long long)gi * KP + gj] = out;
     }
@@ -148,23 +137,10 @@ __global__ void __launch_bounds__(NTHREADS) window_sweep_tiled_fill_kernel(const
 
 template <bool CONJ>
 __global__ void __launch_bounds__(NTHREADS) window_sweep_tiled_border_kernel(const tp_window_sweep_tiled_kargs_t A, const tp_tiled_ws_t ws) {
-    const int tid = threadIdx.x;
     const long long e = blockIdx.x;
-    const int k = A.k, KP = ws.KP;
-    double* M = ws.arena + e * (long long)KP * KP;
-    if (tid == 0) {
-        double* o = ws.scal + e * 8;
-        if constexpr (CONJ) {
-            const long long wp = A.wp_first + e;
-            const EntryScalars es = entry_scalars(A, wp, wp / A.P);
-            o[0] = es.ap; o[1] = sqrt(es.ap); o[2] = es.cc; o[3] = es.q0; o[4] = es.n0;
-        } else {
-            o[0] = 0.0; o[1] = 0.0; o[2] = 0.0; o[3] = 0.0; o[4] = 0.0;
-        }
-        ws.flags[e] = 0;
-    }
-    // rows >= k of the bordered matrix are never pivots (tiled_clear_kernel)
-    for (int x = tid; x < (KP - k) * KP; x += NTHREADS) M[(long long)k * KP + x] = 0.0;
+    EntryScal es{0.0, 0.0, 0.0, 0.0};
+    if constexpr (CONJ) es = entry_scalars(A, A.wp_first + e, (A.wp_first + e) / A.P);
+    close_entry(ws, e, A.k, es);
 }
 
 __global__ void __launch_bounds__(NTHREADS) window_sweep_tiled_scatter_kernel(const tp_window_sweep_tiled_kargs_t A) {
@@ -193,13 +169,12 @@ hipError_t tp_window_sweep_tiled_cw_launch(const tp_window_sweep_tiled_kargs_t& 
 
 hipError_t tp_window_sweep_tiled_fill_launch(const tp_window_sweep_tiled_kargs_t& a, const tp_tiled_ws_t& ws, hipStream_t stream) {
     if (!args_ok(a)) return hipErrorInvalidValue;
-    const long long NT = (long long)ws.NS * (ws.NS + 1) / 2;
-    const long long grid = ((a.e_count + 7) / 8) * 8 * NT;
+    const dim3 grid = xcd_entry_grid(ws.NS, a.e_count);
     if (a.C != nullptr) {
-        hipLaunchKernelGGL(window_sweep_tiled_fill_kernel<true>, dim3((unsigned)grid), dim3(NTHREADS), 0, stream, a, ws);
+        hipLaunchKernelGGL(window_sweep_tiled_fill_kernel<true>, grid, dim3(NTHREADS), 0, stream, a, ws);
         hipLaunchKernelGGL(window_sweep_tiled_border_kernel<true>, dim3((unsigned)a.e_count), dim3(NTHREADS), 0, stream, a, ws);
     } else {
-        hipLaunchKernelGGL(window_sweep_tiled_fill_kernel<false>, dim3((unsigned)grid), dim3(NTHREADS), 0, stream, a, ws);
+        hipLaunchKernelGGL(window_sweep_tiled_fill_kernel<false>, grid, dim3(NTHREADS), 0, stream, a, ws);
         hipLaunchKernelGGL(window_sweep_tiled_border_kernel<false>, dim3((unsigned)a.e_count), dim3(NTHREADS), 0, stream, a, ws);
     }
     return hipGetLastError();
