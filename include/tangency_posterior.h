@@ -140,6 +140,9 @@ int tp_destroy(tp_handle_t h);
  *                      super-tile / block (what automatic picks); any other value: TP_ERR_INVALID (in the
  *                      environment: automatic)
  *   "tiled_fuse"       -1 automatic | 0 / 1 three-kernel / fused left-looking update of the large-k path
+ *   "wave_preload"     1 the one-wave kernel starts a window's accumulators from its shared table slot wherever the batch
+ *                      qualifies (plain conjugate, contiguous layout with shared sums, k mod 16 <= 13) | -1 automatic: there,
+ *                      at the sizes where that measured faster | 0 never (A/B measurements); any other value: TP_ERR_INVALID
  *   "no_shared_gram"   1 = as if every batch carried TP_FLAG_NO_SHARED_GRAM (takes effect at the next upload)
  *   "tiled_arena_gib" / "tiled_arena_mib"  in-flight arena of the large-k path (0: default)
  *   "hf_share_min_blocks"  large-k path, conjugate: intraday windows that advance by a fixed stride share the Grams of

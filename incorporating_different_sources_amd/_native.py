@@ -297,7 +297,7 @@ class Device:
 
     def set_option(self, name: str, value: int):
         """`tp_set_option`: kernel-selection switches of this handle ("wave_kernel", "tiled_wave", "tiled_fuse",
-        "no_shared_gram", "tiled_arena_gib", "tiled_arena_mib", "hf_share_min_blocks",
+        "wave_preload", "no_shared_gram", "tiled_arena_gib", "tiled_arena_mib", "hf_share_min_blocks",
         "sweep_chunk_windows": windows per sub-range of `Batch.solve_sweep`, 0 = automatic); the TP_* environment
         variables are read once, when the Device is created.  An unknown name or a value an option does not take raises
         TangencyError."""

@@ -15,6 +15,8 @@ struct tp_kopts_t {
     int wave_kernel = -1;   // register-tile path: 0 = multi-wave kernel, 1 = one-wave kernel (k <= 143), 2 = two-wave kernel
     int tiled_wave = -1;    // large-k path: 0 = the 4-wave Gram / diagonal-block kernels, 1 = the one-wave kernels (-1, 0, 1 only)
     int tiled_fuse = -1;    // large-k path: 0 / 1 = three-kernel / fused left-looking update + solve
+    int wave_preload = -1;  // one-wave kernel, accumulators started from the table slot: 0 = never, 1 = wherever the batch is
+                            // eligible, -1 = there and at the tile counts where it was measured to pay (wave_preload_pays)
 };
 
 // Dynamic-LDS limit of a kernel: a per-DEVICE function attribute.  The one-process-all-GPUs mode launches the same
@@ -84,6 +86,9 @@ struct tp_kargs_t {
     int center_rows;      // Jeffreys: 0 = J = T - t t'/N, 1 = divide by the window's row count instead, 2 = plain T
     double gamma;
     tp_kopts_t opts;      // host-side only: which kernels run this batch
+    // (behind everything else: the kernels that do not read it keep their argument offsets)
+    const double* winsum_zero;   // register-tile path: one all-zero slot behind the Q tables, for the windows of a sharing batch
+                                 // that have no slot of their own (posterior_wave_impl.h, PRE); null: the batch does not qualify
 };
 
 struct tp_launch_info_t { int grid, block, lds_bytes, ntile; };

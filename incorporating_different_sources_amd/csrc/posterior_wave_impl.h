@@ -192,6 +192,66 @@ __device__ __forceinline__ void wave_settle(d4 (&acc)[N]) {
     }
 }
 
+// ---- accumulators STARTED from a table slot (the PRE form of the one-wave kernel, wave_window_body).  A slot is
+// [tile][2][64 lanes][2] doubles - the accumulator layout - so tile T is two 16-byte loads per lane, and a global load may
+// name AGPRs as its destination: no VGPR visit, no add.  The two loads fill the halves of ONE eight-register operand, which
+// inline assembly can only say with the registers' names: tile T of the AGPR-resident tiles is loaded into a[8T:8T+7]
+// (a physical-register output).  The allocator keeps the value there (checked on the ISA: no v_accvgpr move follows).
+// The compiler counts neither load: wave_slot_arrive1 - s_waitcnt vmcnt(0), which "modifies" the tile - stands between
+// the load and every use, and tools/check_mfma_hazards.py proves on the ISA that nothing touches a destination in between.
+// Address: lane-uniform slot base + 2048 T in SGPRs (scalar adds), 16 lane in one VGPR.
+template <int T>
+__device__ __forceinline__ void wave_slot_load(d4& c, const double* slot_tile, unsigned lane16);
+#define TP_SLOT_LOAD(T, R0, R3, R4, R7)                                                                                        \
+    template <>                                                                                                                 \
+    __device__ __forceinline__ void wave_slot_load<T>(d4& c, const double* slot_tile, unsigned lane16) {                        \
+        asm volatile("global_load_dwordx4 a[" #R0 ":" #R3 "], %1, %2\n\tglobal_load_dwordx4 a[" #R4 ":" #R7 "], %1, %2 offset:1024" \
+                     : "={a[" #R0 ":" #R7 "]}"(c)                                                                               \
+                     : "v"(lane16), "s"(slot_tile)                                                                              \
+                     : "memory");                                                                                               \
+    }
+TP_SLOT_LOAD(0, 0, 3, 4, 7) TP_SLOT_LOAD(1, 8, 11, 12, 15) TP_SLOT_LOAD(2, 16, 19, 20, 23) TP_SLOT_LOAD(3, 24, 27, 28, 31)
+TP_SLOT_LOAD(4, 32, 35, 36, 39) TP_SLOT_LOAD(5, 40, 43, 44, 47) TP_SLOT_LOAD(6, 48, 51, 52, 55) TP_SLOT_LOAD(7, 56, 59, 60, 63)
+TP_SLOT_LOAD(8, 64, 67, 68, 71) TP_SLOT_LOAD(9, 72, 75, 76, 79) TP_SLOT_LOAD(10, 80, 83, 84, 87) TP_SLOT_LOAD(11, 88, 91, 92, 95)
+TP_SLOT_LOAD(12, 96, 99, 100, 103) TP_SLOT_LOAD(13, 104, 107, 108, 111) TP_SLOT_LOAD(14, 112, 115, 116, 119)
+TP_SLOT_LOAD(15, 120, 123, 124, 127) TP_SLOT_LOAD(16, 128, 131, 132, 135) TP_SLOT_LOAD(17, 136, 139, 140, 143)
+TP_SLOT_LOAD(18, 144, 147, 148, 151) TP_SLOT_LOAD(19, 152, 155, 156, 159) TP_SLOT_LOAD(20, 160, 163, 164, 167)
+TP_SLOT_LOAD(21, 168, 171, 172, 175) TP_SLOT_LOAD(22, 176, 179, 180, 183) TP_SLOT_LOAD(23, 184, 187, 188, 191)
+TP_SLOT_LOAD(24, 192, 195, 196, 199) TP_SLOT_LOAD(25, 200, 203, 204, 207) TP_SLOT_LOAD(26, 208, 211, 212, 215)
+TP_SLOT_LOAD(27, 216, 219, 220, 223) TP_SLOT_LOAD(28, 224, 227, 228, 231) TP_SLOT_LOAD(29, 232, 235, 236, 239)
+TP_SLOT_LOAD(30, 240, 243, 244, 247) TP_SLOT_LOAD(31, 248, 251, 252, 255)
+#undef TP_SLOT_LOAD
+template <int T>
+__device__ __forceinline__ void wave_slot_arrive1(d4& c) {
+    static_assert(wave_tile_in_agpr(T), "VGPR-resident tiles are loaded by the compiler's own (counted) loads");
+    asm volatile("s_waitcnt vmcnt(0)" : "+a"(c));
+}
+// every tile of a window from the slot at `q`: the AGPR-resident tiles as above, the VGPR-resident ones (tiles 32.., eight
+// and nine tiles per side) by plain loads, which the compiler counts and waits for itself
+template <int N>
+__device__ __forceinline__ void wave_slot_issue(d4 (&acc)[N], const double* q, int lane) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const unsigned lane16 = 16u * (unsigned)lane;
+    static_for<0, N>([&](auto tc) __attribute__((always_inline)) {
+        constexpr int t = decltype(tc)::value;
+        if constexpr (wave_tile_in_agpr(t)) {
+            wave_slot_load<t>(acc[t], q + 256 * t, lane16);
+        } else {
+            const d2* p = (const d2*)(q + 256 * t) + lane;
+            const d2 lo = p[0], hi = p[64];
+            acc[t] = d4{lo[0], lo[1], hi[0], hi[1]};
+        }
+    });
+}
+template <int N>
+__device__ __forceinline__ void wave_slot_arrive(d4 (&acc)[N]) {
+    static_for<0, N>([&](auto tc) __attribute__((always_inline)) {
+        constexpr int t = decltype(tc)::value;
+        if constexpr (wave_tile_in_agpr(t)) wave_slot_arrive1<t>(acc[t]);
+        else wave_pin1<t>(acc[t]);
+    });
+}
+
 struct WRows {
     const double* base;     // panel
     long long ld;           // leading dimension (doubles)
@@ -214,11 +274,16 @@ struct WRows {
 //  wave wait for the shift row before it could ask for the first panel rows (two memory round trips in a row, and this
 //  wave has nothing else to run meanwhile)
 //  !LEAN: lds_rows[r] / lds_sub[r] hold the panel row and the subtrahend of row r of this pass (staged by wave_stage_rows)
-template <int NT, int NWV, int WV, bool HF, bool LEAN>
+//  PRE (one-wave kernel, HF, LEAN, ones; defaults to off - every other caller compiles to what it was): the accumulators
+//  arrive UNDEFINED and start as the table slot at `slot`, loaded behind the first two k-steps' row loads; the shifted rows
+//  are scaled by `rsc` (subtract, then multiply: a constant column stays exactly zero), column k stays zero (it holds the
+//  slot's t) and u_r goes to column k+2
+template <int NT, int NWV, int WV, bool HF, bool LEAN, bool PRE = false>
 __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&coff)[NT], int k, int lane,
                                           double (&shift)[NT], double (&w0v)[NT], bool ones, bool lazy_mask,
                                           d4 (&acc)[w2_count<NT, NWV>(WV)], const int* lds_rows, const double* lds_sub,
-                                          double (&csum)[NT], double& usum) {
+                                          double (&csum)[NT], double& usum, double rsc = 1.0, const double* slot = nullptr) {
+    static_assert(!PRE || (HF && LEAN && NWV == 1), "the preloaded form exists for the one-wave kernel's intraday pass only");
     constexpr int kI = NT - 1;
     const int fr = lane & 15, fq = lane >> 4;
     const int kc = k - 16 * kI;
@@ -284,6 +349,10 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
         if (HF) {
 #pragma unroll
             for (int i = 0; i < NT; ++i) v[i] -= shift[i];
+            if constexpr (PRE) {
+#pragma unroll
+                for (int i = 0; i < NT; ++i) v[i] *= rsc;
+            }
         } else if (has_sub) {
 #pragma unroll
             for (int i = 0; i < NT; ++i) v[i] -= sub;                // ref:57
@@ -308,7 +377,7 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
                 for (int i = 0; i < NT; ++i) csum[i] += v[i];
                 usum += z;
             }
-            if (fr == kc) v[kI] = z;                                 // u_r = (y_r - shift).w0
+            if (fr == (PRE ? kc + 2 : kc)) v[kI] = z;                // u_r = (y_r - shift).w0
         }
         static_for<0, NT>([&](auto Ic) __attribute__((always_inline)) {
             constexpr int I = decltype(Ic)::value;
@@ -324,13 +393,19 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
         });
     };
 
-    if (nks <= 0) return;
+    if constexpr (!PRE) {
+        if (nks <= 0) return;
+    }
     // Three register sets rotate through load -> (two k-steps of MFMAs) -> use.  The main loop runs whole triples of
     // full k-steps as ONE basic block (loads past the end re-read the last row); at most three k-steps remain.
     double va[NT], vb[NT], vc[NT];
     double sa = 0.0, sb = 0.0, sc = 0.0;
     load(va, sa, 0);
     load(vb, sb, 1);
+    if constexpr (PRE) {
+        __builtin_amdgcn_sched_barrier(0);
+        wave_slot_issue(acc, slot, lane);
+    }
     if (HF && lazy_mask) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -340,7 +415,8 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
             w0v[i] = cv ? w0v[i] : 0.0;
         }
     }
-    wave_pin(acc);
+    if constexpr (PRE) wave_slot_arrive(acc);
+    else wave_pin(acc);
     int ks = 0;
 #pragma nounroll
     for (; 4 * (ks + 3) <= src.count; ks += 3) {
@@ -381,8 +457,14 @@ __device__ __forceinline__ void wave_stage_rows(const WRows& src, int lane, int*
 // next to the inline-assembly MFMAs is exactly what the hazard argument of wave_settle cannot cover).  MODE 2 is therefore
 // not instantiated: batches that ask for a matrix read-back, a custom right-hand side, tp_batch_keep_rhs or a shift run
 // on the multi-wave kernel (wave_mode / launch_one).
-template <int NT, bool LEAN, int MODE>
+// PRE (plain conjugate, LEAN, a batch with shared tables, kc <= 13; wave_launch_variant decides): the accumulators START as
+// the window's table slot Q_L[b0] (wave_gram, PRE), the intraday rows are accumulated on top of it already scaled by
+// sqrt(sc), the rank-one term of the centring is one more k-step of MFMAs, and only tile column kI visits the VGPR half
+// between the row loops - no pass over all tiles (phase C) and no table addition (phase D).  Columns: k the slot's t, k+1
+// ones, k+2 u.  Windows of such a batch without a slot of their own start from the tables' all-zero slot.
+template <int NT, bool LEAN, int MODE, bool PRE = false>
 __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* lds) {
+    static_assert(!PRE || (LEAN && (MODE == 0 || MODE == 3)), "preloaded accumulators: plain conjugate, contiguous layout");
     constexpr bool FULL = MODE == 2;
     constexpr bool POST = MODE >= 3;
     constexpr int PLAIN = POST ? MODE - 3 : MODE;
@@ -428,10 +510,12 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
     double* idx_sub_lds = LEAN ? nullptr : lds + C::OFF_SUB;
     int* idx_rows_lds = LEAN ? nullptr : (int*)(lds + C::OFF_SUB + wave_idx_rows(A.n_r, A.m, A.strategy == 0));
     d4 acc[C::NTILES];
+    if constexpr (!PRE) {
     static_for<0, C::NTILES>([&](auto tc) __attribute__((always_inline)) { acc[decltype(tc)::value] = d4{0.0, 0.0, 0.0, 0.0}; });
     // AGPR values from the first definition on: where two paths of the kernel meet, the accumulators must arrive as AGPR
     // values on both, or the merge keeps all of them in VGPRs (and spills)
     wave_pin(acc);
+    }
 
     // identity tile for the pivot chain (read after many waits on this wave's own LDS traffic)
 #pragma unroll
@@ -476,6 +560,137 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
     };
 
     TP_MARK(0);
+    if constexpr (PRE) {
+        n0 = A.n0[w];
+        WRows hs;
+        hs.base = A.hf_panel; hs.ld = A.hf_ld;
+        hs.ridx = nullptr;
+        hs.first = A.hf_start ? A.hf_start[w] : 0;
+        hs.sub_row = nullptr;
+        hs.count = A.hf_count ? A.hf_count[w] : A.m;
+        hs.count0 = 0x7fffffff; hs.jump = 0;
+        hs.off32 = (A.hf_off32 & 1) != 0;
+        // the daily window first: its table slot is what the accumulators start from (phase D: the edge rows alone)
+        WRows ds;
+        ds.base = A.panel; ds.ld = A.panel_ld;
+        ds.ridx = nullptr;
+        ds.first = A.start ? A.start[w] : 0;
+        ds.sub_row = nullptr;                                       // (a batch with rf_adj has no tables)
+        ds.count = A.n_rows ? A.n_rows[w] : A.n_r;
+        ds.count0 = 0x7fffffff; ds.jump = 0;
+        ds.off32 = (A.panel_off32 & 1) != 0;
+        const double* q;
+        {
+            constexpr int BLK = 16;
+            const long long b0 = (ds.first + BLK - 1) / BLK, b1 = (ds.first + ds.count) / BLK;
+            const int Lw = (int)(b1 - b0);
+            const int li = Lw == A.winsum_L[0] ? 0 : Lw == A.winsum_L[1] ? 1 : Lw == A.winsum_L[2] ? 2 : Lw == A.winsum_L[3] ? 3 : -1;
+            const bool shared = Lw > 0 && li >= 0;
+            // no branch around the loads: a window without a slot of its own reads the all-zero slot, and every row of it
+            // goes through the MFMAs
+            const int c0 = (int)(BLK * b0 - ds.first);
+            ds.count0 = shared ? c0 : 0x7fffffff;
+            ds.jump = shared ? (int)(BLK * b1 - ds.first) - c0 : 0;
+            ds.count = shared ? c0 + (int)(ds.first + ds.count - BLK * b1) : ds.count;
+            q = shared ? A.winsum + ((long long)li * A.prefix_nblk + b0) * ((long long)C::NTILES * 256) : A.winsum_zero;
+        }
+        // ---- phase A: the shift row (the window's first intraday row), w0
+        double shift[NT], w0v[NT], csum[NT];
+        double usum = 0.0;
+        {
+            const double* p0 = hs.base + hs.first * (long long)hs.ld;
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                const int c = 16 * i + fr;
+                const int cl = c < k ? c : k - 1;
+                shift[i] = p0[coff[i]];      // raw: zeroed beyond column k inside wave_gram (lazy_mask)
+                w0v[i] = A.w0[w * k + cl];
+                csum[i] = 0.0;
+            }
+        }
+        const double mm = (double)hs.count;
+        const double invm = 1.0 / mm;
+        const double rsc = sqrt(n0 * (mm / (mm - 1.0)));           // rows scaled by sqrt(sc): the Gram accumulates S0 = sc C
+        TP_MARK(1);
+        // ---- phase B: slot + Gram of the scaled shifted intraday rows (from row 1: the shift row itself is zero)
+        hs.first += 1; hs.count -= 1;
+        wave_gram<NT, 1, 0, true, true, true>(hs, coff, k, lane, shift, w0v, true, true, acc, nullptr, nullptr, csum, usum, rsc, q);
+        TP_MARK(2);
+        // ---- phase C: the rank-one term of the centring as ONE k-step, acc(I,J) += (-tau_I / m) tau_J in row 0 of the step.
+        // tau = column k+1 (sqrt(sc) sums of the shifted rows) over the asset rows, zero at k and k+1, and at k+2 the
+        // sum of u - element (k+1, k+2).  Afterwards column k+2 is sc C w0 and element (k+2, k+2) is q0.
+        static_for<0, NT>([&](auto Ic) __attribute__((always_inline)) {
+            constexpr int I = decltype(Ic)::value;
+            constexpr int t = wtile(NT, I, kI);
+            if (fr == kc + 1) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = fq + 4 * r;
+                    if (I < kI) lds[C::OFF_VEC + 16 * I + row] = acc[t][r];
+                    else if (row != kc + 2) lds[C::OFF_VEC + 16 * I + row] = row < kc ? acc[t][r] : 0.0;
+                }
+            }
+            if (I == kI && fr == kc + 2) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (fq + 4 * r == kc + 1) lds[C::OFF_VEC + 16 * I + kc + 2] = acc[t][r];
+            }
+        });
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        {
+            double ta[NT], tb[NT];
+#pragma unroll
+            for (int J = 0; J < NT; ++J) {
+                const double tv = lds[C::OFF_VEC + 16 * J + fr];
+                tb[J] = fq == 0 ? tv : 0.0;
+                ta[J] = fq == 0 ? -(tv * invm) : 0.0;
+            }
+            static_for<0, NT>([&](auto Ic) __attribute__((always_inline)) {
+                constexpr int I = decltype(Ic)::value;
+                static_for<I, NT>([&](auto Jc) __attribute__((always_inline)) {
+                    constexpr int J = decltype(Jc)::value;
+                    constexpr int t = wtile(NT, I, J);
+                    wave_mfma_agpr<t>(acc[t], ta[I], tb[J]);
+                });
+            });
+            wave_settle<true>(acc);
+        }
+        // scalars (ref:415-418): q0 = w0'S0 w0 is the element (k+2, k+2) - all four registers read, see `corner`
+        {
+            constexpr int t = wtile(NT, kI, kI);
+            const int kx = kc + 2;
+            const int ln = __builtin_amdgcn_readfirstlane(16 * (kx & 3) + kx);
+            const double x0 = readlane_d(acc[t][0], ln), x1 = readlane_d(acc[t][1], ln);
+            const double x2 = readlane_d(acc[t][2], ln), x3 = readlane_d(acc[t][3], ln);
+            const int rr = kx >> 2;
+            q0 = rr == 0 ? x0 : rr == 1 ? x1 : rr == 2 ? x2 : x3;
+        }
+        const double a = n0 + k + 2;
+        cc = (2 * n0) / (a + sqrt(a * a + 4 * n0 * q0));
+        // border pass, tile column kI only: column k (the slot's t) += c * column k+2 (two lanes up in the row group),
+        // columns beyond k cleared
+        static_for<0, NT>([&](auto Ic) __attribute__((always_inline)) {
+            constexpr int I = decltype(Ic)::value;
+            constexpr int t = wtile(NT, I, kI);
+            d4 x = acc[t];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double up = __shfl(x[r], lane + 2, 64);
+                x[r] = colv ? x[r] : (fr == kc) ? fma(cc, up, x[r]) : 0.0;
+            }
+            acc[t] = x;
+            wave_pin1<t>(acc[t]);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        TP_MARK(3);
+        // ---- phase D: the daily edge rows (ref:180), ones in the border column (t, ref:222); the whole blocks came with the slot
+        TP_MARK(32);
+        double none[NT] = {};
+        double nosum = 0.0;
+        wave_gram<NT, 1, 0, false, true>(ds, coff, k, lane, none, none, false, false, acc, nullptr, nullptr, none, nosum);
+        TP_MARK(33);
+    } else {
     if (conj && dbg != 2) {
         n0 = A.n0[w];
         WRows hs;
@@ -671,6 +886,7 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
             });
         }
     }
+    }   // !PRE
     TP_MARK(34);
     // rows >= k of the bordered matrix are never pivots: clear them (they hold 1'X, n_r, ...)
     static_for<0, NT>([&](auto Ic) __attribute__((always_inline)) {
@@ -980,6 +1196,26 @@ __global__ void __launch_bounds__(64, wave_occupancy(NT)) posterior_wave_kernel(
     wave_window_body<NT, LEAN, MODE>(A, lds);
 }
 
+// the PRE form (wave_window_body): contiguous layout, MODE 0 / 3
+template <int NT, int MODE>
+__global__ void __launch_bounds__(64, wave_occupancy(NT)) posterior_wave_kernel_pre(const tp_kargs_t A) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    wave_window_body<NT, true, MODE, true>(A, lds);
+}
+// Does a batch run the PRE form?  Plain conjugate on the contiguous layout (the caller's MODE / LEAN), shared tables with
+// their all-zero slot (the host leaves winsum_zero null where a prior strength or an intraday row count rules the scaled
+// rows out: plan_shared_gram), columns k+1 and k+2 inside tile column kI, and the option (tp_kopts_t::wave_preload).
+// Where the automatic choice takes it: measured per tile count (alternating runs against the parent build, 10,000 windows,
+// profiles/r19_wave_preload_bench.txt).  It pays where the form with the two passes over the tiles spills - 5 tiles per side
+// (k = 77: -15 %), 7 (k = 100: -3 %), 8 and 9 (k = 120, 140: -21 %, -23 %) - and is +- 0 where neither form spills (k = 55,
+// 90: 4 and 6 tiles); 1 to 3 tiles per side were not measured.  wave_preload = 1 runs it wherever the batch is eligible.
+constexpr bool wave_preload_pays(int nt) { return nt == 5 || nt >= 7; }
+template <int NT>
+inline bool wave_preload_eligible(const tp_kargs_t& a) {
+    const bool wanted = a.opts.wave_preload == 1 || (a.opts.wave_preload < 0 && wave_preload_pays(NT));
+    return wanted && a.winsum != nullptr && a.winsum_zero != nullptr && a.strategy == 0 && a.k - 16 * (NT - 1) <= 13;
+}
+
 // LDS bytes of a launch: the fixed image, plus the staging region of the general layout (sized by the batch's passes)
 template <int NT, bool LEAN>
 inline int wave_lds_bytes(const tp_kargs_t& a) {
@@ -1006,11 +1242,24 @@ hipError_t wave_launch_mode(const tp_kargs_t& a, int grid8, hipStream_t stream) 
     }
 }
 
+template <int NT, int MODE>
+hipError_t wave_launch_pre(const tp_kargs_t& a, int grid8, hipStream_t stream) {
+    const int lds_bytes = wave_lds_bytes<NT, true>(a);
+    static std::atomic<unsigned long long> attr_done{0};      // one bit per device (tp_allow_dynamic_lds)
+    { hipError_t e = tp_allow_dynamic_lds(attr_done, posterior_wave_kernel_pre<NT, MODE>, WAVE_LDS_LIMIT); if (e != hipSuccess) return e; }
+    hipLaunchKernelGGL((posterior_wave_kernel_pre<NT, MODE>), dim3(grid8), dim3(64), lds_bytes, stream, a);
+    return hipGetLastError();
+}
+
 template <int NT, bool LEAN>
 hipError_t wave_launch_variant(const tp_kargs_t& a, int grid, hipStream_t stream, tp_launch_info_t* info) {
     if (info) { info->grid = grid; info->block = 64; info->lds_bytes = wave_lds_bytes<NT, LEAN>(a); info->ntile = NT; }
     const int grid8 = 8 * ((grid + 7) / 8);
     const int mode = wave_mode(a);
+    if constexpr (LEAN) {
+        if (mode == 0 && wave_preload_eligible<NT>(a))
+            return a.out_post != nullptr ? wave_launch_pre<NT, 3>(a, grid8, stream) : wave_launch_pre<NT, 0>(a, grid8, stream);
+    }
     switch (mode == 2 ? 2 : tp_post_mode(a, mode)) {
         case 0: return wave_launch_mode<NT, LEAN, 0>(a, grid8, stream);
         case 1: return wave_launch_mode<NT, LEAN, 1>(a, grid8, stream);

@@ -133,6 +133,11 @@ tp_kargs_t tp_host::make_kargs(tp_batch_t b) {
         const size_t slot = b->p.k <= tp_fused_max_assets() ? tp_fused_slot_doubles(b->p.k) : tp_tiled_slot_doubles(b->p.k);
         a.winsum = (const double*)b->prefix.p + (size_t)b->prefix_nblk * slot;
         for (int i = 0; i < 4; ++i) a.winsum_L[i] = b->winsum_L[i];
+        if (b->winsum_zero) {                            // the all-zero slot behind the last table (plan_shared_gram)
+            int n_L = 0;
+            while (n_L < TP_WINSUM_MAX_L && b->winsum_L[n_L] > 0) ++n_L;
+            a.winsum_zero = a.winsum + (size_t)n_L * (size_t)b->prefix_nblk * slot;
+        }
     }
     a.rhs = (const double*)b->rhs.p;
     a.shift = (const double*)b->shift.p;
@@ -346,6 +351,10 @@ int tp_set_option(tp_handle_t h, const char* name, int value) {
         h->opts.tiled_wave = value;
     }
     else if (n == "tiled_fuse") h->opts.tiled_fuse = value;
+    else if (n == "wave_preload") {
+        if (value < -1 || value > 1) return fail(h, TP_ERR_INVALID, "tp_set_option: wave_preload=%d is not -1, 0 or 1", value);
+        h->opts.wave_preload = value;
+    }
     else if (n == "no_shared_gram") h->no_shared_gram = value != 0;
     else if (n == "tiled_arena_gib") h->tiled_arena_gib = value;
     else if (n == "tiled_arena_mib") h->tiled_arena_mib = value;
@@ -484,7 +493,7 @@ static int upload_common(tp_batch_t b, const tp_inputs_t* in, hipStream_t st, bo
 #undef PUT
     b->panel_ld = in->panel_ld;
     b->hf_ld = conj ? in->hf_ld : 0;
-    rc = plan_shared_gram(b, in);
+    rc = plan_shared_gram(b, in, st);
     if (rc != TP_OK) return rc;
     plan_shared_hf(b, in);
     HIP_TRY(h, span.end(st));

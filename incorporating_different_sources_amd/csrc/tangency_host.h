@@ -118,6 +118,8 @@ struct tp_batch_s {
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)
     int winsum_L[4] = {0, 0, 0, 0};                           // register-tile path: the whole-block counts of the windows
+    bool winsum_zero = false;                                 // register-tile path: the tables end in an all-zero slot and the
+                                                              // batch may start its accumulators from a slot (plan_shared_gram)
     DevBuf t_arena, t_rinv, t_ybar, t_zc, t_scal, t_flags;    // large-k path workspace
     // large-k path, conjugate: shared intraday sums (posterior_tiled_wave.h).  Decided at upload (plan_shared_hf): the
     // windows' intraday rows are contiguous, of one length, and advance by hf_B rows; the tables are per sub-batch
@@ -195,7 +197,7 @@ int64_t tiled_arena_entries(tp_handle_t h, size_t per_entry, size_t held = 0);
 int ensure_tiled_ws(tp_batch_t b, tp_tiled_ws_t* ws, int64_t entries = 0);
 int plan_daily_tables(tp_batch_t b, tp_kargs_t& sub);
 int plan_hf_tables(tp_batch_t b, tp_kargs_t& sub);
-int plan_shared_gram(tp_batch_t b, const tp_inputs_t* in);
+int plan_shared_gram(tp_batch_t b, const tp_inputs_t* in, hipStream_t st);
 void plan_shared_hf(tp_batch_t b, const tp_inputs_t* in);
 
 // tangency_comm.cpp

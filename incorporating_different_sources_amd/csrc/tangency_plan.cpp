@@ -1,5 +1,6 @@
 // tangency_plan.cpp - host layer of libtangency.so: validation of the caller's inputs, upload planning (which shared
 // sums a batch qualifies for) and launch planning of the large-k path (workspace, per-sub-batch tables).
+#include <cmath>
 #include <cstring>
 
 #include "tangency_host.h"
@@ -216,10 +217,11 @@ int plan_hf_tables(tp_batch_t b, tp_kargs_t& sub) {
 // (start[]), no column gather, no per-row risk-free adjustment, k in the register-tile range, and windows that
 // together cover the panel at least three times.  The sums are recomputed by EVERY tp_batch_run (nothing is kept
 // between runs); TP_FLAG_NO_SHARED_GRAM switches the scheme off.
-int plan_shared_gram(tp_batch_t b, const tp_inputs_t* in) {
+int plan_shared_gram(tp_batch_t b, const tp_inputs_t* in, hipStream_t st) {
     tp_handle_t h = b->h;
     b->prefix_nblk = 0;
     b->prefix_per_sub = false;
+    b->winsum_zero = false;
     b->h_start.clear(); b->h_n_rows.clear();
     const tp_params_t& p = b->p;
     if ((p.flags & TP_FLAG_NO_SHARED_GRAM) || h->no_shared_gram) return TP_OK;
@@ -265,8 +267,22 @@ int plan_shared_gram(tp_batch_t b, const tp_inputs_t* in) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 3) return TP_OK;   // never crowd out the batch itself
     if ((size_t)in->panel_ld * 8 * 4096 >= (1ull << 32)) return TP_OK;      // 32-bit offsets inside a segment
-    int rc = ensure(h, b->prefix, bytes, "shared daily block sums");
+    // One more slot behind the tables, all zero and written by no kernel.  The one-wave kernel's preloaded form starts a
+    // window's accumulators from its table slot, and a window without one from this slot.  That form accumulates the
+    // intraday rows scaled by sqrt(n0 m / (m - 1)): a batch with a negative or non-finite prior strength, or a window with
+    // fewer than two intraday rows, keeps the form that scales afterwards (its statuses are the reference there).
+    const size_t slot_bytes = sizeof(double) * tp_fused_slot_doubles(p.k);
+    int rc = ensure(h, b->prefix, bytes + slot_bytes, "shared daily block sums");
     if (rc != TP_OK) return rc;
+    bool pre = p.strategy == TP_STRATEGY_CONJUGATE && in->n0 != nullptr && !in->hf_row_idx;
+    for (int64_t w = 0; pre && w < b->W; ++w) {
+        if (!(in->n0[w] >= 0.0) || !std::isfinite(in->n0[w])) pre = false;
+        if (in->hf_count && in->hf_count[w] < 2) pre = false;
+    }
+    if (pre) {
+        HIP_TRY(h, hipMemsetAsync((char*)b->prefix.p + bytes, 0, slot_bytes, st));      // on the upload's stream, like its copies
+        b->winsum_zero = true;
+    }
     b->prefix_nblk = nblk;
     return TP_OK;
 }

@@ -13,6 +13,14 @@ For every kernel whose name contains `posterior_wave_kernel`, `posterior_wave2_k
 for as long as a result is pending) and reports any instruction that reads or writes a register of an asm MFMA's
 destination less than 19 wait states after that MFMA, other than an MFMA accumulating into exactly that tile.
 Exit code 1 on a finding.  Run by tests/test_cabi_symbols.py::test_wave_kernel_asm_hazards (CPU, cross-compile).
+
+Inline-assembly vector-memory LOADS (the one-wave kernel's preloaded form loads a table slot straight into its
+accumulators) are a second thing the compiler does not see: it neither counts them in its s_waitcnt vmcnt nor knows that
+their destination is not valid yet.  On gfx9 every vector-memory instruction - loads and stores alike - increments vmcnt
+and loads return in order, so the script keeps the issue order of ALL vector-memory instructions, lets `s_waitcnt
+vmcnt(N)` retire all but the youngest N, and reports any instruction - an MFMA included - that names a destination
+register of an inline-assembly load still in flight, and any label or branch met while one is in flight (the loads are
+issued and awaited in straight-line code).
 """
 import re
 import sys
@@ -86,6 +94,43 @@ def step(p, pending, findings, name):
     return False, tgt, op == "s_endpgm"
 
 
+VMEM = re.compile(r"^(global_|buffer_|scratch_|flat_)")
+
+
+def check_asm_loads(name, prog):
+    """Destinations of inline-assembly vector-memory loads: untouched until an s_waitcnt vmcnt has retired the load."""
+    findings, flight, n_loads = [], [], 0       # flight: destination registers per vector-memory instruction, oldest first
+    for p in prog:
+        pend = set().union(*flight) if flight else set()
+        if p[0] == "label":
+            if pend:
+                findings.append((name, p[1] + ": label with inline-assembly loads in flight", sorted(pend)[:4]))
+                flight = [set() for _ in flight]
+            continue
+        text, in_asm = p[1], p[2]
+        op = text.split()[0]
+        if op == "s_waitcnt":
+            m = re.search(r"vmcnt\((\d+)\)", text)
+            if m:
+                n = int(m.group(1))
+                flight = flight[len(flight) - n:] if 0 < n < len(flight) else ([] if n == 0 else flight)
+            continue
+        bad = aregs(text) & pend
+        if pend and (op.startswith("s_cbranch") or op in ("s_branch", "s_endpgm", "s_setpc_b64", "s_swappc_b64")):
+            bad = pend
+        if bad:
+            findings.append((name, text, sorted(bad)[:4]))
+        if VMEM.match(op):
+            dst = set()
+            if in_asm and "load" in op:
+                dst = aregs(text[len(op):].split(",")[0])
+                n_loads += 1
+            flight.append(dst)
+    if any(flight):
+        findings.append((name, "end of kernel with inline-assembly loads in flight", sorted(set().union(*flight))[:4]))
+    return findings, n_loads
+
+
 def check_kernel(name, lines):
     prog = parse(lines)
     labels = {p[1]: i for i, p in enumerate(prog) if p[0] == "label"}
@@ -119,13 +164,15 @@ def check_kernel(name, lines):
             follow(labels[tgt], dict(pending), 0)
         if ends or p[1].split()[0] == "s_branch":
             pending = {}                     # no fall-through behind an unconditional branch
+    load_findings, n_loads = check_asm_loads(name, prog)
+    findings += load_findings
     seen, uniq = set(), []
     for f in findings:
         key = (f[1], tuple(f[2]))
         if key not in seen:
             seen.add(key)
             uniq.append(f)
-    return uniq, n_asm
+    return uniq, n_asm, n_loads
 
 
 def main(path):
@@ -146,9 +193,10 @@ def main(path):
         return 2
     rc, total = 0, 0
     for name, lines in kernels.items():
-        findings, n = check_kernel(name, lines)
+        findings, n, n_loads = check_kernel(name, lines)
         total += n
-        print(f"{name}: {n} inline-asm MFMAs, {len(findings)} hazard finding(s)")
+        loads = f", {n_loads} inline-asm loads" if n_loads else ""
+        print(f"{name}: {n} inline-asm MFMAs{loads}, {len(findings)} hazard finding(s)")
         for f in findings[:10]:
             print("   ", f[1], " touches pending registers", f[2])
         if findings:
@@ -181,12 +229,39 @@ SELFTEST = """_Z21posterior_wave_kernelILi7EEvv:
 """
 
 
+# two slot loads behind a compiler load: vmcnt(2) retires only the compiler's, vmcnt(1) the first asm load as well
+SELFTEST_LOADS = """_Z25posterior_wave_kernel_preILi7ELi0EEvv:
+\tglobal_load_dwordx2 v[46:47], v42, s[4:5]
+\t;;#ASMSTART
+\tglobal_load_dwordx4 a[0:3], v62, s[20:21]
+\tglobal_load_dwordx4 a[4:7], v62, s[20:21] offset:1024
+\t;;#ASMEND
+\ts_waitcnt vmcnt(2)
+\tv_add_f64 v[46:47], v[46:47], v[46:47]
+\tv_accvgpr_read_b32 v3, a9
+\ts_waitcnt vmcnt(1)
+\tv_accvgpr_read_b32 v3, a2
+\tv_accvgpr_read_b32 v3, a5
+\ts_waitcnt vmcnt(0)
+\t;;#ASMSTART
+\ts_nop 1
+\tv_mfma_f64_16x16x4_f64 a[0:7], v[46:47], v[50:51], a[0:7]
+\t;;#ASMEND
+\ts_nop 15
+\ts_nop 7
+\ts_endpgm
+.Lfunc_end0:
+"""
+
+
 def selftest():
     """The accumulating MFMA and the read of a9 are legal; a3 (17 wait states, along the branch) is a finding, a1
-    (22 wait states) is not."""
+    (22 wait states) is not.  Loads: a5 is read while its load is in flight (a finding), a2 and a9 are not."""
     lines = SELFTEST.split("\n")[1:]
-    findings, n = check_kernel("selftest", lines)
-    return n == 2 and [f[2] for f in findings] == [[("a", 3)]]
+    findings, n, _ = check_kernel("selftest", lines)
+    ok = n == 2 and [f[2] for f in findings] == [[("a", 3)]]
+    findings, n, n_loads = check_kernel("selftest", SELFTEST_LOADS.split("\n")[1:])
+    return ok and n == 1 and n_loads == 2 and [f[2] for f in findings] == [[("a", 5)]]
 
 
 if __name__ == "__main__":
