@@ -482,6 +482,59 @@ int tp_batch_window_sweep_tiled(tp_batch_t b, int32_t n_len, const int32_t* N /*
 int tp_batch_download_window_sweep(tp_batch_t b, double* weights /* [W x P x n_len x k] */,
                                    int32_t* status /* [W x P x n_len] */,
                                    double* aux /* [W x P x n_len x TP_AUX_STRIDE] */);
+/* Grid sweep: n_size nested universes x n_len nested window lengths per window - the `size` and `rolling_window` axes of a spec
+ * grid crossed (ref: portfolio_specs.py:71-72) - from ONE pack, ONE upload, ONE pass over the rows of the longest window at the
+ * largest size and ONE factorisation per (window, prior, length).  It rests on both nestings at once: the columns are ordered so
+ * that the smaller universe is a prefix of the larger one (tp_batch_size_sweep) and the shorter window is the tail of the longer
+ * one (tp_batch_window_sweep); the caller vouches for both at every (size, length) (batch.pack_windows_grid checks them).
+ * Entry (w, p, l, s), with k_s = sizes[s], the rows, delta, T_l, t_l and N_l = N[l] of tp_batch_window_sweep:
+ *   conjugate batch: what tp_batch_run returns for a batch of size k_s over the prefix columns and the last rows[w][l] rows,
+ *     minus delta[w][l], with (w0_wps, n0_wpl) uploaded and N = N[l] (not bit for bit: the factorisation differs):
+ *     S1 = (a C + T_l)[:k_s,:k_s], a = n0_wpl m/(m-1) ;  v = C[:k_s,:k_s] w0_wps[:k_s] ;  q0 = a w0_wps'v
+ *     c = 2 n0_wpl / (g + sqrt(g^2 + 4 n0_wpl q0)),  g = n0_wpl + k_s + 2 ;  w1 = S1^-1 (c a v + t_l[:k_s]) ;  n1 = n0_wpl + N_l
+ *     weights[w][p][l][s][:k_s] = (n1 + k_s + 2) w1 / (n1 - w1'S1 w1) / gamma ,   weights[w][p][l][s][k_s:] = 0
+ *   Jeffreys batch: n_prior = 0, n0 = w0 = NULL, the outputs have P = 1: weights[w][0][l][s][:k_s] = M[:k_s,:k_s]^-1 t_l[:k_s] / gamma
+ *     with M = T_l - t_l t_l'/N_l (TP_FLAG_CENTER_BY_ROWS: / rows[w][l]; TP_FLAG_NO_CENTER: M = T_l) - the size sweep's definition
+ *     on length l's rows.
+ * Only the first k_s entries of a w0 vector are read.  The batch's own uploaded w0 / n0, its tp_batch_set_rhs and
+ * tp_batch_set_shift are not used.
+ * TP_ERR_INVALID: a batch that was not uploaded; n_size or n_len outside [1, TP_SWEEP_MAX_RHS]; sizes NULL or not strictly
+ * increasing within [1, k]; N NULL, not strictly increasing or < 1; rows NULL; a rows[w][l] < 1, > n_w or decreasing in l (ties
+ * are allowed); a non-finite delta at a position some length reads; conjugate: n_prior < 1, n0 or w0 NULL, an n0 that is not
+ * finite and > 0, a non-finite w0 inside a prefix; Jeffreys: n_prior != 0 or a non-NULL n0 / w0.  All of them are found before
+ * any device work, and a call refused with TP_ERR_INVALID leaves the results of the last grid sweep in place.
+ * TP_ERR_UNSUPPORTED: k > tp_sweep_max_assets() (also: index-layout windows of more than about 10,000 rows).  TP_ERR_HIP: an
+ * allocation failed (the message names the byte count).
+ * How it runs: sub-ranges of windows as in tp_batch_window_sweep ("sweep_chunk_windows", n_len (conjugate: + 1) k x k matrices
+ * per window inside 256 MiB).  Per sub-range the Gram pass and - with a delta - the delta kernel of tp_batch_window_sweep run
+ * as they are; then one workgroup per (window, prior, length) loads the matrix with the rank-two correction applied from left
+ * to right, parks one right-hand side per size behind it (conjugate: the truncated products C[:k_s,:k_s] w0_wps come from the
+ * same pass over C, masked, never multiplied by zero), factorises ONCE in LDS at k and back-substitutes every size over its own
+ * prefix: n_len x n_prior factorisations per window where one window sweep per size takes n_size times as many.
+ * Promises.  An entry depends on the rows of its own suffix, its delta, its prior, N_l, k_s and k.  It does not depend on the
+ * OTHER sizes of the list, on W, n_prior, the window's position or the sub-ranges: bit for bit.  It depends on the other
+ * lengths to rounding only (the list sets where the partial sums of the Gram are cut).  An all-zero delta gives the bits of
+ * delta == NULL.  A column at or beyond k_s - a duplicate, a zero column, a NaN - does not reach size s; a row older than a
+ * length's suffix never reaches that length.
+ * Device memory: W x P x n_len x n_size x (k + 9) doubles of results, W x P x n_size x k of w0, W x P x n_len of n0,
+ * W x n_len x k of t, with a delta W x n_len x (n_r + k + 2) more, and the sub-range's matrices - buffers of its own, kept until
+ * tp_batch_destroy: every other download, tp_batch_download_window_sweep and _size_sweep included, returns what it returned
+ * before.  Streams, the entry drain, timing (kernel_ms covers every launch; one step of tp_region_steps) and the gather
+ * hand-over are as for tp_batch_window_sweep. */
+int tp_batch_grid_sweep(tp_batch_t b, int32_t n_size, const int32_t* sizes /* [n_size] */,
+                        int32_t n_len, const int32_t* N /* [n_len] */, const int32_t* rows /* [W x n_len] */,
+                        const double* delta /* [W x n_len x n_r] or NULL */,
+                        int32_t n_prior, const double* n0 /* [W x n_prior x n_len] */,
+                        const double* w0 /* [W x n_prior x n_size x k] */);
+/* Waits for the grid sweep and copies out weights [W x P x n_len x n_size x k] (P = n_prior, 1 for a Jeffreys batch), status
+ * [W x P x n_len x n_size] - per entry: TP_STATUS_NOT_PD when a pivot j < k_s is <= 0 or no larger than k_s 2^-52 times its
+ * diagonal element of S1 (of M), e.g. a Jeffreys length of fewer rows than k_s; TP_STATUS_NONFINITE; TP_STATUS_BAD_DENOM
+ * (conjugate): n1 - w1'S1 w1 <= 0 - and aux [W x P x n_len x n_size x TP_AUX_STRIDE] (the slots of tp_batch_download's aux: for
+ * a Jeffreys batch 0 except slot 4, t_l'M^-1 t_l over the prefix); each may be NULL.  Without a grid sweep before it:
+ * TP_ERR_INVALID. */
+int tp_batch_download_grid_sweep(tp_batch_t b, double* weights /* [W x P x n_len x n_size x k] */,
+                                 int32_t* status /* [W x P x n_len x n_size] */,
+                                 double* aux /* [W x P x n_len x n_size x TP_AUX_STRIDE] */);
 int tp_batch_download(tp_batch_t b, double* weights /* [W x k] */, int32_t* status /* [W] */,
                       double* aux /* optional [W x TP_AUX_STRIDE] */); /* waits for the stream, D2H */
 int tp_batch_download_S1(tp_batch_t b, int64_t w, double* S1 /* [k x k] */); /* posterior scale matrix

@@ -48,6 +48,7 @@ EXPORTS = [
     "tp_batch_prior_sweep", "tp_batch_prior_sweep_tiled", "tp_batch_download_prior_sweep",
     "tp_batch_size_sweep", "tp_batch_size_sweep_tiled", "tp_batch_download_size_sweep",
     "tp_batch_window_sweep", "tp_batch_window_sweep_tiled", "tp_batch_download_window_sweep",
+    "tp_batch_grid_sweep", "tp_batch_download_grid_sweep",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
     "tp_comm_count", "tp_comm_init_all", "tp_group_gather",
@@ -126,6 +127,9 @@ def _load():
                                           POINTER(c_double), POINTER(c_double)]
     lib.tp_batch_window_sweep_tiled.argtypes = lib.tp_batch_window_sweep.argtypes
     lib.tp_batch_download_window_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
+    lib.tp_batch_grid_sweep.argtypes = [c_void_p, c_int32, POINTER(c_int32), c_int32, POINTER(c_int32), POINTER(c_int32),
+                                        POINTER(c_double), c_int32, POINTER(c_double), POINTER(c_double)]
+    lib.tp_batch_download_grid_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download_S1.argtypes = [c_void_p, c_int64, POINTER(c_double)]
     lib.tp_batch_download_matrix.argtypes = [c_void_p, c_int64, c_int, POINTER(c_double), POINTER(c_double)]
@@ -778,6 +782,73 @@ class Batch:
         self.dev._check(lib.tp_batch_download_window_sweep(self._b, _ptr(weights if weights.size else None, c_double),
                                                            _ptr(status if status.size else None, c_int32),
                                                            _ptr(aux if aux is not None and aux.size else None, c_double)))
+        return weights, status, aux
+
+    def grid_sweep(self, sizes, N, rows, n0=None, w0=None, delta=None, want_aux=True):
+        """`tp_batch_grid_sweep` + `tp_batch_download_grid_sweep`: S nested universes x L nested window lengths per window -
+        entry (l, s) uses the first `sizes[s]` columns and the last `rows[w, l]` daily rows of the window as uploaded - from ONE
+        pass over the rows and ONE factorisation per (window, prior, length).  `sizes` as in `size_sweep`; `N`, `rows` and
+        `delta` as in `window_sweep`.  Conjugate batch: `n0` [W x P x L] (> 0), `w0` [W x P x S x k] (only the first sizes[s]
+        entries of a vector are read).  Jeffreys batch: no priors, P = 1.  Returns (weights [W, P, L, S, k] - zero beyond
+        sizes[s] -, status [W, P, L, S], aux [W, P, L, S, 8] or None).  The batch's results, settings and kept arrays and the
+        other sweeps' results are left alone."""
+        W, k = self.W, self.k
+        if sizes is None or np.asarray(sizes).dtype.kind not in "iu":
+            raise ValueError("sizes: a sequence of integers is expected")
+        sz = np.ascontiguousarray(sizes, dtype=np.int32)
+        if sz.ndim != 1 or not 1 <= sz.size <= SWEEP_MAX_RHS:
+            raise ValueError(f"sizes: between 1 and {SWEEP_MAX_RHS} sizes expected, got shape {tuple(sz.shape)}")
+        if sz[0] < 1 or sz[-1] > k or (np.diff(sz) <= 0).any():
+            raise ValueError(f"sizes: strictly increasing within [1, {k}] expected, got {sz.tolist()}")
+        S = int(sz.size)
+        if N is None or np.asarray(N).dtype.kind not in "iu":
+            raise ValueError("N: a sequence of integers is expected")
+        Nl = np.ascontiguousarray(N, dtype=np.int32)
+        if Nl.ndim != 1 or not 1 <= Nl.size <= SWEEP_MAX_RHS:
+            raise ValueError(f"N: between 1 and {SWEEP_MAX_RHS} lengths expected, got shape {tuple(Nl.shape)}")
+        L = int(Nl.size)
+        if rows is None or np.asarray(rows).dtype.kind not in "iu":
+            raise ValueError("rows: an integer array is expected")
+        rw = np.ascontiguousarray(rows, dtype=np.int32)
+        if rw.shape != (W, L):
+            raise ValueError(f"rows: expected shape ({W}, {L}), got {tuple(rw.shape)}")
+        if delta is not None:
+            if np.asarray(delta).dtype.kind not in "fiu":
+                raise ValueError(f"delta: a real floating-point array is expected, got dtype {np.asarray(delta).dtype}")
+            delta = np.ascontiguousarray(delta, dtype=np.float64)
+            if delta.shape != (W, L, self.n_r):
+                raise ValueError(f"delta: expected shape ({W}, {L}, {self.n_r}), got {tuple(delta.shape)}")
+        if (n0 is None) != (w0 is None):
+            raise ValueError("n0 and w0: both (conjugate batch) or neither (Jeffreys batch) expected")
+        P = 1
+        if n0 is not None:
+            for name, a in (("n0", n0), ("w0", w0)):
+                if np.asarray(a).dtype.kind not in "fiu":
+                    raise ValueError(f"{name}: a real floating-point array is expected, got dtype {np.asarray(a).dtype}")
+            n0 = np.ascontiguousarray(n0, dtype=np.float64)
+            w0 = np.ascontiguousarray(w0, dtype=np.float64)
+            if n0.ndim != 3 or n0.shape[0] != W or n0.shape[1] < 1 or n0.shape[2] != L:
+                raise ValueError(f"n0: expected shape ({W}, P, {L}) with P >= 1, got {tuple(n0.shape)}")
+            P = n0.shape[1]
+            if w0.shape != (W, P, S, k):
+                raise ValueError(f"w0: expected shape ({W}, {P}, {S}, {k}), got {tuple(w0.shape)}")
+        weights = np.empty((W, P, L, S, k), dtype=np.float64)
+        status = np.empty((W, P, L, S), dtype=np.int32)
+        aux = np.empty((W, P, L, S, AUX_STRIDE), dtype=np.float64) if want_aux else None
+        # (W = 0: the library still wants non-NULL arrays)
+        rwp = rw if rw.size else np.ones(1, dtype=np.int32)
+        dp = None if delta is None or not delta.size else delta
+        if n0 is None:
+            self.dev._check(lib.tp_batch_grid_sweep(self._b, S, _ptr(sz, c_int32), L, _ptr(Nl, c_int32), _ptr(rwp, c_int32),
+                                                    _ptr(dp, c_double), 0, None, None))
+        else:
+            n0p = n0 if n0.size else np.ones(1)
+            w0p = w0 if w0.size else np.zeros(1)
+            self.dev._check(lib.tp_batch_grid_sweep(self._b, S, _ptr(sz, c_int32), L, _ptr(Nl, c_int32), _ptr(rwp, c_int32),
+                                                    _ptr(dp, c_double), P, _ptr(n0p, c_double), _ptr(w0p, c_double)))
+        self.dev._check(lib.tp_batch_download_grid_sweep(self._b, _ptr(weights if weights.size else None, c_double),
+                                                         _ptr(status if status.size else None, c_int32),
+                                                         _ptr(aux if aux is not None and aux.size else None, c_double)))
         return weights, status, aux
 
     def download(self, want_aux=True, out=None):

@@ -384,6 +384,44 @@ def pack_windows(trading_dates, portfolio_spec, market_data, members_of=None, re
     return kw, labels
 
 
+def _nan_only_beyond(nan_block, ks):
+    """some row has a NaN beyond column ks and none before it"""
+    return bool((nan_block[:, ks:].any(axis=1) & ~nan_block[:, :ks].any(axis=1)).any())
+
+
+def _candidate_nan_blocks(mp, freq, N, conj, ts, pos, cols):
+    """(daily [rows x k], intraday [bars x k] or None): where the candidate rows of the window of length N at `ts` - before
+    dropna, as pack_windows forms them, minus the rows a NaN risk-free day drops at any size - and the candidate intraday bars
+    (conjugate) are NaN per selected column."""
+    d = pd.Timestamp(ts).value
+    if freq == "daily":
+        first_price = max(0, pos - N + 1)
+        lab0, lab1 = first_price, pos
+        if (mp.L_nan_cum[pos + 1, cols] != mp.L_nan_cum[first_price + 1, cols]).any():
+            daily_nan = mp.L_nan[np.arange(first_price + 1, pos + 1, dtype=np.int64)][:, cols]
+        else:                                        # no NaN return of a selected asset in the window: nothing to gather
+            daily_nan = np.zeros((lab1 - lab0, len(cols)), dtype=bool)
+    else:
+        b = int(mp.bin_of[pos])
+        first_bin = max(0, b - N + 1)
+        daily_nan = mp.L_nan[np.arange(first_bin + 1, b, dtype=np.int64)][:, cols]
+        if b > first_bin:
+            daily_nan = np.vstack([daily_nan, _return_is_nan(mp.P[pos], mp.R[b - 1])[cols][None, :]])
+        lab0, lab1 = first_bin, b
+    daily_nan = daily_nan[~np.isnan(mp.rf_at_label[lab0 + 1:lab1 + 1])]      # a NaN risk-free day drops the row at any size
+    hf_nan = None
+    if conj:
+        span = _CALENDAR_DAYS[freq]
+        a = int(np.searchsorted(mp.hf_ns, d - span * _NS_PER_DAY + _NS_PER_DAY, side="right"))
+        end_of_day = pd.Timestamp(ts).replace(hour=23, minute=59, second=59).value
+        e = int(np.searchsorted(mp.hf_ns, min(d + _NS_PER_DAY, end_of_day), side="right"))
+        if e > a + 1 and mp.H_rownan_cum[e] != mp.H_rownan_cum[a + 1]:      # some bar of the span has a NaN somewhere
+            hf_nan = mp.H_nan[np.arange(a + 1, e, dtype=np.int64)][:, cols]
+        else:
+            hf_nan = np.zeros((0, len(cols)), dtype=bool)
+    return daily_nan, hf_nan
+
+
 def pack_windows_nested(trading_dates, portfolio_spec, sizes, market_data, members_of=None):
     """`pack_windows` at max(sizes) for a size sweep (`_native.Batch.size_sweep`): (kw, labels, caps [W x k], mask [W x S]).
     mask[w, s] says whether the universe of size sizes[s] at date w can be served from the pack as its first sizes[s] columns:
@@ -406,44 +444,14 @@ def pack_windows_nested(trading_dates, portfolio_spec, sizes, market_data, membe
     all_members = np.ones(len(mp.tickers), dtype=bool)
     mask = np.ones((len(trading_dates), len(sizes)), dtype=bool)
 
-    def only_beyond(nan_block, ks):
-        """some row has a NaN beyond column ks and none before it"""
-        return bool((nan_block[:, ks:].any(axis=1) & ~nan_block[:, :ks].any(axis=1)).any())
-
     for w, ts in enumerate(trading_dates):
-        d = pd.Timestamp(ts).value
         pos, members = _date_position_and_members(mp, ts, members_of, all_members)
         cols = kw["col_idx"][w]
-        # candidate rows of the window before dropna, as pack_windows forms them, and where they are NaN per selected column
-        if freq == "daily":
-            first_price = max(0, pos - N + 1)
-            lab0, lab1 = first_price, pos
-            if (mp.L_nan_cum[pos + 1, cols] != mp.L_nan_cum[first_price + 1, cols]).any():
-                daily_nan = mp.L_nan[np.arange(first_price + 1, pos + 1, dtype=np.int64)][:, cols]
-            else:                                        # no NaN return of a selected asset in the window: nothing to gather
-                daily_nan = np.zeros((lab1 - lab0, len(cols)), dtype=bool)
-        else:
-            b = int(mp.bin_of[pos])
-            first_bin = max(0, b - N + 1)
-            daily_nan = mp.L_nan[np.arange(first_bin + 1, b, dtype=np.int64)][:, cols]
-            if b > first_bin:
-                daily_nan = np.vstack([daily_nan, _return_is_nan(mp.P[pos], mp.R[b - 1])[cols][None, :]])
-            lab0, lab1 = first_bin, b
-        daily_nan = daily_nan[~np.isnan(mp.rf_at_label[lab0 + 1:lab1 + 1])]      # a NaN risk-free day drops the row at any size
-        hf_nan = None
-        if conj:
-            span = _CALENDAR_DAYS[freq]
-            a = int(np.searchsorted(mp.hf_ns, d - span * _NS_PER_DAY + _NS_PER_DAY, side="right"))
-            end_of_day = pd.Timestamp(ts).replace(hour=23, minute=59, second=59).value
-            e = int(np.searchsorted(mp.hf_ns, min(d + _NS_PER_DAY, end_of_day), side="right"))
-            if e > a + 1 and mp.H_rownan_cum[e] != mp.H_rownan_cum[a + 1]:      # some bar of the span has a NaN somewhere
-                hf_nan = mp.H_nan[np.arange(a + 1, e, dtype=np.int64)][:, cols]
-            else:
-                hf_nan = np.zeros((0, len(cols)), dtype=bool)
+        daily_nan, hf_nan = _candidate_nan_blocks(mp, freq, N, conj, ts, pos, cols)
         for s, ks in enumerate(sizes[:-1]):
             sub, _ = select_universe(mp, pos, ks, window_days, spec["rebalancing_frequency"], members)
-            mask[w, s] = (len(sub) == ks and np.array_equal(sub, cols[:ks]) and not only_beyond(daily_nan, ks)
-                          and not (conj and only_beyond(hf_nan, ks)))
+            mask[w, s] = (len(sub) == ks and np.array_equal(sub, cols[:ks]) and not _nan_only_beyond(daily_nan, ks)
+                          and not (conj and _nan_only_beyond(hf_nan, ks)))
     return kw, labels, caps, mask
 
 
@@ -521,6 +529,55 @@ def pack_windows_lengths(trading_dates, portfolio_spec, windows, market_data, me
                     delta[w, l, n_w - r:n_w] = adj[kept] - kw["rf_adj"][w, n_w - r:n_w]
             mask[w, l] = ok
         rows[w] = np.maximum.accumulate(rows[w])
+    return kw, labels, caps, rows, delta, mask
+
+
+def pack_windows_grid(trading_dates, portfolio_spec, sizes, windows, market_data, members_of=None):
+    """ONE `pack_windows` at (max(sizes), max(windows)) for a grid sweep (`_native.Batch.grid_sweep`):
+    (kw, labels, caps [W x k], rows [W x L], delta [W x L x n_r], mask [W x S x L]).
+    kw, rows and delta are `pack_windows_lengths`'s at the largest size: the suffix a length uses and its risk-free correction
+    do not depend on the size.  mask[w, s, l] says whether the spec (sizes[s], windows[l]) at date w can be served from the pack
+    as its first sizes[s] columns and last rows[w, l] rows:
+      * `pack_windows_lengths`'s conditions for length l at the LARGEST size (universe, completeness, gap assertion, a row) -
+        a stock that enters the short window's universe below the prefix switches the prefix off with it: a false negative;
+      * `select_universe` at (sizes[s], that length's `window_days`) returns the prefix in the pack's order - selected again and
+        compared wherever the length's eligibility threshold admits other stocks than the longest window's (verified, not
+        assumed), otherwise the comparison at the longest window stands;
+      * no candidate row of the LONGEST window, daily or intraday, was dropped because of a NaN in a column beyond the prefix
+        alone - sufficient for every suffix (a NaN outside a shorter suffix costs that pair a fallback, never a wrong result).
+    `portfolio_spec["size"]` and `["rolling_window"]` are not read.  Raises what `pack_windows` raises at the largest size and
+    the longest window."""
+    sizes = [int(s) for s in sizes]
+    if not sizes or any(b <= a for a, b in zip(sizes, sizes[1:])) or sizes[0] < 1:
+        raise ValueError(f"sizes: a strictly increasing list of positive sizes expected, got {sizes}")
+    spec = dict(portfolio_spec, size=sizes[-1])
+    kw, labels, caps, rows, delta, mask_len = pack_windows_lengths(trading_dates, spec, windows, market_data, members_of=members_of)
+    windows = [int(n) for n in windows]
+    freq = spec["rolling_window_frequency"]
+    conj = spec["weighting_strategy"].startswith("conjugate")
+    mp = panels_for(market_data, freq)
+    all_members = np.ones(len(mp.tickers), dtype=bool)
+    mask = np.repeat(mask_len[:, None, :], len(sizes), axis=1)
+    long_days = windows[-1] * _TRADING_DAYS[freq]
+    for w, ts in enumerate(trading_dates):
+        pos, members = _date_position_and_members(mp, ts, members_of, all_members)
+        cols = kw["col_idx"][w]
+        daily_nan, hf_nan = _candidate_nan_blocks(mp, freq, windows[-1], conj, ts, pos, cols)
+        run = mp.valid_run[pos]
+        eligible_long = run >= min(long_days, pos + 1)
+        for s, ks in enumerate(sizes[:-1]):
+            if _nan_only_beyond(daily_nan, ks) or (conj and _nan_only_beyond(hf_nan, ks)):
+                mask[w, s] = False
+                continue
+            sub, _ = select_universe(mp, pos, ks, long_days, spec["rebalancing_frequency"], members)
+            prefix_long = len(sub) == ks and np.array_equal(sub, cols[:ks])
+            for l, N in enumerate(windows):
+                window_days = N * _TRADING_DAYS[freq]
+                ok = prefix_long
+                if mask[w, s, l] and not np.array_equal(run >= min(window_days, pos + 1), eligible_long):
+                    sub, _ = select_universe(mp, pos, ks, window_days, spec["rebalancing_frequency"], members)
+                    ok = len(sub) == ks and np.array_equal(sub, cols[:ks])
+                mask[w, s, l] &= ok
     return kw, labels, caps, rows, delta, mask
 
 

@@ -12,6 +12,7 @@
 #include "../../include/tangency_posterior.h"
 #include "host_resources.h"
 #include "posterior_kernels.h"
+#include "posterior_grid_sweep.h"
 #include "posterior_prior_sweep.h"
 #include "posterior_size_sweep.h"
 #include "posterior_size_sweep_tiled.h"
@@ -49,7 +50,7 @@ struct tp_handle_s {
     int hf_share_min_blocks = 6;    // "hf_share_min_blocks": whole intraday blocks per window from which the large-k path shares them
     int tiled_arena_gib = 0;        // TP_TILED_ARENA_GIB / "tiled_arena_gib" (0: default)
     int tiled_arena_mib = 0;        // TP_TILED_ARENA_MIB / "tiled_arena_mib": a sub-GiB arena (tests: many sub-batches from few windows)
-    int sweep_chunk_windows = 0;    // "sweep_chunk_windows": windows per sub-range of tp_batch_solve_sweep / _prior_sweep / _size_sweep / _window_sweep (0: automatic)
+    int sweep_chunk_windows = 0;    // "sweep_chunk_windows": windows per sub-range of tp_batch_solve_sweep / _prior_sweep / _size_sweep / _window_sweep / _grid_sweep (0: automatic)
     int phase_limit = 0;            // TP_PHASE_LIMIT (diagnostic builds only)
     std::vector<tp_batch_t> batches;   // live batches of this handle (destroyed with it if the caller forgot them)
     // per-step kernel times inside a tp_region_begin / tp_region_end bracket: every timed launch of the region records
@@ -102,6 +103,13 @@ struct WindowSweepWs {
     int P = 0, L = 0;               // shape of the last sweep (0: none yet)
 };
 
+// Grid sweep (`gr`): the window sweep's buffers - C, the snapshots, the delta sums, the results at [W x P x L x S] - of its
+// own, so that tp_batch_download_window_sweep returns what it returned before, and the universes' sizes.
+struct GridSweepWs : WindowSweepWs {
+    DevBuf sizes;                   // [S]
+    int S = 0;                      // sizes of the last sweep (0: none yet)
+};
+
 struct tp_batch_s {
     tp_handle_t h = nullptr;
     tp_params_t p{};
@@ -114,6 +122,7 @@ struct tp_batch_s {
     SolveSweepWs sw;                                          // tp_batch_solve_sweep / _solve_sweep_tiled
     PriorSweepWs ps, zs;                                      // tp_batch_prior_sweep / _prior_sweep_tiled; tp_batch_size_sweep / _size_sweep_tiled
     WindowSweepWs wn;                                         // tp_batch_window_sweep / _window_sweep_tiled
+    GridSweepWs gr;                                           // tp_batch_grid_sweep
     PriceStaging fe, fe_hf;                                   // daily and intraday (freed after a synchronous upload)
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)

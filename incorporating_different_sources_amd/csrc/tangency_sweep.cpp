@@ -1,5 +1,5 @@
 // tangency_sweep.cpp - the sweeps of the C-ABI of libtangency.so (include/tangency_posterior.h): many solves per window
-// from one Gram pass - tp_batch_solve_sweep, _prior_sweep, _size_sweep, _window_sweep, the four tiled forms above
+// from one Gram pass - tp_batch_solve_sweep, _prior_sweep, _size_sweep, _window_sweep, _grid_sweep, the four tiled forms above
 // tp_sweep_max_assets(), and their downloads.  Every sweep is: checks, a drain of the handle's stream, its workspace (SolveSweepWs / PriorSweepWs,
 // tangency_host.h), then per sub-range of windows a Gram stage and a solve stage inside one timed span.
 #include <cmath>
@@ -218,6 +218,28 @@ int ensure_sweep_tiled_ws(tp_batch_t b, int R, int64_t entries, tp_tiled_ws_t* w
 // sub-range (C and T: two k x k matrices per window), the sweep's buffers and the copies of the caller's arrays.
 // *chunk_out = 0: W = 0, nothing to launch (the sweep's shape is set).
 struct SizeAxis { int32_t n_size; const int32_t* sizes; };
+
+int check_size_axis(tp_handle_t h, const char* name, const SizeAxis& sz, int k) {
+    if (sz.n_size < 1 || sz.n_size > TP_SWEEP_MAX_RHS)
+        return fail(h, TP_ERR_INVALID, "%s: n_size=%d outside [1, %d]", name, sz.n_size, TP_SWEEP_MAX_RHS);
+    if (!sz.sizes) return fail(h, TP_ERR_INVALID, "%s: sizes is NULL", name);
+    for (int s = 0; s < sz.n_size; ++s)
+        if (sz.sizes[s] < 1 || sz.sizes[s] > k || (s > 0 && sz.sizes[s] <= sz.sizes[s - 1]))
+            return fail(h, TP_ERR_INVALID, "%s: sizes[%d]=%d: strictly increasing sizes within [1, %d] expected", name, s, sz.sizes[s], k);
+    return TP_OK;
+}
+
+// w0 [pairs x S x k] of the caller (`sz` == nullptr: S = 1): finite - with sizes, inside each vector's prefix only (a size sweep
+// reads the first sizes[s] entries of a vector)
+int check_finite_w0(tp_handle_t h, const char* name, const double* w0, int64_t pairs, int k, const SizeAxis* sz) {
+    const int S = sz ? sz->n_size : 1;
+    for (int64_t e = 0; e < pairs * S; ++e) {
+        const int ke = sz ? sz->sizes[e % S] : k;
+        for (int i = 0; i < ke; ++i)
+            if (!std::isfinite(w0[e * k + i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)(e * k + i));
+    }
+    return TP_OK;
+}
 int prior_sweep_prepare(tp_batch_t b, PriorSweepWs& ws, const char* name, bool tiled, int32_t n_prior, const double* n0,
                         const double* w0, int64_t* chunk_out, const SizeAxis* sz = nullptr) {
     tp_handle_t h = b->h;
@@ -228,12 +250,8 @@ int prior_sweep_prepare(tp_batch_t b, PriorSweepWs& ws, const char* name, bool t
     if (!sz && !conj) return fail(h, TP_ERR_INVALID, "%s applies to the conjugate strategy only", name);
     if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
     if (sz) {
-        if (sz->n_size < 1 || sz->n_size > TP_SWEEP_MAX_RHS)
-            return fail(h, TP_ERR_INVALID, "%s: n_size=%d outside [1, %d]", name, sz->n_size, TP_SWEEP_MAX_RHS);
-        if (!sz->sizes) return fail(h, TP_ERR_INVALID, "%s: sizes is NULL", name);
-        for (int s = 0; s < sz->n_size; ++s)
-            if (sz->sizes[s] < 1 || sz->sizes[s] > k || (s > 0 && sz->sizes[s] <= sz->sizes[s - 1]))
-                return fail(h, TP_ERR_INVALID, "%s: sizes[%d]=%d: strictly increasing sizes within [1, %d] expected", name, s, sz->sizes[s], k);
+        const int rcs = check_size_axis(h, name, *sz, k);
+        if (rcs != TP_OK) return rcs;
     }
     if (sz && !conj && (n_prior != 0 || n0 || w0))
         return fail(h, TP_ERR_INVALID, "%s: a Jeffreys batch takes no priors (n_prior = 0, n0 = w0 = NULL)", name);
@@ -245,11 +263,8 @@ int prior_sweep_prepare(tp_batch_t b, PriorSweepWs& ws, const char* name, bool t
         if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "%s: %s is NULL", name, !n0 ? "n0" : "w0");
         rc = check_finite_sign(h, name, "n0", n0, W * P, true);
         if (rc != TP_OK) return rc;
-        for (int64_t e = 0; e < W * P * S; ++e) {          // (a size sweep reads the first sizes[s] entries of a vector only)
-            const int ke = sz ? sz->sizes[e % S] : k;
-            for (int i = 0; i < ke; ++i)
-                if (!std::isfinite(w0[e * k + i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)(e * k + i));
-        }
+        rc = check_finite_w0(h, name, w0, W * P, k, sz);
+        if (rc != TP_OK) return rc;
     }
     rc = check_sweep_k(h, tiled, name, sz ? "tp_batch_size_sweep" : "tp_batch_prior_sweep", k);
     if (rc != TP_OK) return rc;
@@ -347,12 +362,14 @@ int download_prior_ws(tp_batch_t b, const PriorSweepWs& ws, double* weights, int
 // What the two window sweeps share - tp_batch_window_sweep (`tiled` = false, k <= tp_sweep_max_assets()) and
 // tp_batch_window_sweep_tiled (above it): the argument checks, the k range, the drain, the checks against the windows' own row
 // counts, the windows per sub-range (L snapshots - conjugate: and C - per window), the sweep's buffers and the copies of the
-// caller's arrays.  A call refused for its arguments leaves the last sweep's shape and results in place.
+// caller's arrays - into `ws`, the window sweeps' or the grid sweep's (`sz` given: n_size universes per (window, prior, length),
+// w0 per (window, prior, size) and read inside its prefix only, results per (window, prior, length, size); the sizes themselves
+// are the caller's to store).  A call refused for its arguments leaves the last sweep's shape and results in place.
 // *chunk_out = 0: W = 0, nothing to launch (the sweep's shape is set).
-int window_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_len, const int32_t* N, const int32_t* rows,
-                         const double* delta, int32_t n_prior, const double* n0, const double* w0, int64_t* chunk_out) {
+int window_sweep_prepare(tp_batch_t b, WindowSweepWs& ws, const char* name, bool tiled, int32_t n_len, const int32_t* N,
+                         const int32_t* rows, const double* delta, int32_t n_prior, const double* n0, const double* w0,
+                         int64_t* chunk_out, const SizeAxis* sz = nullptr) {
     tp_handle_t h = b->h;
-    WindowSweepWs& ws = b->wn;
     const int k = b->p.k, n_r = b->p.n_r;
     const int64_t W = b->W;
     const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
@@ -365,16 +382,18 @@ int window_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_l
         if (N[l] < 1 || (l > 0 && N[l] <= N[l - 1]))
             return fail(h, TP_ERR_INVALID, "%s: N[%d]=%d: strictly increasing lengths >= 1 expected", name, l, N[l]);
     if (!rows) return fail(h, TP_ERR_INVALID, "%s: rows is NULL", name);
+    int rc = sz ? check_size_axis(h, name, *sz, k) : TP_OK;
+    if (rc != TP_OK) return rc;
     const int L = n_len;
     const int P = conj ? n_prior : 1;
-    int rc = TP_OK;
+    const int S = sz ? sz->n_size : 1;
     if (conj) {
         if (n_prior < 1) return fail(h, TP_ERR_INVALID, "%s: n_prior=%d < 1", name, n_prior);
         if (!n0 || !w0) return fail(h, TP_ERR_INVALID, "%s: %s is NULL", name, !n0 ? "n0" : "w0");
         rc = check_finite_sign(h, name, "n0", n0, W * P * L, true);
         if (rc != TP_OK) return rc;
-        for (int64_t i = 0; i < W * P * k; ++i)
-            if (!std::isfinite(w0[i])) return fail(h, TP_ERR_INVALID, "%s: w0[%lld] must be finite", name, (long long)i);
+        rc = check_finite_w0(h, name, w0, W * P, k, sz);
+        if (rc != TP_OK) return rc;
     } else if (n_prior != 0 || n0 || w0) {
         return fail(h, TP_ERR_INVALID, "%s: a Jeffreys batch takes no priors (n_prior = 0, n0 = w0 = NULL)", name);
     }
@@ -404,6 +423,7 @@ int window_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_l
     const int64_t chunk = sweep_chunk(h, (size_t)(L + (conj ? 1 : 0)) * mat_bytes, (int64_t)P * L, W, true,
                                       tiled ? TP_WINDOW_SWEEP_TILED_WORKSPACE_BYTES : TP_SWEEP_WORKSPACE_BYTES);
     const size_t WL = (size_t)W * (size_t)L, WPL = WL * (size_t)P;
+    const size_t WPS = (size_t)W * (size_t)P * (size_t)S, WPLS = WPL * (size_t)S;
     const std::string what = std::string(name) + ": ";
     if (conj) rc = ensure(h, ws.C, mat_bytes * (size_t)chunk, (what + "intraday scatters of one sub-range").c_str());
     if (rc == TP_OK) rc = ensure(h, ws.T, mat_bytes * (size_t)chunk * L, (what + "daily Gram snapshots of one sub-range").c_str());
@@ -411,20 +431,20 @@ int window_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_l
     if (rc == TP_OK) rc = ensure(h, ws.N, sizeof(int32_t) * (size_t)L, (what + "lengths").c_str());
     if (rc == TP_OK) rc = ensure(h, ws.rows, sizeof(int32_t) * WL, (what + "row counts").c_str());
     if (rc == TP_OK && conj) rc = ensure(h, ws.n0, sizeof(double) * WPL, (what + "prior strengths").c_str());
-    if (rc == TP_OK && conj) rc = ensure(h, ws.w0, sizeof(double) * (size_t)W * P * k, (what + "prior weights").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, ws.w0, sizeof(double) * WPS * k, (what + "prior weights").c_str());
     if (rc == TP_OK && delta) rc = ensure(h, ws.delta, sizeof(double) * WL * n_r, (what + "row offsets").c_str());
     if (rc == TP_OK && delta) rc = ensure(h, ws.dv, sizeof(double) * WL * k, (what + "offset-weighted column sums").c_str());
     if (rc == TP_OK && delta) rc = ensure(h, ws.ds, sizeof(double) * WL * 2, (what + "offset sums").c_str());
-    if (rc == TP_OK) rc = ensure(h, ws.weights, sizeof(double) * WPL * k, (what + "weights").c_str());
-    if (rc == TP_OK) rc = ensure(h, ws.status, sizeof(int32_t) * WPL, (what + "statuses").c_str());
-    if (rc == TP_OK) rc = ensure(h, ws.aux, sizeof(double) * WPL * TP_AUX_STRIDE, (what + "aux").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.weights, sizeof(double) * WPLS * k, (what + "weights").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.status, sizeof(int32_t) * WPLS, (what + "statuses").c_str());
+    if (rc == TP_OK) rc = ensure(h, ws.aux, sizeof(double) * WPLS * TP_AUX_STRIDE, (what + "aux").c_str());
     if (rc != TP_OK) return rc;
     // the caller's arrays: copied here, no host pointer is kept
     HIP_TRY(h, hipMemcpyAsync(ws.N.p, N, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(ws.rows.p, rows, sizeof(int32_t) * WL, hipMemcpyHostToDevice, h->stream));
     if (conj) {
         HIP_TRY(h, hipMemcpyAsync(ws.n0.p, n0, sizeof(double) * WPL, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(ws.w0.p, w0, sizeof(double) * (size_t)W * P * k, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(ws.w0.p, w0, sizeof(double) * WPS * k, hipMemcpyHostToDevice, h->stream));
     }
     if (delta) HIP_TRY(h, hipMemcpyAsync(ws.delta.p, delta, sizeof(double) * WL * n_r, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
@@ -432,9 +452,8 @@ int window_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_l
     return TP_OK;
 }
 
-// the segmented Gram's and the delta kernel's arguments, the same for both window sweeps
-void window_gram_delta_kargs(tp_batch_t b, int L, tp_window_gram_kargs_t* ga_out, tp_window_delta_kargs_t* da_out) {
-    const WindowSweepWs& ws = b->wn;
+// the segmented Gram's and the delta kernel's arguments over the buffers of `ws`, the same for both window sweeps and the grid sweep
+void window_gram_delta_kargs(tp_batch_t b, const WindowSweepWs& ws, int L, tp_window_gram_kargs_t* ga_out, tp_window_delta_kargs_t* da_out) {
     tp_window_gram_kargs_t ga;
     memset(&ga, 0, sizeof ga);
     ga.in = neutral_kargs(b);
@@ -771,11 +790,11 @@ int tp_batch_window_sweep(tp_batch_t b, int32_t n_len, const int32_t* N, const i
     const int L = n_len;
     const int P = conj ? n_prior : 1;
     int64_t chunk = 0;
-    const int rc = window_sweep_prepare(b, name, false, n_len, N, rows, delta, n_prior, n0, w0, &chunk);
+    const int rc = window_sweep_prepare(b, ws, name, false, n_len, N, rows, delta, n_prior, n0, w0, &chunk);
     if (rc != TP_OK || chunk == 0) return rc;
     tp_window_gram_kargs_t ga;
     tp_window_delta_kargs_t da;
-    window_gram_delta_kargs(b, L, &ga, &da);
+    window_gram_delta_kargs(b, ws, L, &ga, &da);
     tp_window_sweep_kargs_t sa;
     memset(&sa, 0, sizeof sa);
     sa.C = conj ? (const double*)ws.C.p : nullptr;
@@ -823,7 +842,7 @@ int tp_batch_window_sweep_tiled(tp_batch_t b, int32_t n_len, const int32_t* N, c
     const int L = n_len;
     const int P = conj ? n_prior : 1;
     int64_t chunk = 0;
-    int rc = window_sweep_prepare(b, name, true, n_len, N, rows, delta, n_prior, n0, w0, &chunk);
+    int rc = window_sweep_prepare(b, wn, name, true, n_len, N, rows, delta, n_prior, n0, w0, &chunk);
     if (rc != TP_OK || chunk == 0) return rc;
     // the batch's own tiled workspace: the Gram stage of C, then the entries; staging rows for one group of entries
     tp_tiled_ws_t ws;
@@ -844,7 +863,7 @@ int tp_batch_window_sweep_tiled(tp_batch_t b, int32_t n_len, const int32_t* N, c
     (void)ta;
     tp_window_gram_kargs_t ga;
     tp_window_delta_kargs_t da;
-    window_gram_delta_kargs(b, L, &ga, &da);
+    window_gram_delta_kargs(b, wn, L, &ga, &da);
     tp_window_sweep_tiled_kargs_t sa;
     memset(&sa, 0, sizeof sa);
     sa.C = conj ? (const double*)wn.C.p : nullptr;
@@ -906,6 +925,71 @@ int tp_batch_download_window_sweep(tp_batch_t b, double* weights, int32_t* statu
     if (ws.P < 1 || ws.L < 1) return fail(h, TP_ERR_INVALID, "tp_batch_download_window_sweep: no tp_batch_window_sweep before it");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t n = (size_t)b->W * ws.P * ws.L;
+    return download(h, {{weights, ws.weights.p, sizeof(double) * n * b->p.k}, {status, ws.status.p, sizeof(int32_t) * n},
+                        {aux, ws.aux.p, sizeof(double) * n * TP_AUX_STRIDE}});
+}
+
+// Grid sweep.  The window sweep's sub-ranges and Gram stages - the segmented Gram pass stores C once and (T_l, t_l) per length at
+// the batch's k, the delta kernel forms the sums of the rank-two correction - into the grid sweep's own workspace; then
+// posterior_grid_sweep_kernel factorises every (window, prior, length) once at k and solves every size over its prefix.
+int tp_batch_grid_sweep(tp_batch_t b, int32_t n_size, const int32_t* sizes, int32_t n_len, const int32_t* N, const int32_t* rows,
+                        const double* delta, int32_t n_prior, const double* n0, const double* w0) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    GridSweepWs& ws = b->gr;
+    const char* name = "tp_batch_grid_sweep";
+    const int k = b->p.k, n_r = b->p.n_r;
+    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
+    const int L = n_len, S = n_size;
+    const int P = conj ? n_prior : 1;
+    const SizeAxis sz{n_size, sizes};
+    int64_t chunk = 0;
+    int rc = window_sweep_prepare(b, ws, name, false, n_len, N, rows, delta, n_prior, n0, w0, &chunk, &sz);
+    if (rc != TP_OK) return rc;
+    if (chunk == 0) { ws.S = S; return TP_OK; }            // W = 0: nothing to launch, the shape is set
+    ws.S = 0;
+    rc = ensure(h, ws.sizes, sizeof(int32_t) * (size_t)S, "tp_batch_grid_sweep: sizes");
+    if (rc != TP_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(ws.sizes.p, sizes, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    tp_window_gram_kargs_t ga;
+    tp_window_delta_kargs_t da;
+    window_gram_delta_kargs(b, ws, L, &ga, &da);
+    tp_grid_sweep_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.C = conj ? (const double*)ws.C.p : nullptr;
+    sa.T = (const double*)ws.T.p; sa.t = (const double*)ws.t.p;
+    sa.dv = delta ? (const double*)ws.dv.p : nullptr; sa.ds = delta ? (const double*)ws.ds.p : nullptr;
+    sa.n0 = conj ? (const double*)ws.n0.p : nullptr; sa.w0 = conj ? (const double*)ws.w0.p : nullptr;
+    sa.hf_count = (const int*)b->hf_count.p;
+    sa.rows = ga.rows; sa.N = (const int*)ws.N.p; sa.sizes = (const int*)ws.sizes.p;
+    sa.weights = (double*)ws.weights.p; sa.status = (int*)ws.status.p; sa.aux = (double*)ws.aux.p;
+    sa.k = k; sa.P = P; sa.L = L; sa.S = S; sa.m = b->p.m; sa.center_rows = ga.in.center_rows;
+    sa.gamma = b->p.gamma;
+    return run_sweep(b, chunk, [&](int64_t wf, int64_t n) {
+        ga.in.w_first = wf; ga.in.w_count = n;
+        const hipError_t e = tp_window_gram_launch(ga, h->stream);
+        if (e == hipErrorNotSupported)
+            return fail(h, TP_ERR_UNSUPPORTED, "%s: windows of %d daily / %d intraday rows in the index layout are too long "
+                                               "for the Gram pass", name, n_r, b->p.m);
+        int rcl = launched(h, e, "grid sweep Gram");
+        if (rcl == TP_OK && delta) {
+            da.in.w_first = wf; da.in.w_count = n;
+            rcl = launched(h, tp_window_delta_launch(da, h->stream), "grid sweep delta kernel");
+        }
+        if (rcl != TP_OK) return rcl;
+        sa.w_first = wf; sa.w_count = n;
+        return launched(h, tp_grid_sweep_launch(sa, h->stream), "grid sweep kernel");
+    }, [&] { ws.P = P; ws.L = L; ws.S = S; });
+}
+
+int tp_batch_download_grid_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    const GridSweepWs& ws = b->gr;
+    if (ws.P < 1 || ws.L < 1 || ws.S < 1) return fail(h, TP_ERR_INVALID, "tp_batch_download_grid_sweep: no tp_batch_grid_sweep before it");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)b->W * ws.P * ws.L * ws.S;
     return download(h, {{weights, ws.weights.p, sizeof(double) * n * b->p.k}, {status, ws.status.p, sizeof(int32_t) * n},
                         {aux, ws.aux.p, sizeof(double) * n * TP_AUX_STRIDE}});
 }

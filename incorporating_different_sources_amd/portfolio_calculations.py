@@ -1188,6 +1188,101 @@ def calculate_weights_for_windows(trading_dates, portfolio_specs_list, market_da
     return out
 
 
+def _grid_family(portfolio_spec):
+    """Specs with equal (rebalancing frequency, window frequency): `size` picks a prefix of the cap-ordered universe and
+    `rolling_window` a tail of the longest window's rows."""
+    return tuple(portfolio_spec.get(name) for name in ("rebalancing_frequency", "rolling_window_frequency"))
+
+
+def calculate_weights_for_grid(trading_dates, portfolio_specs_list, market_data):
+    """Weights of specs that differ in `size` AND in `rolling_window` (conjugate specs: also in the prior - vw / ew, VIX / EPU,
+    mcm_scaling) for the same dates with ONE host pack at (largest size, longest window) (`batch.pack_windows_grid`), ONE upload
+    and ONE grid sweep (`Batch.grid_sweep`): every daily row passes the device once, every (date, prior, length) is factorised
+    once at the largest size and each size solved over its prefix.  Conjugate specs only, or Jeffreys specs only, of one
+    (rebalancing frequency, window frequency) family.  (date, size, length) triples the pack cannot serve (its mask), sizes
+    above `_native.sweep_max_assets()`, more than `_native.SWEEP_MAX_RHS` sizes or lengths and a pack that raises go through
+    `_weights_for_dates` spec by spec, so the reference's exceptions surface where the reference raises them.
+    Returns one (weights, labels, cols, caps) per spec, each at its own size - equal to `_weights_for_dates` spec by spec
+    within the solve's rounding - and remembers the conjugate ones in the cache slots `calculate_weights_for_specs` fills.
+    Opt-in: nothing calls it by default."""
+    specs = list(portfolio_specs_list)
+    if not specs:
+        return []
+    conj = specs[0]["weighting_strategy"] in _CONJUGATE
+    if (any((sp["weighting_strategy"] in _CONJUGATE) != conj or (not conj and sp["weighting_strategy"] != "jeffreys") for sp in specs)
+            or len({_grid_family(sp) for sp in specs}) != 1):
+        raise ValueError("calculate_weights_for_grid: conjugate specs, or Jeffreys specs, of equal frequencies expected")
+    trading_dates = list(trading_dates)
+    n_dates = len(trading_dates)
+    members_of = _members_provider(market_data)
+    gammas = [sp["risk_aversion"] for sp in specs]
+    same_gamma = all(g == gammas[0] for g in gammas)
+    windows = sorted({int(sp["rolling_window"]) for sp in specs})
+    sizes = sorted({int(sp["size"]) for sp in specs if int(sp["size"]) <= _native.sweep_max_assets()})
+    packed = None
+    if sizes and len(sizes) <= _native.SWEEP_MAX_RHS and len(windows) <= _native.SWEEP_MAX_RHS:
+        try:
+            packed = batch.pack_windows_grid(trading_dates, specs[0], sizes, windows, market_data, members_of=members_of)
+        except (ValueError, AssertionError) as exc:      # the specs decide one by one what the caller sees
+            logger.warning(f"grid sweep dropped ({exc}); solving the {len(specs)} specs one by one")
+    swept = None
+    if packed is not None:
+        k = sizes[-1]
+        kw, labels, caps, rows, delta, mask = packed
+        n0 = w0 = None
+        prior_keys = []
+        if conj:
+            prior_of = lambda sp: (sp["weighting_strategy"], sp["mcm_scaling"])
+            prior_keys = list(dict.fromkeys(prior_of(sp) for sp in specs if sp["size"] <= k))
+            n0 = np.empty((n_dates, len(prior_keys), len(windows)))
+            w0 = np.zeros((n_dates, len(prior_keys), len(sizes), k))
+            for p, key in enumerate(prior_keys):
+                sp = next(sp for sp in specs if prior_of(sp) == key)
+                wanted = {int(x["size"]) for x in specs if prior_of(x) == key}
+                for l, N in enumerate(windows):          # n0 reads the length (ref:112, 265), not the size
+                    n0[:, p, l] = batch.prior_inputs(trading_dates, dict(sp, size=k, rolling_window=N), market_data, caps)[1]
+                # w0 over the prefix (ref:692-695 / 670-672) reads the caps alone - neither the length nor the dates: one date is
+                # passed so that the n0 it returns next to it is not computed W times per size
+                for s, ks in enumerate(sizes):
+                    if ks in wanted:
+                        w0[:, p, s, :ks] = batch.prior_inputs(trading_dates[:1], dict(sp, size=ks), market_data, caps[:, :ks])[0]
+                    else:                                # no spec asks for this pair: any finite prior does, its result is not read
+                        w0[:, p, s, :ks] = 1.0 / ks
+        b = _native.Batch(_native.default_device(), "conjugate" if conj else "jeffreys", k, windows[-1], kw["n_r"],
+                          gammas[0] if same_gamma else 1.0, n_dates, kw.get("m") or 0)
+        try:
+            b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m")})
+            weights, status, _ = b.grid_sweep(sizes, windows, rows, n0, w0, delta=delta if delta.any() else None, want_aux=False)
+        finally:
+            b.close()
+        swept = (weights, status, labels, kw["col_idx"], caps, mask, prior_keys)
+    out = []
+    for sp in specs:
+        ks = int(sp["size"])
+        if swept is None or ks not in sizes:
+            res = _weights_for_dates(trading_dates, sp, market_data)
+        else:
+            weights, status, labels, cols, caps, mask, prior_keys = swept
+            s, l = sizes.index(ks), windows.index(int(sp["rolling_window"]))
+            p = prior_keys.index((sp["weighting_strategy"], sp["mcm_scaling"])) if conj else 0
+            ok = mask[:, s, l]
+            _raise_on_status(status[ok, p, l, s])
+            w = np.ascontiguousarray(weights[:, p, l, s, :ks])
+            if not same_gamma:
+                w = 1.0 / sp["risk_aversion"] * w
+            lab = [row[:ks] for row in labels]
+            res = (w, lab, cols[:, :ks].copy(), caps[:, :ks].copy())      # (copies: several specs share a size, a fallback writes)
+            if not ok.all():                             # these dates' spec is not the pack's prefix and suffix, or trips a check
+                miss = np.flatnonzero(~ok)
+                alone = _weights_for_dates([trading_dates[i] for i in miss], sp, market_data)
+                for j, i in enumerate(miss):
+                    res[0][i], res[1][i], res[2][i], res[3][i] = alone[0][j], alone[1][j], alone[2][j], alone[3][j]
+        if conj:
+            res = _fill_spec_cache([sp], trading_dates, market_data, res[0], n_dates, True, res[1], res[2], res[3])[0]
+        out.append(res)
+    return out
+
+
 def _replicated_weights(kw, priors, n_specs, k, N, gamma):
     """Every window once per spec in ONE device batch of n_specs x n_dates windows."""
     per_window = ("row_idx", "n_rows", "col_idx", "rf_adj", "hf_row_idx", "hf_count")
