@@ -526,12 +526,53 @@ int tp_batch_grid_sweep(tp_batch_t b, int32_t n_size, const int32_t* sizes /* [n
                         const double* delta /* [W x n_len x n_r] or NULL */,
                         int32_t n_prior, const double* n0 /* [W x n_prior x n_len] */,
                         const double* w0 /* [W x n_prior x n_size x k] */);
+/* tp_batch_grid_sweep above tp_sweep_max_assets(), on the large-k tiled pipeline: the same definition of entry (w, p, l, s),
+ * arguments, validation and result buffers (tp_batch_download_grid_sweep serves both calls; a call refused with TP_ERR_INVALID
+ * leaves the results of the last grid sweep of either kind in place).  Single sizes may be anything in [1, k], sizes
+ * <= tp_sweep_max_assets() included: they ride along as prefixes of the same entries.
+ * TP_ERR_UNSUPPORTED: k <= tp_sweep_max_assets() (tp_batch_grid_sweep serves those); k + n_size > tp_max_assets() + 1 (the
+ * right-hand sides of the sizes travel in columns k .. k + n_size - 1 of an arena of side 64 ceil((k + n_size)/64) <= 2048).  No
+ * limit on the rows of an index-layout window: the rows are not staged.
+ * How it runs: sub-ranges of windows under the rule and the 4 GiB budget of tp_batch_window_sweep_tiled ("sweep_chunk_windows",
+ * n_len (conjugate: + 1) k x k matrices per window, at least one window).  Per sub-range, conjugate: the batch's own tiled Gram
+ * stage runs ONCE per window over the intraday rows, steered by its arguments as in tp_batch_prior_sweep_tiled, so C is
+ * RAW-MOMENT centred (exact to rounding for returns, it loses digits under a large common offset of the intraday panel) and
+ * never comes from the shared intraday sums; it goes through the batch's run workspace, which is not grown.  The segmented Gram
+ * of tp_batch_window_sweep_tiled stores (T_l, t_l) per length at the batch's k from ONE pass over the daily rows, and with a
+ * delta the delta kernel forms v, s1 and s2.  One kernel per (window, prior) forms the n_size truncated products
+ * v_s = C[:k_s,:k_s] w0_wps[:k_s] and w0_wps'v_s in one pass over the rows of C - terms at or beyond k_s selected out, never
+ * multiplied by zero; they depend on neither the length nor n0.  An ENTRY is a (window, prior, length); the entries of a sub-range
+ * go through the tiled solve sweep's workspace at R = n_size (shared with tp_batch_solve_sweep_tiled and
+ * tp_batch_size_sweep_tiled, whose downloads are left alone) in groups of its capacity, ALL lengths together: a fill kernel writes
+ * a C + (G_l - v 1' - 1 v' + s2 1 1') - the correction from left to right - or the Jeffreys matrix inside k x k and the
+ * right-hand side of size s into rows < k_s of column k + s, exact zeros elsewhere; the block steps of the tiled factorisation
+ * factorise ONCE at k and forward-substitute the columns; the solve kernel reads N_l and n0_wpl per entry, back-substitutes every
+ * size over its own prefix and writes weights, statuses and aux rows straight to their slots.
+ * Statuses per size are those of tp_batch_download_grid_sweep (the relative pivot floor over the prefix, from the diagonal the
+ * fill stored); the entry's own not-positive-definite flag decides no size.
+ * Promises.  Bit for bit: an entry does not depend on W, n_prior, the window's or the prior's slot, the sub-ranges or the arena's
+ * size ("tiled_arena_mib"); an all-zero delta gives the bits of delta == NULL.  To rounding only: an entry depends on the OTHER
+ * lengths of the list (the list sets where the partial sums of the Gram are cut) and on the other SIZES (n_size sets the arena's
+ * side, as in tp_batch_size_sweep_tiled).  A row older than a length's suffix never reaches that length.  Columns at or beyond a
+ * prefix: a finite degenerate column j (a duplicate, a zero column) leaves every k_s <= j intact and flags the sizes > j; a
+ * NON-FINITE column j leaves k_s <= 64 floor(j/64) intact, the sizes in (64 floor(j/64), j] may come back flagged - the block
+ * steps multiply whole 64-row blocks with MFMAs, where a structural zero times a NaN is a NaN - and the sizes > j are flagged.
+ * No size is TP_STATUS_OK with numbers that are not its own.
+ * Device memory: that of tp_batch_grid_sweep plus, conjugate, n_size (k + 1) doubles per (window, prior) of a sub-range and, per
+ * entry of the sweep's workspace, KP^2 + 4096 ceil(k/64) + k doubles - as many entries as the arena budget allows
+ * ("tiled_arena_gib" / "tiled_arena_mib"); kept until tp_batch_destroy.  Streams, the entry drain, timing (kernel_ms covers every
+ * launch; one step of tp_region_steps), the gather hand-over and what the call leaves alone are as for tp_batch_grid_sweep. */
+int tp_batch_grid_sweep_tiled(tp_batch_t b, int32_t n_size, const int32_t* sizes /* [n_size] */,
+                              int32_t n_len, const int32_t* N /* [n_len] */, const int32_t* rows /* [W x n_len] */,
+                              const double* delta /* [W x n_len x n_r] or NULL */,
+                              int32_t n_prior, const double* n0 /* [W x n_prior x n_len] */,
+                              const double* w0 /* [W x n_prior x n_size x k] */);
 /* Waits for the grid sweep and copies out weights [W x P x n_len x n_size x k] (P = n_prior, 1 for a Jeffreys batch), status
  * [W x P x n_len x n_size] - per entry: TP_STATUS_NOT_PD when a pivot j < k_s is <= 0 or no larger than k_s 2^-52 times its
  * diagonal element of S1 (of M), e.g. a Jeffreys length of fewer rows than k_s; TP_STATUS_NONFINITE; TP_STATUS_BAD_DENOM
  * (conjugate): n1 - w1'S1 w1 <= 0 - and aux [W x P x n_len x n_size x TP_AUX_STRIDE] (the slots of tp_batch_download's aux: for
- * a Jeffreys batch 0 except slot 4, t_l'M^-1 t_l over the prefix); each may be NULL.  Without a grid sweep before it:
- * TP_ERR_INVALID. */
+ * a Jeffreys batch 0 except slot 4, t_l'M^-1 t_l over the prefix); each may be NULL.  Without a grid sweep (of either kind)
+ * before it: TP_ERR_INVALID. */
 int tp_batch_download_grid_sweep(tp_batch_t b, double* weights /* [W x P x n_len x n_size x k] */,
                                  int32_t* status /* [W x P x n_len x n_size] */,
                                  double* aux /* [W x P x n_len x n_size x TP_AUX_STRIDE] */);

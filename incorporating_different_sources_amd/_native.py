@@ -48,7 +48,7 @@ EXPORTS = [
     "tp_batch_prior_sweep", "tp_batch_prior_sweep_tiled", "tp_batch_download_prior_sweep",
     "tp_batch_size_sweep", "tp_batch_size_sweep_tiled", "tp_batch_download_size_sweep",
     "tp_batch_window_sweep", "tp_batch_window_sweep_tiled", "tp_batch_download_window_sweep",
-    "tp_batch_grid_sweep", "tp_batch_download_grid_sweep",
+    "tp_batch_grid_sweep", "tp_batch_grid_sweep_tiled", "tp_batch_download_grid_sweep",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
     "tp_comm_count", "tp_comm_init_all", "tp_group_gather",
@@ -129,6 +129,7 @@ def _load():
     lib.tp_batch_download_window_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_grid_sweep.argtypes = [c_void_p, c_int32, POINTER(c_int32), c_int32, POINTER(c_int32), POINTER(c_int32),
                                         POINTER(c_double), c_int32, POINTER(c_double), POINTER(c_double)]
+    lib.tp_batch_grid_sweep_tiled.argtypes = lib.tp_batch_grid_sweep.argtypes
     lib.tp_batch_download_grid_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_download_S1.argtypes = [c_void_p, c_int64, POINTER(c_double)]
@@ -785,6 +786,15 @@ class Batch:
         return weights, status, aux
 
     def grid_sweep(self, sizes, N, rows, n0=None, w0=None, delta=None, want_aux=True):
+        return self._grid_sweep(lib.tp_batch_grid_sweep, sizes, N, rows, n0, w0, delta, want_aux)
+
+    def grid_sweep_tiled(self, sizes, N, rows, n0=None, w0=None, delta=None, want_aux=True):
+        """`tp_batch_grid_sweep_tiled` + `tp_batch_download_grid_sweep`: `grid_sweep` for k > `sweep_max_assets()`, on the
+        large-k tiled pipeline - the same arguments, checks (before any device call) and results; single sizes may lie below
+        that bound.  k + len(sizes) <= `max_assets()` + 1."""
+        return self._grid_sweep(lib.tp_batch_grid_sweep_tiled, sizes, N, rows, n0, w0, delta, want_aux)
+
+    def _grid_sweep(self, call, sizes, N, rows, n0, w0, delta, want_aux):
         """`tp_batch_grid_sweep` + `tp_batch_download_grid_sweep`: S nested universes x L nested window lengths per window -
         entry (l, s) uses the first `sizes[s]` columns and the last `rows[w, l]` daily rows of the window as uploaded - from ONE
         pass over the rows and ONE factorisation per (window, prior, length).  `sizes` as in `size_sweep`; `N`, `rows` and
@@ -839,13 +849,13 @@ class Batch:
         rwp = rw if rw.size else np.ones(1, dtype=np.int32)
         dp = None if delta is None or not delta.size else delta
         if n0 is None:
-            self.dev._check(lib.tp_batch_grid_sweep(self._b, S, _ptr(sz, c_int32), L, _ptr(Nl, c_int32), _ptr(rwp, c_int32),
-                                                    _ptr(dp, c_double), 0, None, None))
+            self.dev._check(call(self._b, S, _ptr(sz, c_int32), L, _ptr(Nl, c_int32), _ptr(rwp, c_int32), _ptr(dp, c_double), 0,
+                                 None, None))
         else:
             n0p = n0 if n0.size else np.ones(1)
             w0p = w0 if w0.size else np.zeros(1)
-            self.dev._check(lib.tp_batch_grid_sweep(self._b, S, _ptr(sz, c_int32), L, _ptr(Nl, c_int32), _ptr(rwp, c_int32),
-                                                    _ptr(dp, c_double), P, _ptr(n0p, c_double), _ptr(w0p, c_double)))
+            self.dev._check(call(self._b, S, _ptr(sz, c_int32), L, _ptr(Nl, c_int32), _ptr(rwp, c_int32), _ptr(dp, c_double), P,
+                                 _ptr(n0p, c_double), _ptr(w0p, c_double)))
         self.dev._check(lib.tp_batch_download_grid_sweep(self._b, _ptr(weights if weights.size else None, c_double),
                                                          _ptr(status if status.size else None, c_int32),
                                                          _ptr(aux if aux is not None and aux.size else None, c_double)))

@@ -13,6 +13,7 @@
 #include "host_resources.h"
 #include "posterior_kernels.h"
 #include "posterior_grid_sweep.h"
+#include "posterior_grid_sweep_tiled.h"
 #include "posterior_prior_sweep.h"
 #include "posterior_size_sweep.h"
 #include "posterior_size_sweep_tiled.h"
@@ -107,6 +108,8 @@ struct WindowSweepWs {
 // own, so that tp_batch_download_window_sweep returns what it returned before, and the universes' sizes.
 struct GridSweepWs : WindowSweepWs {
     DevBuf sizes;                   // [S]
+    DevBuf mdiag;                   // tp_batch_grid_sweep_tiled: the diagonals [entries of one group x k] its fill keeps for the statuses
+                                    // (its prior products of one sub-range lie in cw [chunk x P x S x k] and cq [chunk x P x S])
     int S = 0;                      // sizes of the last sweep (0: none yet)
 };
 
@@ -122,7 +125,7 @@ struct tp_batch_s {
     SolveSweepWs sw;                                          // tp_batch_solve_sweep / _solve_sweep_tiled
     PriorSweepWs ps, zs;                                      // tp_batch_prior_sweep / _prior_sweep_tiled; tp_batch_size_sweep / _size_sweep_tiled
     WindowSweepWs wn;                                         // tp_batch_window_sweep / _window_sweep_tiled
-    GridSweepWs gr;                                           // tp_batch_grid_sweep
+    GridSweepWs gr;                                           // tp_batch_grid_sweep / _grid_sweep_tiled
     PriceStaging fe, fe_hf;                                   // daily and intraday (freed after a synchronous upload)
     DevBuf prefix;                                            // shared Gram prefixes of the daily panel (register-tile path)
     int prefix_nblk = 0;                                      // > 0: the layout qualifies (decided at upload)

@@ -1,5 +1,5 @@
 // tangency_sweep.cpp - the sweeps of the C-ABI of libtangency.so (include/tangency_posterior.h): many solves per window
-// from one Gram pass - tp_batch_solve_sweep, _prior_sweep, _size_sweep, _window_sweep, _grid_sweep, the four tiled forms above
+// from one Gram pass - tp_batch_solve_sweep, _prior_sweep, _size_sweep, _window_sweep, _grid_sweep, the five tiled forms above
 // tp_sweep_max_assets(), and their downloads.  Every sweep is: checks, a drain of the handle's stream, its workspace (SolveSweepWs / PriorSweepWs,
 // tangency_host.h), then per sub-range of windows a Gram stage and a solve stage inside one timed span.
 #include <cmath>
@@ -15,7 +15,7 @@ using namespace tp_host;
 // Bound of the matrices one sub-range of windows keeps: 256 MiB, the size of the Infinity Cache (the solve kernel reads what
 // the Gram pass has just written).
 #define TP_SWEEP_WORKSPACE_BYTES (256ull << 20)
-// tp_batch_window_sweep_tiled alone: 4 GiB.  Its entries are factorised in groups of ONE length, each a chain of some 3 NS small
+// tp_batch_window_sweep_tiled (and tp_batch_grid_sweep_tiled, which keeps its rule): 4 GiB.  Its entries are factorised in groups of ONE length, each a chain of some 3 NS small
 // launches over the sub-range's windows x priors, so the sub-range - not the cache - decides how full the chip runs: at 256 MiB
 // (25 windows at k = 500, L = 4) the sweep took 1.6 - 3.6x the device time of one batch per length, at 4 GiB 1.3 - 2.5x less
 // (DESIGN.md section 4m).
@@ -360,7 +360,7 @@ int download_prior_ws(tp_batch_t b, const PriorSweepWs& ws, double* weights, int
 // ---- window sweeps ---------------------------------------------------------------------------------------------------
 
 // What the two window sweeps share - tp_batch_window_sweep (`tiled` = false, k <= tp_sweep_max_assets()) and
-// tp_batch_window_sweep_tiled (above it): the argument checks, the k range, the drain, the checks against the windows' own row
+// tp_batch_window_sweep_tiled (above it; `partner`: the sweep below a tiled one, named when k is too small) -: the argument checks, the k range, the drain, the checks against the windows' own row
 // counts, the windows per sub-range (L snapshots - conjugate: and C - per window), the sweep's buffers and the copies of the
 // caller's arrays - into `ws`, the window sweeps' or the grid sweep's (`sz` given: n_size universes per (window, prior, length),
 // w0 per (window, prior, size) and read inside its prefix only, results per (window, prior, length, size); the sizes themselves
@@ -368,7 +368,7 @@ int download_prior_ws(tp_batch_t b, const PriorSweepWs& ws, double* weights, int
 // *chunk_out = 0: W = 0, nothing to launch (the sweep's shape is set).
 int window_sweep_prepare(tp_batch_t b, WindowSweepWs& ws, const char* name, bool tiled, int32_t n_len, const int32_t* N,
                          const int32_t* rows, const double* delta, int32_t n_prior, const double* n0, const double* w0,
-                         int64_t* chunk_out, const SizeAxis* sz = nullptr) {
+                         int64_t* chunk_out, const SizeAxis* sz = nullptr, const char* partner = "tp_batch_window_sweep") {
     tp_handle_t h = b->h;
     const int k = b->p.k, n_r = b->p.n_r;
     const int64_t W = b->W;
@@ -397,8 +397,10 @@ int window_sweep_prepare(tp_batch_t b, WindowSweepWs& ws, const char* name, bool
     } else if (n_prior != 0 || n0 || w0) {
         return fail(h, TP_ERR_INVALID, "%s: a Jeffreys batch takes no priors (n_prior = 0, n0 = w0 = NULL)", name);
     }
-    rc = check_sweep_k(h, tiled, name, "tp_batch_window_sweep", k);
+    rc = check_sweep_k(h, tiled, name, partner, k);
     if (rc != TP_OK) return rc;
+    if (tiled && sz && k + S > tp_max_assets() + 1)
+        return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d with %d sizes exceeds the arena side %d", name, k, S, tp_max_assets() + 1);
     rc = drain_for_sweep(b);
     if (rc != TP_OK) return rc;
     if (W == 0) { ws.P = P; ws.L = L; return TP_OK; }      // (*chunk_out = 0: nothing to launch, the shape is set)
@@ -981,6 +983,104 @@ int tp_batch_grid_sweep(tp_batch_t b, int32_t n_size, const int32_t* sizes, int3
         sa.w_first = wf; sa.w_count = n;
         return launched(h, tp_grid_sweep_launch(sa, h->stream), "grid sweep kernel");
     }, [&] { ws.P = P; ws.L = L; ws.S = S; });
+}
+
+// Grid sweep above tp_sweep_max_assets(), on the large-k tiled pipeline: the tiled window sweep's Gram stages into the grid
+// sweep's workspace, the tiled size sweep's entries.  Per sub-range (the tiled window sweep's rule and budget): conjugate, the
+// batch's own tiled Gram stage over the INTRADAY rows leaves the raw-moment-centred C in gr.C through the batch's run workspace,
+// neither grown nor re-shaped; the segmented one-wave Gram stores the snapshots T_l, t_l at the batch's k; the delta kernel - with
+// a delta only - forms the sums of the rank-two correction; one kernel forms the S truncated prior products per (window, prior).
+// Then the sub-range's (window, prior, length) entries go through the SWEEP's workspace (the tiled solve sweep's, at R = n_size)
+// in groups of its capacity, ALL lengths together: posterior_grid_sweep_tiled.hip fills them, the block steps factorise them ONCE
+// at k and forward-substitute the n_size columns, and the sweep's own kernel - which reads N and n0 per entry - back-substitutes
+// every size over its prefix and writes the results to their slots.
+int tp_batch_grid_sweep_tiled(tp_batch_t b, int32_t n_size, const int32_t* sizes, int32_t n_len, const int32_t* N, const int32_t* rows,
+                              const double* delta, int32_t n_prior, const double* n0, const double* w0) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    GridSweepWs& gr = b->gr;
+    const char* name = "tp_batch_grid_sweep_tiled";
+    const int k = b->p.k;
+    const bool conj = b->p.strategy == TP_STRATEGY_CONJUGATE;
+    const int L = n_len, S = n_size;
+    const int P = conj ? n_prior : 1;
+    const SizeAxis sz{n_size, sizes};
+    int64_t chunk = 0;
+    int rc = window_sweep_prepare(b, gr, name, true, n_len, N, rows, delta, n_prior, n0, w0, &chunk, &sz, "tp_batch_grid_sweep");
+    if (rc != TP_OK) return rc;
+    if (chunk == 0) { gr.S = S; return TP_OK; }            // W = 0: nothing to launch, the shape is set
+    gr.S = 0;
+    // the batch's run workspace as a run would size it, for the pass over the intraday rows; the sweep's own for the entries
+    tp_tiled_ws_t gws;
+    memset(&gws, 0, sizeof gws);
+    int64_t gcap = 0;
+    if (conj) {
+        rc = ensure_tiled_ws(b, &gws);
+        if (rc != TP_OK) return rc;
+        gcap = b->tiled_capacity;
+    }
+    tp_tiled_ws_t ws;
+    int64_t cap = 0;
+    rc = ensure_sweep_tiled_ws(b, S, chunk * P * L, &ws, &cap);
+    if (rc != TP_OK) return rc;
+    const std::string what = std::string(name) + ": ";
+    rc = ensure(h, gr.sizes, sizeof(int32_t) * (size_t)S, (what + "sizes").c_str());
+    if (rc == TP_OK) rc = ensure(h, gr.mdiag, sizeof(double) * (size_t)cap * k, (what + "diagonals of one group of entries").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, gr.cw, sizeof(double) * (size_t)chunk * P * S * k, (what + "prior products of one sub-range").c_str());
+    if (rc == TP_OK && conj) rc = ensure(h, gr.cq, sizeof(double) * (size_t)chunk * P * S, (what + "prior quadratic forms of one sub-range").c_str());
+    if (rc != TP_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(gr.sizes.p, sizes, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+
+    tp_kargs_t ta, ca;                                 // conjugate: `ca`, the pass over the intraday rows, alone (T_l, t_l: the segmented Gram)
+    tiled_conjugate_gram_kargs(b, gr.T, gr.t, gr.C, &ta, &ca);
+    (void)ta;
+    tp_window_gram_kargs_t ga;
+    tp_window_delta_kargs_t da;
+    window_gram_delta_kargs(b, gr, L, &ga, &da);
+    tp_grid_sweep_tiled_kargs_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.C = conj ? (const double*)gr.C.p : nullptr;
+    sa.T = (const double*)gr.T.p; sa.t = (const double*)gr.t.p;
+    sa.dv = delta ? (const double*)gr.dv.p : nullptr; sa.ds = delta ? (const double*)gr.ds.p : nullptr;
+    sa.n0 = conj ? (const double*)gr.n0.p : nullptr; sa.w0 = conj ? (const double*)gr.w0.p : nullptr;
+    sa.hf_count = (const int*)b->hf_count.p;
+    sa.rows = ga.rows; sa.N = (const int*)gr.N.p; sa.sizes = (const int*)gr.sizes.p;
+    sa.cv = conj ? (double*)gr.cw.p : nullptr; sa.cq = conj ? (double*)gr.cq.p : nullptr;
+    sa.mdiag = (double*)gr.mdiag.p;
+    sa.weights = (double*)gr.weights.p; sa.status = (int*)gr.status.p; sa.aux = (double*)gr.aux.p;
+    sa.k = k; sa.P = P; sa.L = L; sa.S = S; sa.m = b->p.m; sa.center_rows = ga.in.center_rows;
+    sa.gamma = b->p.gamma;
+    // the block steps read k, w_count (set per group below) and the kernel choices; everything else stays zero
+    tp_kargs_t fa;
+    memset(&fa, 0, sizeof fa);
+    fa.k = k;
+    fa.opts = h->opts;
+    return run_sweep(b, chunk, [&](int64_t wf, int64_t n) {
+        int rcg = conj ? tiled_gram_stage(b, "tiled grid sweep Gram", {&ca}, gws, gcap, wf, n) : TP_OK;
+        if (rcg != TP_OK) return rcg;
+        ga.in.w_first = wf; ga.in.w_count = n;
+        rcg = launched(h, tp_tiled_window_gram_launch(ga, h->stream), "tiled grid sweep segmented Gram");
+        if (rcg == TP_OK && delta) {
+            da.in.w_first = wf; da.in.w_count = n;
+            rcg = launched(h, tp_window_delta_launch(da, h->stream), "grid sweep delta kernel");
+        }
+        if (rcg != TP_OK) return rcg;
+        sa.wc_first = wf;
+        if (conj) {
+            sa.wp_first = wf * P; sa.wp_count = n * P;
+            rcg = launched(h, tp_grid_sweep_tiled_cw_launch(sa, h->stream), "tiled grid sweep prior products");
+            if (rcg != TP_OK) return rcg;
+        }
+        return in_groups(n * P * L, cap, [&](int64_t e0, int64_t ne) {
+            sa.e_first = wf * P * L + e0; sa.e_count = ne;
+            int rce = launched(h, tp_grid_sweep_tiled_fill_launch(sa, ws, h->stream), "tiled grid sweep fill");
+            fa.w_count = ne;
+            if (rce == TP_OK) rce = launched(h, tp_tiled_block_steps_launch(fa, ws, h->stream), "tiled grid sweep factor");
+            if (rce == TP_OK) rce = launched(h, tp_grid_sweep_tiled_solve_launch(sa, ws, h->stream), "tiled grid sweep solve");
+            return rce;
+        });
+    }, [&] { gr.P = P; gr.L = L; gr.S = S; });
 }
 
 int tp_batch_download_grid_sweep(tp_batch_t b, double* weights, int32_t* status, double* aux) {

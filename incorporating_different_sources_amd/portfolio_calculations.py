@@ -1188,6 +1188,13 @@ def calculate_weights_for_windows(trading_dates, portfolio_specs_list, market_da
     return out
 
 
+# `calculate_weights_for_grid` with a largest size above `_native.sweep_max_assets()`: True packs every requested size once at
+# the largest (and the longest window) and takes one tiled grid sweep (`Batch.grid_sweep_tiled`) - the sizes below that bound
+# are then prefixes of the same sweep - instead of one `_weights_for_dates` per spec above it.  Off: DESIGN.md section 4o holds
+# the timings a later change decides the default from.
+GRID_SWEEP_TILED = False
+
+
 def _grid_family(portfolio_spec):
     """Specs with equal (rebalancing frequency, window frequency): `size` picks a prefix of the cap-ordered universe and
     `rolling_window` a tail of the longest window's rows."""
@@ -1201,7 +1208,9 @@ def calculate_weights_for_grid(trading_dates, portfolio_specs_list, market_data)
     once at the largest size and each size solved over its prefix.  Conjugate specs only, or Jeffreys specs only, of one
     (rebalancing frequency, window frequency) family.  (date, size, length) triples the pack cannot serve (its mask), sizes
     above `_native.sweep_max_assets()`, more than `_native.SWEEP_MAX_RHS` sizes or lengths and a pack that raises go through
-    `_weights_for_dates` spec by spec, so the reference's exceptions surface where the reference raises them.
+    `_weights_for_dates` spec by spec, so the reference's exceptions surface where the reference raises them - unless
+    GRID_SWEEP_TILED is set: then, when the largest size exceeds that bound (and the sizes and lengths fit one tiled sweep), ALL
+    sizes are packed once at the largest and swept with `Batch.grid_sweep_tiled`.
     Returns one (weights, labels, cols, caps) per spec, each at its own size - equal to `_weights_for_dates` spec by spec
     within the solve's rounding - and remembers the conjugate ones in the cache slots `calculate_weights_for_specs` fills.
     Opt-in: nothing calls it by default."""
@@ -1218,7 +1227,11 @@ def calculate_weights_for_grid(trading_dates, portfolio_specs_list, market_data)
     gammas = [sp["risk_aversion"] for sp in specs]
     same_gamma = all(g == gammas[0] for g in gammas)
     windows = sorted({int(sp["rolling_window"]) for sp in specs})
-    sizes = sorted({int(sp["size"]) for sp in specs if int(sp["size"]) <= _native.sweep_max_assets()})
+    sizes = sorted({int(sp["size"]) for sp in specs})
+    tiled = bool(GRID_SWEEP_TILED and sizes[-1] > _native.sweep_max_assets() and len(sizes) <= _native.SWEEP_MAX_RHS
+                 and len(windows) <= _native.SWEEP_MAX_RHS and sizes[-1] + len(sizes) <= _native.max_assets() + 1)
+    if not tiled:
+        sizes = [ks for ks in sizes if ks <= _native.sweep_max_assets()]
     packed = None
     if sizes and len(sizes) <= _native.SWEEP_MAX_RHS and len(windows) <= _native.SWEEP_MAX_RHS:
         try:
@@ -1252,7 +1265,8 @@ def calculate_weights_for_grid(trading_dates, portfolio_specs_list, market_data)
                           gammas[0] if same_gamma else 1.0, n_dates, kw.get("m") or 0)
         try:
             b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m")})
-            weights, status, _ = b.grid_sweep(sizes, windows, rows, n0, w0, delta=delta if delta.any() else None, want_aux=False)
+            weights, status, _ = (b.grid_sweep_tiled if tiled else b.grid_sweep)(
+                sizes, windows, rows, n0, w0, delta=delta if delta.any() else None, want_aux=False)
         finally:
             b.close()
         swept = (weights, status, labels, kw["col_idx"], caps, mask, prior_keys)
