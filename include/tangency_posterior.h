@@ -182,6 +182,15 @@ int tp_batch_shared_gram_blocks(tp_batch_t b);
 /* After an upload, large-k path, conjugate: whole stride-long blocks of intraday rows per window whose Grams the windows
  * of a sub-batch share (0: every intraday row of every window goes through the MFMAs). */
 int tp_batch_shared_intraday_blocks(tp_batch_t b);
+/* How the Gram kernels form their load addresses for a panel of `panel_bytes` bytes with leading dimension `ld` (doubles)
+ * whose windows have `rows_per_window` rows (n_r for the daily panel, m for the intraday one).  Needs no device.
+ * Bit 0: windows with explicit rows use one 32-bit byte offset per row from the panel base (the panel is below 2^32
+ * bytes and has fewer than 2^24 rows).  Bit 1: contiguous windows use 32-bit offsets from the window's first row
+ * ((rows_per_window + 64) * ld * 8 < 2^32 and rows_per_window < 2^24).  Both clear when ld < 1 or 8 ld >= 2^24.  A clear bit: 64-bit addresses. */
+int tp_addressing_flags(int64_t panel_bytes, int32_t ld, int32_t rows_per_window);
+/* After an upload: the flag words above as the next launch of this batch will see them, for the daily panel and the
+ * intraday panel (0 when the batch has none).  Either pointer may be NULL. */
+int tp_batch_addressing(tp_batch_t b, int* panel_flags, int* hf_flags);
 /* Page-locked host memory for panels and result arrays (hipHostMalloc): DMA at PCIe rate, asynchronous. */
 int tp_host_alloc(void** out, int64_t bytes);
 int tp_host_free(void* p);

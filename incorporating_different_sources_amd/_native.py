@@ -42,6 +42,7 @@ EXPORTS = [
     "tp_log_returns", "tp_batch_create", "tp_batch_upload", "tp_batch_upload_async", "tp_batch_upload_wait",
     "tp_batch_shared_gram_blocks",
     "tp_batch_shared_intraday_blocks",
+    "tp_addressing_flags", "tp_batch_addressing",
     "tp_host_alloc", "tp_host_free", "tp_batch_set_rhs", "tp_batch_set_shift", "tp_batch_keep_rhs",
     "tp_batch_download_rhs", "tp_batch_keep_posterior", "tp_batch_download_posterior", "tp_batch_run", "tp_batch_download", "tp_batch_download_S1", "tp_batch_download_matrix",
     "tp_batch_solve_sweep", "tp_batch_solve_sweep_tiled", "tp_batch_download_sweep", "tp_batch_download_sweep_rhs",
@@ -101,6 +102,8 @@ def _load():
     lib.tp_batch_upload_wait.argtypes = [c_void_p]
     lib.tp_batch_shared_gram_blocks.argtypes = [c_void_p]
     lib.tp_batch_shared_intraday_blocks.argtypes = [c_void_p]
+    lib.tp_addressing_flags.argtypes = [c_int64, c_int32, c_int32]
+    lib.tp_batch_addressing.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int)]
     lib.tp_host_alloc.argtypes = [POINTER(c_void_p), c_int64]
     lib.tp_host_free.argtypes = [c_void_p]
     lib.tp_batch_keep_rhs.argtypes = [c_void_p, c_int]
@@ -171,6 +174,12 @@ def max_assets() -> int:
 def sweep_max_assets() -> int:
     """Largest k `Batch.solve_sweep` covers (`tp_sweep_max_assets`)."""
     return int(lib.tp_sweep_max_assets())
+
+
+def addressing_flags(panel_bytes: int, ld: int, rows_per_window: int) -> int:
+    """`tp_addressing_flags`: bit 0 - explicit-row windows, bit 1 - contiguous windows of such a panel load through
+    32-bit byte offsets; a clear bit means 64-bit addresses.  Needs no device."""
+    return int(lib.tp_addressing_flags(int(panel_bytes), int(ld), int(rows_per_window)))
 
 
 def device_count() -> int:
@@ -513,6 +522,13 @@ class Batch:
     def shared_intraday_blocks(self) -> int:
         """Large-k path, conjugate: whole intraday blocks (days) per window taken from shared block Grams (0: none)."""
         return int(lib.tp_batch_shared_intraday_blocks(self._b))
+
+    def addressing(self) -> tuple:
+        """`tp_batch_addressing` after an upload: (daily, intraday) flag words of `addressing_flags` as the next launch sees
+        them; the intraday word is 0 for a batch without an intraday panel."""
+        pf, hf = c_int(), c_int()
+        self.dev._check(lib.tp_batch_addressing(self._b, ctypes.byref(pf), ctypes.byref(hf)))
+        return pf.value, hf.value
 
     def keep_rhs(self, on=True):
         """Keep the right-hand side every window is solved for in later runs (`download_rhs` reads the last run's)."""

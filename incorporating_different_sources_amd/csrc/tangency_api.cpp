@@ -161,18 +161,7 @@ tp_kargs_t tp_host::make_kargs(tp_batch_t b) {
     a.w_count = b->W;
     a.panel_ld = b->panel_ld;
     a.hf_ld = b->hf_ld;
-    // 32-bit addressing of the staging loads: row x (8 ld) as a 24 x 24 bit product that fits 32 bits
-    auto off32 = [](size_t bytes, int ld, int rows_per_window) {
-        if (ld < 1 || (size_t)ld * 8 >= (1u << 24)) return 0;
-        const size_t rows = bytes / ((size_t)ld * 8);
-        int f = 0;
-        if (bytes < (1ull << 32) && rows < (1u << 24)) f |= 1;
-        // + 64: the lean loop advances its row offset one chunk past the window before it is clamped
-        if (((size_t)rows_per_window + 64) * ld * 8 < (1ull << 32) && (size_t)rows_per_window < (1u << 24)) f |= 2;
-        return f;
-    };
-    a.panel_off32 = off32(b->panel.bytes, b->panel_ld, b->p.n_r);
-    a.hf_off32 = b->hf_panel.p ? off32(b->hf_panel.bytes, b->hf_ld, b->p.m) : 0;
+    (void)tp_batch_addressing(b, &a.panel_off32, &a.hf_off32);   // tp_addressing_flags of the two panels: 32-bit offsets or not
     a.k = b->p.k; a.N = b->p.N; a.n_r = b->p.n_r; a.m = b->p.m; a.strategy = b->p.strategy;
     a.gamma = b->p.gamma;
     return a;
@@ -549,6 +538,25 @@ int tp_host_free(void* p) {
     if (!p) return TP_OK;
     if (g_shut_down.load()) return TP_OK;           // after the exit handler: no call into a runtime that is shutting down
     return hipHostFree(p) == hipSuccess ? TP_OK : TP_ERR_HIP;
+}
+
+// 32-bit addressing of the staging loads: row x (8 ld) as a 24 x 24 bit product that fits 32 bits
+int tp_addressing_flags(int64_t panel_bytes, int32_t ld, int32_t rows_per_window) {
+    const size_t bytes = (size_t)panel_bytes;
+    if (ld < 1 || (size_t)ld * 8 >= (1u << 24)) return 0;
+    const size_t rows = bytes / ((size_t)ld * 8);
+    int f = 0;
+    if (bytes < (1ull << 32) && rows < (1u << 24)) f |= 1;
+    // + 64: the lean loop advances its row offset one chunk past the window before it is clamped
+    if (((size_t)rows_per_window + 64) * ld * 8 < (1ull << 32) && (size_t)rows_per_window < (1u << 24)) f |= 2;
+    return f;
+}
+
+int tp_batch_addressing(tp_batch_t b, int* panel_flags, int* hf_flags) {
+    if (!b) return TP_ERR_INVALID;
+    if (panel_flags) *panel_flags = tp_addressing_flags((int64_t)b->panel.bytes, b->panel_ld, b->p.n_r);
+    if (hf_flags) *hf_flags = b->hf_panel.p ? tp_addressing_flags((int64_t)b->hf_panel.bytes, b->hf_ld, b->p.m) : 0;
+    return TP_OK;
 }
 
 int tp_batch_shared_gram_blocks(tp_batch_t b) { return b ? b->prefix_nblk : 0; }
