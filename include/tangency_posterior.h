@@ -143,6 +143,10 @@ int tp_destroy(tp_handle_t h);
  *   "wave_preload"     1 the one-wave kernel starts a window's accumulators from its shared table slot wherever the batch
  *                      qualifies (plain conjugate, contiguous layout with shared sums, k mod 16 <= 13) | -1 automatic: there,
  *                      at the sizes where that measured faster | 0 never (A/B measurements); any other value: TP_ERR_INVALID
+ *   "shared_tables"    how a register-tile batch (k <= 239) with shared sums builds its block-window tables, every run:
+ *                      1 one kernel straight from the daily panel | 0 the pair of kernels used before (block Grams to
+ *                      memory, then their sums) | -1 automatic: the one kernel at the tile counts where it measured faster.
+ *                      The tables are the same bit for bit; any other value: TP_ERR_INVALID.  No environment variable
  *   "no_shared_gram"   1 = as if every batch carried TP_FLAG_NO_SHARED_GRAM (takes effect at the next upload)
  *   "tiled_arena_gib" / "tiled_arena_mib"  in-flight arena of the large-k path (0: default)
  *   "hf_share_min_blocks"  large-k path, conjugate: intraday windows that advance by a fixed stride share the Grams of
@@ -153,6 +157,10 @@ int tp_destroy(tp_handle_t h);
  *                      results do not depend on it
  * Replaces nothing in the reference. */
 int tp_set_option(tp_handle_t h, const char* name, int value);
+/* The current value of an option tp_set_option takes, and one read-only name: "last_shared_tables" = what built the
+ * tables of the last tp_batch_run on the register-tile path: 1 the one kernel, 0 the pair, -1 the batch had none (or the
+ * run was on the large-k path).  An unknown name: TP_ERR_INVALID. */
+int tp_get_option(tp_handle_t h, const char* name, int* value);
 const char* tp_last_error(tp_handle_t h); /* h may be NULL: last error of a failed tp_create */
 int tp_device_info(tp_handle_t h, char* name, int name_len, int* compute_units, int* clock_mhz,
                    int64_t* hbm_bytes);

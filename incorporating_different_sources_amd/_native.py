@@ -37,7 +37,7 @@ SWEEP_MAX_RHS = 16
 
 # every symbol include/tangency_posterior.h declares (checked by tests/test_cabi_symbols.py)
 EXPORTS = [
-    "tp_version", "tp_max_assets", "tp_sweep_max_assets", "tp_device_count", "tp_create", "tp_destroy", "tp_set_option", "tp_last_error",
+    "tp_version", "tp_max_assets", "tp_sweep_max_assets", "tp_device_count", "tp_create", "tp_destroy", "tp_set_option", "tp_get_option", "tp_last_error",
     "tp_device_info",
     "tp_log_returns", "tp_batch_create", "tp_batch_upload", "tp_batch_upload_async", "tp_batch_upload_wait",
     "tp_batch_shared_gram_blocks",
@@ -93,6 +93,7 @@ def _load():
     lib.tp_create.argtypes = [c_int, POINTER(c_void_p)]
     lib.tp_destroy.argtypes = [c_void_p]
     lib.tp_set_option.argtypes = [c_void_p, c_char_p, c_int]
+    lib.tp_get_option.argtypes = [c_void_p, c_char_p, POINTER(c_int)]
     lib.tp_device_info.argtypes = [c_void_p, c_char_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int64)]
     lib.tp_log_returns.argtypes = [c_void_p, POINTER(c_double), c_int64, c_int32, POINTER(c_int32), POINTER(c_int32),
                                    c_int64, POINTER(c_double)]
@@ -311,12 +312,21 @@ class Device:
 
     def set_option(self, name: str, value: int):
         """`tp_set_option`: kernel-selection switches of this handle ("wave_kernel", "tiled_wave", "tiled_fuse",
-        "wave_preload", "no_shared_gram", "tiled_arena_gib", "tiled_arena_mib", "hf_share_min_blocks",
+        "wave_preload", "shared_tables", "no_shared_gram", "tiled_arena_gib", "tiled_arena_mib", "hf_share_min_blocks",
         "sweep_chunk_windows": windows per sub-range of `Batch.solve_sweep`, 0 = automatic); the TP_* environment
-        variables are read once, when the Device is created.  An unknown name or a value an option does not take raises
-        TangencyError."""
+        variables are read once, when the Device is created.  "shared_tables": 1 = a register-tile batch with shared sums
+        builds its block-window tables in one kernel straight from the daily panel, 0 = with the pair of kernels used
+        before, -1 (default) = the one kernel at the tile counts where it measured faster; the tables are the same bit
+        for bit.  An unknown name or a value an option does not take raises TangencyError."""
         self._check(lib.tp_set_option(self._h, name.encode(), int(value)))
         return self
+
+    def get_option(self, name: str) -> int:
+        """`tp_get_option`: the current value of an option, or of the read-only "last_shared_tables" (what built the
+        tables of the last register-tile run: 1 the one kernel, 0 the pair, -1 none)."""
+        v = c_int()
+        self._check(lib.tp_get_option(self._h, name.encode(), ctypes.byref(v)))
+        return v.value
 
     def _check(self, rc):
         if rc != TP_OK:

@@ -1232,6 +1232,7 @@ hipError_t launch_one(const tp_kargs_t& a, int grid, hipStream_t stream, tp_laun
     using C = Cfg<NT, NW>;
     static_assert(C::CH == TP_PREFIX_BLOCK_ROWS(NT), "posterior_kernels.h: block rows of the shared Gram prefixes");
     if (wave_mode(a) == 2) wave = nullptr;         // read-backs, custom right-hand sides, shifts: the multi-wave kernel
+    if (info) info->shared_tables = -1;
     if (!tp_layout_is_lean(a)) {
         // general layout: the one- / two-wave kernels stage a pass's row indices in LDS (posterior_wave_impl.h,
         // WCfg::OFF_SUB); a batch whose passes are too long for that is answered with hipErrorNotSupported before anything
@@ -1244,16 +1245,25 @@ hipError_t launch_one(const tp_kargs_t& a, int grid, hipStream_t stream, tp_laun
     }
     if (a.winsum != nullptr) {
         // the shared sums first, on the same stream: part of every run, nothing is kept between runs
-        static std::atomic<unsigned long long> attr_done{0};
-        { hipError_t e = tp_allow_dynamic_lds(attr_done, block_gram_kernel<NT, NW>, C::LDS_BYTES); if (e != hipSuccess) return e; }
-        hipLaunchKernelGGL((block_gram_kernel<NT, NW>), dim3((unsigned)a.prefix_nblk), dim3(C::NTHREADS), C::LDS_BYTES, stream, a,
-                           (double*)a.prefix);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
         int n_L = 0;
         while (n_L < TP_WINSUM_MAX_L && a.winsum_L[n_L] > 0) ++n_L;
-        e = tp_window_sums_launch(a.prefix, (double*)a.winsum, a.prefix_nblk, (size_t)C::NTILES * 256, a.winsum_L, n_L, stream);
-        if (e != hipSuccess) return e;
+        const bool one_kernel = a.shared_tables == 1 || (a.shared_tables < 0 && tp_shared_tables_pays(NT));
+        if (one_kernel) {
+            // the tables straight from the panel (posterior_shared_tables.hip): the G region of the buffer stays unwritten
+            const hipError_t e = tp_shared_tables_launch(a.panel, a.panel_ld, a.k, (double*)a.winsum, a.prefix_nblk, a.winsum_L, n_L,
+                                                         stream);
+            if (e != hipSuccess) return e;
+        } else {
+            static std::atomic<unsigned long long> attr_done{0};
+            { hipError_t e = tp_allow_dynamic_lds(attr_done, block_gram_kernel<NT, NW>, C::LDS_BYTES); if (e != hipSuccess) return e; }
+            hipLaunchKernelGGL((block_gram_kernel<NT, NW>), dim3((unsigned)a.prefix_nblk), dim3(C::NTHREADS), C::LDS_BYTES, stream,
+                               a, (double*)a.prefix);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            e = tp_window_sums_launch(a.prefix, (double*)a.winsum, a.prefix_nblk, (size_t)C::NTILES * 256, a.winsum_L, n_L, stream);
+            if (e != hipSuccess) return e;
+        }
+        if (info) info->shared_tables = one_kernel ? 1 : 0;
     }
     if (wave) {
         const hipError_t e = wave(a, grid, stream, info, true);

@@ -1,6 +1,7 @@
 // posterior_kernels.h - internal interface between the host layer (tangency_api.cpp, tangency_sweep.cpp) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #define TP_KSTATUS_OK 0
@@ -51,7 +52,8 @@ struct tp_kargs_t {
     const double* w0;
     const double* n0;
     const double* prefix; // optional (contiguous layout, no rf_adj): workspace of the shared Gram sums of the daily panel:
-                          // the per-block Grams G[prefix_nblk][slot], filled by every launch before the window kernel
+                          // the per-block Grams G[prefix_nblk][slot], filled by every launch before the window kernel (the
+                          // register-tile path builds its tables without them unless shared_tables says otherwise: left unwritten)
     int prefix_nblk;      // whole TP_PREFIX_BLOCK_ROWS-row blocks of the panel
     int prefix_blk0;      // large-k path: the tables cover blocks prefix_blk0 .. prefix_blk0 + prefix_nblk - 1 (those of the
                           // sub-batch in flight; a whole-panel table at k = 1000 and 125,000 windows would be 102 GB); else 0
@@ -84,6 +86,10 @@ struct tp_kargs_t {
     int k, N, n_r, m, strategy;
     int phase_limit;      // diagnostic (TP_PHASE_LIMIT): 1 = stop after the Gram phases (outputs are then invalid)
     int center_rows;      // Jeffreys: 0 = J = T - t t'/N, 1 = divide by the window's row count instead, 2 = plain T
+    int shared_tables;    // host-side only, the handle's option "shared_tables": how launch_one builds the Q tables: 1 = one
+                          // kernel from the panel (posterior_shared_tables.hip), 0 = block_gram_kernel + tp_window_sums_kernel,
+                          // -1 = the one kernel at the tile counts where it measured faster (tp_shared_tables_pays).  It sits
+                          // in the 4 bytes of padding in front of gamma and not in tp_kopts_t: no kernel's argument offsets move
     double gamma;
     tp_kopts_t opts;      // host-side only: which kernels run this batch
     // (behind everything else: the kernels that do not read it keep their argument offsets)
@@ -91,7 +97,12 @@ struct tp_kargs_t {
                                  // that have no slot of their own (posterior_wave_impl.h, PRE); null: the batch does not qualify
 };
 
-struct tp_launch_info_t { int grid, block, lds_bytes, ntile; };
+static_assert(sizeof(tp_kargs_t) == 376 && offsetof(tp_kargs_t, gamma) == 344 && offsetof(tp_kargs_t, winsum_zero) == 368,
+              "tp_kargs_t: a new member moved the kernels' argument offsets");
+
+// shared_tables: what built the Q tables of the last register-tile launch: -1 = the batch has none, 0 = the pair of
+// kernels, 1 = the one kernel (tp_get_option "last_shared_tables")
+struct tp_launch_info_t { int grid, block, lds_bytes, ntile, shared_tables = -1; };
 
 // Shared Gram prefixes of the register-tile path: aligned blocks of the staged chunk's rows (16; 32 with eight waves,
 // NT >= 13); 16 rows on the tiled path.
@@ -110,6 +121,14 @@ inline size_t tp_fused_prefix_bytes(int k, long long panel_rows, int n_L, int* n
 // abs0: absolute block index of table position 0 (groups are cut in absolute positions: posterior_fused.hip)
 hipError_t tp_window_sums_launch(const double* G, double* Q, int nblk, size_t slot_doubles, const int* L, int n_L,
                                  hipStream_t stream, long long abs0 = 0);
+// The same Q_L tables, bit for bit, in ONE kernel straight from the daily panel (posterior_shared_tables.hip): no block
+// Grams in memory.  Register-tile path only (slot layout of block_gram_kernel, blocks of TP_PREFIX_BLOCK_ROWS rows, table
+// position 0 = block 0).
+hipError_t tp_shared_tables_launch(const double* panel, int ld, int k, double* Q, int nblk, const int* L, int n_L,
+                                   hipStream_t stream);
+// Tile counts at which the automatic choice (shared_tables = -1) takes the one kernel: where it measured faster than the
+// pair on MI355X (profiles/r23_shared_tables_bench.txt)
+bool tp_shared_tables_pays(int nt);
 
 // which register-tile kernel runs a tile count: 0 = the multi-wave kernel (posterior_fused_impl.h), 1 = one wave per
 // window (posterior_wave_impl.h), 2 = two / four waves per window (posterior_wave2_impl.h); `choice` =

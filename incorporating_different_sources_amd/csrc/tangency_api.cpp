@@ -147,6 +147,7 @@ tp_kargs_t tp_host::make_kargs(tp_batch_t b) {
     a.phase_limit = b->h->phase_limit;                // diagnostic build only (TP_PHASE_LIMIT, read in tp_create)
 #endif
     a.opts = b->h->opts;
+    a.shared_tables = b->h->shared_tables;
     a.weights = b->out_weights();
     a.status = (int*)b->out_status();
     a.aux = (double*)b->aux.p;
@@ -344,6 +345,10 @@ int tp_set_option(tp_handle_t h, const char* name, int value) {
         if (value < -1 || value > 1) return fail(h, TP_ERR_INVALID, "tp_set_option: wave_preload=%d is not -1, 0 or 1", value);
         h->opts.wave_preload = value;
     }
+    else if (n == "shared_tables") {
+        if (value < -1 || value > 1) return fail(h, TP_ERR_INVALID, "tp_set_option: shared_tables=%d is not -1, 0 or 1", value);
+        h->shared_tables = value;
+    }
     else if (n == "no_shared_gram") h->no_shared_gram = value != 0;
     else if (n == "tiled_arena_gib") h->tiled_arena_gib = value;
     else if (n == "tiled_arena_mib") h->tiled_arena_mib = value;
@@ -353,6 +358,24 @@ int tp_set_option(tp_handle_t h, const char* name, int value) {
         h->sweep_chunk_windows = value;
     }
     else return fail(h, TP_ERR_INVALID, "tp_set_option: unknown option '%s'", name);
+    return TP_OK;
+}
+
+int tp_get_option(tp_handle_t h, const char* name, int* value) {
+    if (!h || !name || !value) return TP_ERR_INVALID;
+    const std::string n(name);
+    if (n == "wave_kernel") *value = h->opts.wave_kernel;
+    else if (n == "tiled_wave") *value = h->opts.tiled_wave;
+    else if (n == "tiled_fuse") *value = h->opts.tiled_fuse;
+    else if (n == "wave_preload") *value = h->opts.wave_preload;
+    else if (n == "shared_tables") *value = h->shared_tables;
+    else if (n == "last_shared_tables") *value = h->last_launch.shared_tables;   // read-only: what the last run did
+    else if (n == "no_shared_gram") *value = h->no_shared_gram;
+    else if (n == "tiled_arena_gib") *value = h->tiled_arena_gib;
+    else if (n == "tiled_arena_mib") *value = h->tiled_arena_mib;
+    else if (n == "hf_share_min_blocks") *value = h->hf_share_min_blocks;
+    else if (n == "sweep_chunk_windows") *value = h->sweep_chunk_windows;
+    else return fail(h, TP_ERR_INVALID, "tp_get_option: unknown option '%s'", name);
     return TP_OK;
 }
 

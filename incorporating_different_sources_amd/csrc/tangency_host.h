@@ -47,6 +47,8 @@ struct tp_handle_s {
     // tp_set_option on this handle - no launch path reads the environment (several host threads launch at once in the
     // one-process-all-GPUs mode while a test may be changing it).
     tp_kopts_t opts{};
+    int shared_tables = -1;         // "shared_tables": the Q tables of the register-tile path from one kernel (1), from the pair
+                                    // (0), or the one kernel where it measured faster (-1); read by every run (tp_kargs_t)
     int no_shared_gram = 0;         // TP_NO_SHARED_GRAM / "no_shared_gram"
     int hf_share_min_blocks = 6;    // "hf_share_min_blocks": whole intraday blocks per window from which the large-k path shares them
     int tiled_arena_gib = 0;        // TP_TILED_ARENA_GIB / "tiled_arena_gib" (0: default)

@@ -212,8 +212,9 @@ int plan_hf_tables(tp_batch_t b, tp_kargs_t& sub) {
 }
 
 // Rolling windows over one shared panel overlap almost entirely; the register-tile path then takes the whole aligned
-// row blocks of every window from running Gram sums of the panel that all windows share (posterior_fused_impl.h,
-// block_gram_kernel + tp_window_sums_kernel; the tiled path: tiled_prefix_kernel) instead of pushing every row of every window through the MFMAs.  Qualifies: contiguous windows
+// row blocks of every window from block-window Gram sums of the panel that all windows share (one kernel straight from the
+// panel, posterior_shared_tables.hip - or, option shared_tables = 0, block_gram_kernel + tp_window_sums_kernel; the tiled
+// path: tiled_block_gram_kernel + tp_window_sums_kernel) instead of pushing every row of every window through the MFMAs.  Qualifies: contiguous windows
 // (start[]), no column gather, no per-row risk-free adjustment, k in the register-tile range, and windows that
 // together cover the panel at least three times.  The sums are recomputed by EVERY tp_batch_run (nothing is kept
 // between runs); TP_FLAG_NO_SHARED_GRAM switches the scheme off.
@@ -251,8 +252,9 @@ int plan_shared_gram(tp_batch_t b, const tp_inputs_t* in, hipStream_t st) {
         bytes = fused ? tp_fused_prefix_bytes(p.k, rows, n_L, &nblk) : tp_tiled_prefix_bytes(p.k, rows, n_L, &nblk);
     }
     if (nblk < 2 || (double)b->W * p.n_r < 3.0 * (double)rows) return TP_OK;
-    // a handful of tiny windows: the two extra launches cost more than the rows they save (configs[0], k = 10, 100 windows:
-    // 28.6 us with the shared sums, 21.5 us without)
+    // a handful of tiny windows: building the tables costs more than the rows they save (configs[0], k = 10, 100 windows:
+    // 28.6 us with the shared sums, 21.5 us without - measured when the tables took two launches; the gate decides which
+    // batches share and so what they compute, and stays where it is)
     if (p.k <= 31 && b->W < 256) return TP_OK;
     if (p.k > tp_fused_max_assets()) {
         // large-k path: a slot is megabytes (4.35 MB at k = 1000), a table over the whole panel of a long run does not fit
