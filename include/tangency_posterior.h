@@ -618,6 +618,58 @@ int tp_batch_destroy(tp_batch_t b);
 int tp_posterior_batch(tp_handle_t h, const tp_params_t* p, int64_t W, const tp_inputs_t* in,
                        double* weights, int32_t* status, double* aux);
 
+/* Backtest replay: the daily loop of ref:1127-1219 - mark to market, weight drift, rebalance, turnover (ref:1054-1075), weight
+ * metrics and the distance to the value-weighted portfolio (ref:1077-1104) - for MANY portfolios whose weights at every
+ * rebalancing date are already in hand (a sweep's download, a spec grid), one wavefront per portfolio in one launch.  Replaces
+ * the loop over dates of backtest_portfolio (ref:1232) around Portfolio.update_portfolio, per spec.
+ *
+ * tp_replay_merge_maps needs no device.  For a universe table cols [R x k] (row j at cols + j * stride; entries are ticker
+ * indices in [0, K), no ticker twice in a row) it fills, both [R x k] dense:
+ *     prev_slot[j][i] = the slot ticker cols[j][i] held at date j-1, or -1 (row 0: all -1)
+ *     next_slot[j][i] = the slot ticker cols[j][i] holds at date j+1, or -1 (row R-1: all -1)
+ * so that the outer merge of the turnover needs no table of K entries on the device.  TP_ERR_INVALID: an index outside [0, K),
+ * a ticker twice in one row, R < 1, k < 1, K < 1, stride < 0, a NULL pointer (tp_last_error(NULL) has the message). */
+int tp_replay_merge_maps(const int32_t* cols, int64_t R, int32_t k, int64_t stride, int32_t K,
+                         int32_t* prev_slot /* [R x k] */, int32_t* next_slot /* [R x k] */);
+/* One call for all portfolios that share trading days and a rebalancing schedule; every pointer is a HOST pointer.
+ * Shared: S [D x ld] simple returns of trading day d (row 0 is not read; NaN allowed), of which the first K columns are tickers;
+ * rf_daily [D]; reb_day [R] the trading-day index of every rebalancing date, strictly increasing, reb_day[0] == 0, all < D.
+ * Portfolio p < P holds k[p] assets; at rebalancing date j its weights are weights[w_off[p] + j w_stride[p] + i], its tickers
+ * cols[u_off[p] + j u_stride[p] + i] and their market caps caps[u_off[p] + j u_stride[p] + i], i < k[p] - offsets and strides in
+ * elements, so that a sweep's download [W x P x n_len x n_size x k] is replayed where it lies and the specs of one family
+ * share one universe table.  weights_len / universe_len: elements of the flat buffers (cols and caps have one shape).
+ * Per trading day d >= 1, in the operations and order of ref:1131-1164 with the NaN-skipping sums pandas uses:
+ *     r_i = S[d][col_i] ;  cash = 1 - nansum(w) ;  returns[p][d] = nansum(r w) + cash rf_daily[d]
+ *     drifted = w (1 + r) ;  total = nansum(drifted) + cash (1 + rf_daily[d]) ;  w = drifted / total
+ *     |(sum(w) + cash (1 + rf_daily[d]) / total) - 1| > 1e-5 (plain sum: a NaN never trips it): status[p] = TP_REPLAY_SUM_CHECK,
+ *     bad_day[p] = d, the portfolio's outputs from that day and rebalancing date on are NaN and its loop ends (ref:1160-1162)
+ * and per rebalancing date j, after the day's mark to market: metrics[p][j] = max_long, max_short, avg_long, avg_short (NaN for
+ * an empty side; the first two are selections, bit-equal to the input weight) and nanmean |w scaling[p] - caps / nansum(caps)|;
+ * for j > 0 turnover[p][j] = (sum over the union of |before - after|, a missing or NaN entry as 0, + |nansum(before) -
+ * nansum(after)|) / 2 and returns[p][reb_day[j]] -= cost[p] / 10000 * turnover[p][j] (ref:1212).
+ * Every sum is a lane-local partial sum in slot order and a fixed 64-lane tree: a portfolio's results are the same bit for bit
+ * from run to run, alone or among others, packed densely or in place.  Against the host's summation order they agree to
+ * rounding.
+ * TP_ERR_INVALID: D, R, P, ld, K out of range, a NULL array, reb_day[0] != 0 or not strictly increasing below D, k[p] < 1, an
+ * offset or stride that is negative or runs past its buffer (checked without overflow), a column index outside [0, K), a ticker
+ * twice in one row.  TP_ERR_UNSUPPORTED: k[p] > tp_max_assets().  TP_ERR_HIP: an allocation failed (the message names the byte
+ * count).  The merge maps are built inside the call, once per distinct (u_off, u_stride, k).
+ * The call waits for whatever was queued on the handle's stream, copies every input to the device (no host pointer is kept),
+ * and queues one launch per slots-per-lane class (k <= 64, 128, 256, ...) without waiting for it.  kernel_ms of tp_last_timing
+ * covers the launches (one HIP-event pair; one step of tp_region_steps); tp_last_launch keeps describing tp_batch_run.  The
+ * buffers belong to the handle and are kept until tp_destroy; batches and their results are left alone. */
+#define TP_REPLAY_SUM_CHECK 1 /* status[p]: "Weights do not sum to 1." (ref:1160-1162) on day bad_day[p] */
+int tp_replay_run(tp_handle_t h, int64_t D, int32_t ld, const double* S /* [D x ld] */, const double* rf_daily /* [D] */,
+                  int64_t R, const int32_t* reb_day /* [R] */, int32_t K,
+                  int64_t P, const int32_t* k /* [P] */, const double* scaling /* [P] */, const double* cost /* [P] */,
+                  const int64_t* w_off /* [P] */, const int64_t* w_stride /* [P] */,
+                  const int64_t* u_off /* [P] */, const int64_t* u_stride /* [P] */,
+                  const double* weights, int64_t weights_len, const int32_t* cols, const double* caps, int64_t universe_len);
+/* Waits for the replay and copies out returns [P x D] (returns[p][0] is NaN), turnover [P x R] (turnover[p][0] is NaN), metrics
+ * [P x R x 5], status [P] (0 or TP_REPLAY_SUM_CHECK) and bad_day [P] (-1 without a status); each may be NULL.  Without a
+ * tp_replay_run before it: TP_ERR_INVALID. */
+int tp_replay_download(tp_handle_t h, double* returns, double* turnover, double* metrics, int32_t* status, int32_t* bad_day);
+
 int tp_synchronize(tp_handle_t h);
 /* Timings of the most recent call of each kind on this handle, in milliseconds (HIP events on the
  * handle's stream): posterior kernel, H2D upload, D2H download, RCCL gather. */

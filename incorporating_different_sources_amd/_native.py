@@ -34,6 +34,8 @@ FLAG_NO_CENTER = 2
 FLAG_NO_SHARED_GRAM = 4
 UNIQUE_ID_BYTES = 128
 SWEEP_MAX_RHS = 16
+REPLAY_SUM_CHECK = 1
+REPLAY_METRICS = 5
 
 # every symbol include/tangency_posterior.h declares (checked by tests/test_cabi_symbols.py)
 EXPORTS = [
@@ -50,6 +52,7 @@ EXPORTS = [
     "tp_batch_size_sweep", "tp_batch_size_sweep_tiled", "tp_batch_download_size_sweep",
     "tp_batch_window_sweep", "tp_batch_window_sweep_tiled", "tp_batch_download_window_sweep",
     "tp_batch_grid_sweep", "tp_batch_grid_sweep_tiled", "tp_batch_download_grid_sweep",
+    "tp_replay_merge_maps", "tp_replay_run", "tp_replay_download",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
     "tp_comm_count", "tp_comm_init_all", "tp_group_gather",
@@ -142,6 +145,13 @@ def _load():
     lib.tp_batch_destroy.argtypes = [c_void_p]
     lib.tp_posterior_batch.argtypes = [c_void_p, POINTER(tp_params_t), c_int64, POINTER(tp_inputs_t),
                                        POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
+    lib.tp_replay_merge_maps.argtypes = [POINTER(c_int32), c_int64, c_int32, c_int64, c_int32, POINTER(c_int32), POINTER(c_int32)]
+    lib.tp_replay_run.argtypes = [c_void_p, c_int64, c_int32, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_int32),
+                                  c_int32, c_int64, POINTER(c_int32), POINTER(c_double), POINTER(c_double),
+                                  POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
+                                  POINTER(c_double), c_int64, POINTER(c_int32), POINTER(c_double), c_int64]
+    lib.tp_replay_download.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32),
+                                       POINTER(c_int32)]
     lib.tp_synchronize.argtypes = [c_void_p]
     lib.tp_last_timing.argtypes = [c_void_p] + [POINTER(c_double)] * 4
     lib.tp_region_begin.argtypes = [c_void_p]
@@ -181,6 +191,24 @@ def addressing_flags(panel_bytes: int, ld: int, rows_per_window: int) -> int:
     """`tp_addressing_flags`: bit 0 - explicit-row windows, bit 1 - contiguous windows of such a panel load through
     32-bit byte offsets; a clear bit means 64-bit addresses.  Needs no device."""
     return int(lib.tp_addressing_flags(int(panel_bytes), int(ld), int(rows_per_window)))
+
+
+def replay_merge_maps(cols, K: int):
+    """`tp_replay_merge_maps` for a universe table `cols` [R x k] of ticker indices in [0, K): (prev_slot, next_slot), both
+    [R x k] - the slot each ticker of date j held at j-1 / holds at j+1, or -1.  Needs no device.  Raises TangencyError
+    (TP_ERR_INVALID) for an index outside [0, K) or a ticker twice in one row."""
+    if cols is None or np.asarray(cols).dtype.kind not in "iu":
+        raise ValueError("cols: an integer array is expected")
+    c = np.ascontiguousarray(cols, dtype=np.int32)
+    if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] < 1:
+        raise ValueError(f"cols: expected shape (R, k) with R, k >= 1, got {tuple(c.shape)}")
+    R, k = c.shape
+    prev_slot = np.empty((R, k), dtype=np.int32)
+    next_slot = np.empty((R, k), dtype=np.int32)
+    rc = lib.tp_replay_merge_maps(_ptr(c, c_int32), R, k, k, int(K), _ptr(prev_slot, c_int32), _ptr(next_slot, c_int32))
+    if rc != TP_OK:
+        raise TangencyError(rc, lib.tp_last_error(None).decode())
+    return prev_slot, next_slot
 
 
 def device_count() -> int:
@@ -429,6 +457,93 @@ class Device:
         self._check(lib.tp_log_returns(self._h, _ptr(P, c_double), P.shape[0], P.shape[1], _ptr(num, c_int32),
                                        _ptr(den, c_int32), num.size, _ptr(out, c_double)))
         return out
+
+    # ---- backtest replay ----------------------------------------------------------------------
+    def replay(self, S, rf_daily, reb_day, K, k, scaling, cost, w_off, w_stride, u_off, u_stride, weights, cols, caps):
+        """`tp_replay_run` + `tp_replay_download`: daily P&L, weight drift, turnover and weight metrics of P portfolios that
+        share trading days and a rebalancing schedule, one wavefront each.  `S` [D x ld] simple returns (the first `K` columns
+        are tickers), `rf_daily` [D], `reb_day` [R] trading-day indices (strictly increasing from 0, below D).  Portfolio p
+        holds `k[p]` assets; at rebalancing date j its weights are `weights.flat[w_off[p] + j * w_stride[p] + i]`, its tickers
+        and their caps `cols.flat[...]` / `caps.flat[u_off[p] + j * u_stride[p] + i]` (cols and caps have one shape).  Every
+        check is made before any device call.  Returns (returns [P, D], turnover [P, R], metrics [P, R, 5], status [P],
+        bad_day [P]); returns[:, 0] and turnover[:, 0] are NaN; status REPLAY_SUM_CHECK: the weights of that portfolio stopped
+        summing to 1 on day bad_day (the host replay raises there)."""
+        def real(name, a, ndim=None):
+            if a is None or np.asarray(a).dtype.kind not in "fiu":
+                raise ValueError(f"{name}: a real floating-point array is expected, got dtype {np.asarray(a).dtype}")
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if ndim is not None and a.ndim != ndim:
+                raise ValueError(f"{name}: a {ndim}-D array is expected, got shape {tuple(a.shape)}")
+            return a
+
+        def integer(name, a, dtype, shape=None):
+            if a is None or np.asarray(a).dtype.kind not in "iu":
+                raise ValueError(f"{name}: an integer array is expected")
+            wide = np.asarray(a)
+            if wide.size and (wide.min() < np.iinfo(dtype).min or wide.max() > np.iinfo(dtype).max):
+                raise ValueError(f"{name}: an entry does not fit {np.dtype(dtype).name}")
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if shape is not None and a.shape != shape:
+                raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
+            return a
+
+        S = real("S", S, 2)
+        D, ld = S.shape
+        if D < 1 or ld < 1:
+            raise ValueError(f"S: at least one day and one column expected, got shape {tuple(S.shape)}")
+        K = int(K)
+        if not 1 <= K <= ld:
+            raise ValueError(f"K={K}: within [1, {ld}] (the columns of S) expected")
+        rf = real("rf_daily", rf_daily)
+        if rf.shape != (D,):
+            raise ValueError(f"rf_daily: expected shape ({D},), got {tuple(rf.shape)}")
+        reb = integer("reb_day", reb_day, np.int32)
+        if reb.ndim != 1 or reb.size < 1:
+            raise ValueError(f"reb_day: a 1-D array of at least one day is expected, got shape {tuple(reb.shape)}")
+        if reb[0] != 0:
+            raise ValueError(f"reb_day[0]={int(reb[0])}: the first trading day rebalances")
+        if (np.diff(reb) <= 0).any() or reb[-1] >= D:
+            raise ValueError(f"reb_day: strictly increasing below D={D} expected")
+        R = int(reb.size)
+        kk = integer("k", k, np.int32)
+        if kk.ndim != 1:
+            raise ValueError(f"k: a 1-D array is expected, got shape {tuple(kk.shape)}")
+        P = int(kk.size)
+        if P and kk.min() < 1:
+            raise ValueError("k: every portfolio holds at least one asset")
+        if P and kk.max() > max_assets():
+            raise ValueError(f"k={int(kk.max())} exceeds the largest supported universe {max_assets()}")
+        sc, co = real("scaling", scaling), real("cost", cost)
+        for name, a in (("scaling", sc), ("cost", co)):
+            if a.shape != (P,):
+                raise ValueError(f"{name}: expected shape ({P},), got {tuple(a.shape)}")
+        wo, wst, uo, ust = (integer(name, a, np.int64, (P,)) for name, a in
+                            (("w_off", w_off), ("w_stride", w_stride), ("u_off", u_off), ("u_stride", u_stride)))
+        wts = real("weights", weights).reshape(-1)
+        cl = integer("cols", cols, np.int32).reshape(-1)
+        cp = real("caps", caps).reshape(-1)
+        if cl.size != cp.size:
+            raise ValueError(f"cols and caps: one shape expected, got {cl.size} and {cp.size} elements")
+        for name, off, stride, n in (("w", wo, wst, wts.size), ("u", uo, ust, cl.size)):
+            for p in range(P):
+                o, s = int(off[p]), int(stride[p])          # (Python integers: no overflow)
+                if o < 0 or s < 0 or o + (R - 1) * s + int(kk[p]) > n:
+                    raise ValueError(f"{name}_off[{p}]={o}, {name}_stride[{p}]={s}: {R} rows of {int(kk[p])} run past the buffer's "
+                                     f"{n} elements")
+        # (the column indices themselves are checked by the library, on the host, while it builds the merge maps)
+        returns = np.empty((P, D), dtype=np.float64)
+        turnover = np.empty((P, R), dtype=np.float64)
+        metrics = np.empty((P, R, REPLAY_METRICS), dtype=np.float64)
+        status = np.empty(P, dtype=np.int32)
+        bad_day = np.empty(P, dtype=np.int32)
+        nz = lambda a, ct: _ptr(a if a.size else None, ct)   # noqa: E731
+        self._check(lib.tp_replay_run(self._h, D, ld, _ptr(S, c_double), _ptr(rf, c_double), R, _ptr(reb, c_int32), K, P,
+                                      nz(kk, c_int32), nz(sc, c_double), nz(co, c_double), nz(wo, c_int64), nz(wst, c_int64),
+                                      nz(uo, c_int64), nz(ust, c_int64), nz(wts, c_double), wts.size, nz(cl, c_int32),
+                                      nz(cp, c_double), cl.size))
+        self._check(lib.tp_replay_download(self._h, nz(returns, c_double), nz(turnover, c_double), nz(metrics, c_double),
+                                           nz(status, c_int32), nz(bad_day, c_int32)))
+        return returns, turnover, metrics, status, bad_day
 
     # ---- batches ------------------------------------------------------------------------------
     def batch(self, strategy, k, N, n_r, gamma, W, m=0, flags=0) -> "Batch":

@@ -1,5 +1,5 @@
 // tangency_host.h - internal to the host layer of libtangency.so (tangency_api.cpp, tangency_sweep.cpp,
-// tangency_plan.cpp, tangency_comm.cpp): the handle and batch structures and the helpers the four files share.
+// tangency_plan.cpp, tangency_comm.cpp, tangency_replay.cpp): the handle and batch structures and the helpers the files share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -20,7 +20,18 @@
 #include "posterior_solve_sweep_tiled.h"
 #include "posterior_window_sweep.h"
 
+#include "backtest_replay.h"
+
 #define TP_REGION_MAX_STEPS 512
+
+// Backtest replay (tp_replay_run / tp_replay_download, tangency_replay.cpp): the inputs and results of the last run.  The
+// replay belongs to the handle, not to a batch; plain DevBufs, freed with the handle.
+struct ReplayWs {
+    DevBuf S, rf, reb, weights, cols, caps, prev, next, port, order;
+    DevBuf ret, turnover, metrics, status, bad_day;
+    int64_t P = 0, D = 0, R = 0;    // shape of the last run
+    bool ran = false;               // a run completed its launches (tp_replay_download has something to copy)
+};
 
 // Members are destroyed in reverse order of declaration: the kernel stream is declared before every other stream and
 // event, so it goes last (destroy_handle takes the communicator down before any of them).
@@ -62,6 +73,7 @@ struct tp_handle_s {
     int ring_used = 0;
     bool in_region = false;
     std::vector<double> step_ms;
+    ReplayWs replay;                // tp_replay_run / tp_replay_download (destroy_handle drains the stream before it goes)
 };
 
 struct PriceStaging { DevBuf prices, num, den; };   // price front-end: prices and the row pairs of the returns

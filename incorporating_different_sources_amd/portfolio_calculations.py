@@ -1617,6 +1617,77 @@ def _replay_backtest(trading_dates, rebalance_dates, weights, cols, caps, ticker
                 columns=["max_long", "max_short", "avg_long", "avg_short", "average_distance_to_comparison_portfolio"])}
 
 
+# `backtest_portfolios` replays its specs on the device (`replay_backtests_device`: one call per group of specs with the same
+# rebalancing frequency and ticker list) instead of one host loop per spec.  Opt-in: the host replay is the default and the
+# yardstick; the two agree to the rounding of their summation orders.
+DEVICE_REPLAY = False
+
+
+def replay_backtests_device(trading_dates, rebalance_dates, items, market_data, tickers=None, device=None):
+    """`_replay_backtest` for MANY specs in ONE device call (`_native.Device.replay`): `items` is a list of
+    (weights [R x k], cols [R x k], caps [R x k], portfolio_spec) over the same trading dates, rebalancing dates and ticker
+    list (`tickers`; default: the panels' of the first spec's window frequency).  Returns, per item, the dict
+    `_replay_backtest` returns - same indices, names, dtypes and columns.  Arrays that are the same object (the universe and
+    caps of one spec family, the passive weights) are packed and uploaded once."""
+    items = list(items)
+    if not items:
+        return []
+    if tickers is None:
+        tickers = batch.panels_for(market_data, items[0][3]["rolling_window_frequency"]).tickers
+    sr = market_data["stock_simple_returns_df"]
+    missing = [ts for ts in trading_dates[1:] if ts not in sr.index]
+    if missing:
+        raise KeyError(missing[0])                                        # ref:1134 `.loc[trading_date_ts]`
+    S = sr.reindex(index=pd.DatetimeIndex(trading_dates), columns=tickers).to_numpy(dtype=np.float64)
+    rf_daily = (_rf_asof(market_data["risk_free_rate_df"], trading_dates) + 1) ** (1 / 252) - 1         # ref:1140
+    day_of = {ts: d for d, ts in enumerate(trading_dates)}
+    reb_day = np.array([day_of[ts] for ts in rebalance_dates], dtype=np.int32)
+    R = len(rebalance_dates)
+    w_parts, c_parts, p_parts, w_at, u_at = [], [], [], {}, {}
+    w_len = u_len = 0
+    ks, scaling, cost, w_off, u_off = [], [], [], [], []
+    for weights, cols, caps, spec in items:
+        k = int(np.shape(cols)[1])
+        if np.shape(weights) != (R, k) or np.shape(cols) != (R, k) or np.shape(caps) != (R, k):
+            raise ValueError(f"{spec['display_name']}: weights, cols and caps of shape ({R}, k) expected, got "
+                             f"{np.shape(weights)}, {np.shape(cols)}, {np.shape(caps)}")
+        if id(weights) not in w_at:
+            w_at[id(weights)] = w_len
+            w_parts.append(np.ascontiguousarray(weights, dtype=np.float64).reshape(-1))
+            w_len += R * k
+        if (id(cols), id(caps)) not in u_at:
+            u_at[(id(cols), id(caps))] = u_len
+            c_parts.append(np.ascontiguousarray(cols, dtype=np.int32).reshape(-1))
+            p_parts.append(np.ascontiguousarray(caps, dtype=np.float64).reshape(-1))
+            u_len += R * k
+        ks.append(k)
+        scaling.append(spec["risk_aversion"] if spec.get("risk_aversion") is not None else 1)
+        cost.append(spec["turnover_cost"])
+        w_off.append(w_at[id(weights)])
+        u_off.append(u_at[(id(cols), id(caps))])
+    ks = np.array(ks, dtype=np.int32)
+    stride = ks.astype(np.int64)
+    dev = device if device is not None else _native.default_device()
+    returns, turnover, metrics, status, _bad_day = dev.replay(
+        S, rf_daily, reb_day, len(tickers), ks, np.array(scaling, dtype=np.float64), np.array(cost, dtype=np.float64),
+        np.array(w_off, dtype=np.int64), stride, np.array(u_off, dtype=np.int64), stride,
+        np.concatenate(w_parts), np.concatenate(c_parts), np.concatenate(p_parts))
+    if np.any(np.asarray(status) != 0):
+        logger.error("Weights do not sum to 1.")
+        raise ValueError("Weights do not sum to 1.")
+    days = pd.DatetimeIndex(trading_dates)
+    reb = pd.DatetimeIndex(rebalance_dates)
+    out = []
+    for p, (_w, _c, _m, spec) in enumerate(items):
+        name = spec["display_name"]
+        out.append({"portfolio_simple_returns_series": pd.Series(returns[p, 1:], index=days[1:], name=name, dtype="float64"),
+                    "portfolio_turnover_series": pd.Series(turnover[p, 1:], index=reb[1:], name=name, dtype="float64"),
+                    "portfolio_weights_metrics_df": pd.DataFrame(
+                        metrics[p], index=reb, dtype="float64",
+                        columns=["max_long", "max_short", "avg_long", "avg_short", "average_distance_to_comparison_portfolio"])})
+    return out
+
+
 def backtest_portfolio(portfolio_spec, ts_start_date, ts_end_date, market_data):
     """Same inputs and outputs as ref:1221-1238.  All posterior solves of the backtest happen in ONE device
     batch, and the daily replay runs over arrays (`_replay_backtest`); `Portfolio.update_portfolio` remains the
@@ -1645,9 +1716,24 @@ def backtest_portfolios(portfolio_specs_dict, ts_start_date, ts_end_date, market
         if len(specs) > 1:
             calculate_weights_for_specs(rebalancing_schedule(trading_dates, specs[0]["rebalancing_frequency"]), specs, market_data)
     out = {}
+    pending = {}          # DEVICE_REPLAY: (rebalancing frequency, ticker list) -> [(name, weights, cols, caps, spec)]
     for name, sp in portfolio_specs_dict.items():
         if sp["weighting_strategy"] in _OUT_OF_SCOPE and sp["weighting_strategy"] not in _EXTERNAL_STRATEGIES:
             logger.warning(f"{name}: {sp['weighting_strategy']} is outside the scope of this build (pypfopt); skipped.")
             continue
-        out[name] = backtest_portfolio(sp, ts_start_date, ts_end_date, market_data)
+        if not DEVICE_REPLAY:
+            out[name] = backtest_portfolio(sp, ts_start_date, ts_end_date, market_data)
+            continue
+        # every spec's weights as `backtest_portfolio` obtains them; the replay waits for the whole group
+        rebalance_dates = rebalancing_schedule(trading_dates, sp["rebalancing_frequency"])
+        _prefetch_siblings(sp, rebalance_dates, market_data)
+        weights, labels, cols, caps = _weights_for_dates(rebalance_dates, sp, market_data)
+        tickers = batch.panels_for(market_data, sp["rolling_window_frequency"]).tickers
+        out[name] = None                                                  # (keeps the specs' order)
+        pending.setdefault((sp["rebalancing_frequency"], tuple(tickers)), []).append((name, weights, cols, caps, sp))
+    for (frequency, tickers), members in pending.items():
+        results = replay_backtests_device(trading_dates, rebalancing_schedule(trading_dates, frequency),
+                                          [m[1:] for m in members], market_data, tickers=list(tickers))
+        for m, res in zip(members, results):
+            out[m[0]] = res
     return out

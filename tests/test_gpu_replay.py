@@ -1,0 +1,346 @@
+"""The device backtest replay (-m gpu): `tp_replay_run` against the host replay `_replay_backtest` on identical inputs, the
+reference's goldens through `backtest_portfolios` with DEVICE_REPLAY on, independence of a portfolio from the launch it
+shares, the in-place sweep layout, and the turnover cost.
+
+Tolerance of the comparisons with the host (rtol 1e-10, atol 1e-12): two summation orders of k terms differ by at most
+2 (k-1) 2^-53 sum|terms|; the drift carries that over at most 64 days, about 2e-12 relative at k = 130; the project's golden
+comparisons of these series use rtol 1e-9, atol 1e-12.  max_long / max_short are selections and must be bit-equal.
+
+The sum check (status TP_REPLAY_SUM_CHECK) trips on the host only when the portfolio's value is within rounding of zero; such
+inputs - finite, no overflow - are found by a scan on the CPU inside the test (Case F)."""
+import os
+
+import numpy as np
+import pandas as pd
+import pytest
+
+from incorporating_different_sources_amd import synthetic
+
+from conftest import GOLDEN
+
+pytestmark = pytest.mark.gpu
+
+RTOL, ATOL = 1e-10, 1e-12
+METRIC_COLS = ["max_long", "max_short", "avg_long", "avg_short", "average_distance_to_comparison_portfolio"]
+
+
+@pytest.fixture(scope="module")
+def pc():
+    from incorporating_different_sources_amd import portfolio_calculations
+    return portfolio_calculations
+
+
+@pytest.fixture(scope="module")
+def dev():
+    from incorporating_different_sources_amd import _native
+    return _native.default_device()
+
+
+def _spec(name, freq, cost=15, gamma=None):
+    return {"weighting_strategy": "external", "size": 0, "risk_aversion": gamma, "turnover_cost": cost,
+            "rebalancing_frequency": freq, "rolling_window": 20, "rolling_window_frequency": "daily", "mcm_scaling": None,
+            "display_name": name}
+
+
+def _market(D, K, seed):
+    """Simple returns [D x K] with ticker 0 missing (NaN) on days 5 .. 9, and a risk-free frame."""
+    rng = np.random.default_rng(seed)
+    days = [pd.Timestamp(d) for d in pd.bdate_range("2021-01-04", periods=D)]
+    tickers = [f"T{i:04d}" for i in range(K)]
+    S = rng.normal(0.0005, 0.02, (D, K))
+    S[5:10, 0] = np.nan
+    md = {"stock_simple_returns_df": pd.DataFrame(S, index=pd.DatetimeIndex(days), columns=tickers),
+          "risk_free_rate_df": pd.DataFrame({"rf": 0.01 + 0.02 * rng.random(D)}, index=pd.DatetimeIndex(days))}
+    return days, tickers, md
+
+
+def _universes(rng, R, k, K):
+    """[R x k] ticker indices: every date drops and adds some tickers and now and then reorders the rest; ticker 0 (the
+    one with missing returns) is held on three dates out of four."""
+    rows, cur = [], rng.permutation(np.arange(1, K))[:k]
+    for j in range(R):
+        cur = cur[cur != 0]
+        free = np.setdiff1d(np.arange(1, K), cur)
+        if cur.size < k:
+            cur = np.append(cur, rng.permutation(free)[:k - cur.size])
+        elif j > 0 and free.size:
+            n_swap = min(int(rng.integers(0, max(2, k // 4 + 1))), free.size)
+            at = rng.permutation(k)[:n_swap]
+            cur = cur.copy()
+            cur[at] = rng.permutation(free)[:n_swap]
+        if j % 3 == 1:
+            cur = rng.permutation(cur)
+        if j % 4 != 3:
+            cur = cur.copy()
+            cur[int(rng.integers(k))] = 0
+        rows.append(cur.copy())
+    cols = np.array(rows, dtype=np.int32)
+    assert all(np.unique(r).size == k for r in cols)
+    return cols
+
+
+def _items(rng, R, k, K, freq):
+    """Four portfolios over two universe tables: long / short and levered (the cash position is negative for some), long
+    only (no short side: max_short and avg_short are NaN), NaN entries in the caps, another cost and scaling."""
+    cols_a, cols_b = _universes(rng, R, k, K), _universes(rng, R, k, K)
+    caps_a = rng.lognormal(3, 1, (R, k))
+    caps_b = rng.lognormal(3, 1, (R, k))
+    caps_b[rng.random((R, k)) < 0.2] = np.nan
+    caps_b[0, 0] = np.nan
+    mixed = rng.normal(0.02, 0.4, (R, k))
+    mixed[0] = np.abs(mixed[0]) * 1.7 / np.abs(mixed[0]).sum() * np.sign(rng.normal(size=k) + 0.8)
+    long_only = np.abs(rng.normal(0.0, 1.0, (R, k)))
+    long_only *= rng.uniform(0.5, 1.6, (R, 1)) / long_only.sum(axis=1, keepdims=True)
+    return [(mixed, cols_a, caps_a, _spec("mixed", freq)),
+            (long_only, cols_a, caps_a, _spec("long_only", freq, cost=0)),
+            (rng.normal(0.0, 0.3, (R, k)), cols_b, caps_b, _spec("nan_caps", freq, cost=35, gamma=5)),
+            (mixed, cols_b, caps_b, _spec("other_universe", freq, cost=5, gamma=2.5))]
+
+
+CASES = [(k, freq, 64) for k in (1, 5, 63, 64, 65, 130) for freq in ("daily", "weekly", "monthly")] + [(300, "weekly", 12)]
+_case_cache = {}
+
+
+def _case(pc, k, freq, D):
+    """Inputs and the host's results of one case, computed once and shared."""
+    key = (k, freq, D)
+    if key not in _case_cache:
+        K = 2 * k + 7
+        days, tickers, md = _market(D, K, seed=1000 + k)
+        reb = pc.rebalancing_schedule(days, freq)
+        items = _items(np.random.default_rng(7 * k + len(reb)), len(reb), k, K, freq)
+        host = [pc._replay_backtest(days, reb, w, c, m, tickers, sp, md) for w, c, m, sp in items]
+        _case_cache[key] = (days, tickers, md, reb, items, host)
+    return _case_cache[key]
+
+
+def _assert_same_as_host(got, want, what):
+    for key in ("portfolio_simple_returns_series", "portfolio_turnover_series"):
+        assert got[key].index.equals(want[key].index) and got[key].name == want[key].name and got[key].dtype == want[key].dtype
+        np.testing.assert_allclose(got[key].to_numpy(), want[key].to_numpy(), rtol=RTOL, atol=ATOL, equal_nan=True,
+                                   err_msg=f"{what} {key}")
+    g, w = got["portfolio_weights_metrics_df"], want["portfolio_weights_metrics_df"]
+    assert g.index.equals(w.index) and list(g.columns) == list(w.columns) == METRIC_COLS
+    for c in ("max_long", "max_short"):                                   # selections: bit-equal
+        assert np.array_equal(g[c].to_numpy(), w[c].to_numpy(), equal_nan=True), f"{what} {c}"
+    np.testing.assert_allclose(g.to_numpy(), w.to_numpy(), rtol=RTOL, atol=ATOL, equal_nan=True, err_msg=f"{what} metrics")
+
+
+@pytest.mark.filterwarnings("ignore:Mean of empty slice")                 # k = 1 with a NaN cap: the host's nanmean of nothing
+@pytest.mark.parametrize("k,freq,D", CASES)
+def test_replay_matches_the_host_replay(pc, k, freq, D):
+    """Case A."""
+    days, tickers, md, reb, items, host = _case(pc, k, freq, D)
+    got = pc.replay_backtests_device(days, reb, items, md, tickers=tickers)
+    assert len(got) == len(host)
+    for (w, c, m, sp), g, h in zip(items, got, host):
+        _assert_same_as_host(g, h, f"k={k} {freq} {sp['display_name']}")
+    if k > 1:
+        metrics = host[1]["portfolio_weights_metrics_df"]                 # the long-only portfolio has no short side
+        assert metrics["max_short"].isna().all() and metrics["avg_short"].isna().all()
+        assert got[1]["portfolio_weights_metrics_df"]["avg_short"].isna().all()
+    if freq != "daily" and k > 1:
+        # the missing returns leave NaN weights behind until the next rebalance; the turnover counts them as 0
+        assert np.isfinite(host[0]["portfolio_turnover_series"].to_numpy()).all()
+        assert np.isfinite(got[0]["portfolio_turnover_series"].to_numpy()).all()
+
+
+def test_sum_check_trips_where_the_host_raises(pc, dev):
+    """Case F.  Finite inputs for which `_replay_backtest` raises "Weights do not sum to 1.": a levered position whose loss
+    on day 3 takes the portfolio's value to within rounding of zero (total ~ 1e-12 of wealth 1), so the renormalised weights
+    are ~ 1e14 and their sum misses 1 by far more than 1e-5.  No overflow: every intermediate is finite.  Candidates around the
+    exact wipe-out are scanned on the CPU; with k = 2 both sides round the same operations in the same order, so the
+    device's status is set for exactly the candidates the host raises for, on the host's day."""
+    D, K = 8, 4
+    days, tickers, md = _market(D, K, seed=77)
+    S = md["stock_simple_returns_df"].to_numpy()
+    rf = (pc._rf_asof(md["risk_free_rate_df"], days) + 1) ** (1 / 252) - 1
+    reb, reb_day = [days[0], days[2], days[5]], np.array([0, 2, 5], dtype=np.int32)
+    cols = np.tile(np.array([1, 2], dtype=np.int32), (3, 1))
+    caps = np.ones((3, 2))
+    w1 = 0.3
+    wipe_out = -(1 + rf[3] + w1 * (S[3, 2] - rf[3])) / (S[3, 1] - rf[3])    # total of day 3 = 0 in exact arithmetic
+    spec = _spec("wiped_out", "monthly")
+
+    def host_day(w):
+        """The day the host raises on (None: it does not): the shortest prefix of the trading days that raises."""
+        for n_days in range(2, D + 1):
+            try:
+                pc._replay_backtest(days[:n_days], [ts for ts in reb if ts in days[:n_days]], w, cols, caps, tickers, spec, md)
+            except ValueError as exc:
+                assert str(exc) == "Weights do not sum to 1."
+                return n_days - 1
+        return None
+
+    raised, passed = [], []
+    for n in range(-300, 301):
+        w = np.array([[0.7, -0.2], [wipe_out * (1 + n * 2.0 ** -47), w1], [0.5, 0.2]])
+        assert np.isfinite(w).all()
+        day = host_day(w)
+        (raised if day is not None else passed).append((w, day))
+        if len(raised) >= 20 and len(passed) >= 20:
+            break
+    assert len(raised) >= 5, "no candidate trips the host's check"
+    chosen = raised[:20] + passed[:20]
+    assert all(day == 3 for _, day in raised)
+    P = len(chosen)
+    returns, turnover, metrics, status, bad_day = dev.replay(
+        S=S, rf_daily=rf, reb_day=reb_day, K=K, k=np.full(P, 2, dtype=np.int32), scaling=np.ones(P), cost=np.full(P, 15.0),
+        w_off=np.arange(P, dtype=np.int64) * 6, w_stride=np.full(P, 2, dtype=np.int64), u_off=np.zeros(P, dtype=np.int64),
+        u_stride=np.full(P, 2, dtype=np.int64), weights=np.concatenate([w.reshape(-1) for w, _ in chosen]), cols=cols, caps=caps)
+    for p, (w, day) in enumerate(chosen):
+        if day is None:                                                   # (a total of exactly 0 leaves NaN behind and no status)
+            assert status[p] == 0 and bad_day[p] == -1
+            with np.errstate(all="ignore"):
+                want = pc._replay_backtest(days, reb, w, cols, caps, tickers, spec, md)
+            np.testing.assert_allclose(returns[p, 1:], want["portfolio_simple_returns_series"].to_numpy(), rtol=RTOL, atol=ATOL,
+                                       equal_nan=True)
+            np.testing.assert_allclose(turnover[p, 1:], want["portfolio_turnover_series"].to_numpy(), rtol=RTOL, atol=ATOL,
+                                       equal_nan=True)
+        else:
+            assert status[p] == 1 and bad_day[p] == day
+            assert np.isfinite(returns[p, 1:day]).all() and np.isnan(returns[p, day:]).all()      # the outputs end with that day
+            assert np.isfinite(turnover[p, 1]) and np.isnan(turnover[p, 2])
+            assert np.isfinite(metrics[p, :2]).all() and np.isnan(metrics[p, 2]).all()
+    with pytest.raises(ValueError, match="Weights do not sum to 1."):
+        pc.replay_backtests_device(days, reb, [(chosen[0][0], cols, caps, spec)], md, tickers=tickers)
+    ok = pc.replay_backtests_device(days, reb, [(chosen[-1][0], cols, caps, spec)], md, tickers=tickers)
+    _assert_same_as_host(ok[0], pc._replay_backtest(days, reb, chosen[-1][0], cols, caps, tickers, spec, md), "not wiped out")
+
+
+def _golden_spec(strat, g):
+    simple = strat in ("vw", "ew")
+    return {"weighting_strategy": strat, "size": int(g["size"]), "risk_aversion": None if simple else 5, "turnover_cost": 15,
+            "rebalancing_frequency": str(g["rebal"]), "rolling_window": int(g["N"]),
+            "rolling_window_frequency": str(g["window_freq"]),
+            "mcm_scaling": None if simple or strat in ("jeffreys", "jorion", "greyserman") else 1, "display_name": strat}
+
+
+@pytest.mark.parametrize("name,strats", [("backtest_k10_n60_daily", None),
+                                         ("backtest_k8_n30_weekly_monthly", ["vw"]),
+                                         ("backtest_k6_n9_monthly_weekly", ["ew"]),
+                                         ("backtest_shipped_k50_n250_weekly_monthly", ["vw", "ew"])])
+def test_goldens_through_the_device_replay(pc, monkeypatch, name, strats):
+    """Case B: the reference's recorded series through `backtest_portfolios` with DEVICE_REPLAY on - the passive cases of
+    test_passive_backtests_match_reference, and every strategy of backtest_k10_n60_daily but the randomised one."""
+    g = np.load(os.path.join(GOLDEN, name + ".npz"))
+    md, _ = synthetic.make_market_data(n_tickers=int(g["n_tickers"]), n_days=int(g["n_days"]), seed=int(g["seed"]),
+                                       rf_nan_every=int(g["rf_nan_every"]))
+    days = md["stock_prices_df"].index
+    if strats is None:
+        strats = [str(s) for s in g["strategies"] if str(s) != "greyserman"]
+    calls = []
+    real = pc.replay_backtests_device
+    monkeypatch.setattr(pc, "replay_backtests_device", lambda *a, **kw: (calls.append(len(a[2])), real(*a, **kw))[1])
+    monkeypatch.setattr(pc, "_replay_backtest", lambda *a, **kw: pytest.fail("the host replay ran"))
+    monkeypatch.setattr(pc, "DEVICE_REPLAY", True)
+    res = pc.backtest_portfolios({s: _golden_spec(s, g) for s in strats}, days[int(g["start_idx"])], days[-1], md)
+    assert calls == [len(strats)] and list(res) == strats                 # one group: one device call
+    for strat in strats:
+        r, t, mdf = (res[strat]["portfolio_simple_returns_series"], res[strat]["portfolio_turnover_series"],
+                     res[strat]["portfolio_weights_metrics_df"])
+        assert r.name == strat and t.name == strat and list(mdf.columns) == METRIC_COLS
+        for series, key in ((r, "returns_dates"), (t, "turnover_dates"), (mdf, "metrics_dates")):
+            if f"{strat}_{key}" in g.files:                               # (the shipped configuration records the metrics' dates only)
+                assert np.array_equal(series.index.values.astype("datetime64[ns]").astype(np.int64), g[f"{strat}_{key}"])
+        assert len(r) == len(g[f"{strat}_returns"]) and len(t) == len(g[f"{strat}_turnover"])
+        np.testing.assert_allclose(r.to_numpy(), g[f"{strat}_returns"], rtol=1e-9, atol=1e-12, err_msg=strat)
+        np.testing.assert_allclose(t.to_numpy(), g[f"{strat}_turnover"], rtol=1e-9, atol=1e-12, err_msg=strat)
+        np.testing.assert_allclose(mdf.to_numpy(), g[f"{strat}_metrics"], rtol=1e-9, atol=1e-12, equal_nan=True, err_msg=strat)
+
+
+def _flat_call(rng, D, K, reb_day, ks, n_tables=3):
+    """Arguments of `Device.replay` for len(ks) portfolios of mixed size, cost and scaling, packed densely."""
+    R = len(reb_day)
+    S = rng.normal(0.0005, 0.02, (D, K))
+    S[3:6, 0] = np.nan
+    weights, cols, caps, w_off, u_off, tables = [], [], [], [], [], {}
+    w_len = u_len = 0
+    for p, k in enumerate(ks):
+        key = (k, p % n_tables)
+        if key not in tables:
+            tables[key] = u_len
+            cols.append(_universes(rng, R, k, K).reshape(-1))
+            caps.append(rng.lognormal(3, 1, R * k))
+            u_len += R * k
+        u_off.append(tables[key])
+        w_off.append(w_len)
+        weights.append(rng.normal(0.01, 0.3, R * k))
+        w_len += R * k
+    ks = np.array(ks, dtype=np.int32)
+    return dict(S=S, rf_daily=0.0001 * rng.random(D), reb_day=np.array(reb_day, dtype=np.int32), K=K, k=ks,
+                scaling=rng.choice([1.0, 2.5, 5.0], len(ks)), cost=rng.choice([0.0, 5.0, 15.0, 35.0], len(ks)),
+                w_off=np.array(w_off, dtype=np.int64), w_stride=ks.astype(np.int64),
+                u_off=np.array(u_off, dtype=np.int64), u_stride=ks.astype(np.int64),
+                weights=np.concatenate(weights), cols=np.concatenate(cols), caps=np.concatenate(caps))
+
+
+def _same_bytes(a, b):
+    return all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
+
+
+def test_portfolios_do_not_depend_on_their_launch(dev):
+    """Case C: 33 portfolios of mixed size, cost and scaling in one call; each equals, byte for byte, itself run alone and
+    the whole call run a second time."""
+    rng = np.random.default_rng(33)
+    ks = [int(k) for k in rng.choice([1, 5, 40, 63, 64, 65, 100, 130, 200], 33)]
+    ks[:4] = [130, 1, 65, 64]
+    kw = _flat_call(rng, D=40, K=420, reb_day=[0, 1, 2, 7, 8, 20, 39], ks=ks)
+    first = dev.replay(**kw)
+    assert (first[3] == 0).all() and (first[4] == -1).all()
+    assert np.isnan(first[0][:, 0]).all() and np.isnan(first[1][:, 0]).all()
+    assert np.isfinite(first[0][:, 1:]).all() and np.isfinite(first[1][:, 1:]).all()
+    assert _same_bytes(first, dev.replay(**kw))
+    for p in range(len(ks)):
+        alone = dict(kw)
+        for name in ("k", "scaling", "cost", "w_off", "w_stride", "u_off", "u_stride"):
+            alone[name] = kw[name][p:p + 1]
+        assert _same_bytes([x[p:p + 1] for x in first], dev.replay(**alone)), f"portfolio {p} (k={ks[p]})"
+
+
+def test_sweep_download_is_replayed_where_it_lies(dev):
+    """Case D: the weights laid out as a grid sweep's download [W x P x L x S x k] (W: the rebalancing dates; a smaller
+    size is a prefix of the universe, zero beyond it), addressed through w_off / w_stride, against the same portfolios
+    packed densely."""
+    rng = np.random.default_rng(44)
+    W, P, L, sizes, k, K, D = 6, 2, 3, [5, 70], 70, 160, 30
+    n_s = len(sizes)
+    grid = np.zeros((W, P, L, n_s, k))
+    for s, ks in enumerate(sizes):
+        grid[..., s, :ks] = rng.normal(0.01, 0.3, (W, P, L, ks))
+    cols = _universes(rng, W, k, K)
+    caps = rng.lognormal(3, 1, (W, k))
+    S = rng.normal(0.0005, 0.02, (D, K))
+    entries = [(p, l, s) for p in range(P) for l in range(L) for s in range(n_s)]
+    n = len(entries)
+    shared = dict(S=S, rf_daily=np.full(D, 0.0001), reb_day=np.array([0, 4, 9, 10, 21, 29], dtype=np.int32), K=K,
+                  k=np.array([sizes[s] for _, _, s in entries], dtype=np.int32), scaling=np.full(n, 5.0),
+                  cost=np.full(n, 15.0), u_off=np.zeros(n, dtype=np.int64), u_stride=np.full(n, k, dtype=np.int64),
+                  cols=cols, caps=caps)
+    in_place = dev.replay(weights=grid, w_off=np.array([((p * L + l) * n_s + s) * k for p, l, s in entries], dtype=np.int64),
+                          w_stride=np.full(n, P * L * n_s * k, dtype=np.int64), **shared)
+    dense = np.concatenate([grid[:, p, l, s, :sizes[s]].reshape(-1) for p, l, s in entries])
+    lens = np.array([W * sizes[s] for _, _, s in entries], dtype=np.int64)
+    packed = dev.replay(weights=dense, w_off=np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64),
+                        w_stride=shared["k"].astype(np.int64), **shared)
+    assert (in_place[3] == 0).all() and np.isfinite(in_place[0][:, 1:]).all()
+    assert _same_bytes(in_place, packed)
+
+
+def test_turnover_cost_is_subtracted_as_on_the_host(dev):
+    """Case E: two portfolios that differ only in `cost`: the same turnover byte for byte; the returns differ on the
+    rebalancing days by exactly fl(fl(cost / 10000) * turnover), subtracted once, and on no other day."""
+    rng = np.random.default_rng(55)
+    kw = _flat_call(rng, D=30, K=150, reb_day=[0, 3, 4, 11, 29], ks=[70, 70])
+    for name in ("w_off", "u_off", "scaling"):
+        kw[name] = np.repeat(kw[name][:1], 2)
+    kw["cost"] = np.array([0.0, 35.0])
+    returns, turnover, metrics, status, _ = dev.replay(**kw)
+    assert (status == 0).all()
+    assert turnover[0].tobytes() == turnover[1].tobytes() and metrics[0].tobytes() == metrics[1].tobytes()
+    want = returns[0].copy()
+    for j, d in enumerate(kw["reb_day"]):
+        if j > 0:
+            want[d] -= 35.0 / 10000 * turnover[0, j]                      # the host's expression (`_replay_backtest`)
+    assert want.tobytes() == returns[1].tobytes()
+    assert (turnover[0, 1:] > 0).all() and (returns[0, kw["reb_day"][1:]] != returns[1, kw["reb_day"][1:]]).all()
