@@ -11,17 +11,14 @@ inputs - finite, no overflow - are found by a scan on the CPU inside the test (C
 import os
 
 import numpy as np
-import pandas as pd
 import pytest
 
 from incorporating_different_sources_amd import synthetic
 
 from conftest import GOLDEN
+from _replay_cases import ATOL, CASES, METRIC_COLS, RTOL, _flat_call, _market, _same_bytes, _spec, _universes, case_inputs
 
 pytestmark = pytest.mark.gpu
-
-RTOL, ATOL = 1e-10, 1e-12
-METRIC_COLS = ["max_long", "max_short", "avg_long", "avg_short", "average_distance_to_comparison_portfolio"]
 
 
 @pytest.fixture(scope="module")
@@ -36,68 +33,6 @@ def dev():
     return _native.default_device()
 
 
-def _spec(name, freq, cost=15, gamma=None):
-    return {"weighting_strategy": "external", "size": 0, "risk_aversion": gamma, "turnover_cost": cost,
-            "rebalancing_frequency": freq, "rolling_window": 20, "rolling_window_frequency": "daily", "mcm_scaling": None,
-            "display_name": name}
-
-
-def _market(D, K, seed):
-    """Simple returns [D x K] with ticker 0 missing (NaN) on days 5 .. 9, and a risk-free frame."""
-    rng = np.random.default_rng(seed)
-    days = [pd.Timestamp(d) for d in pd.bdate_range("2021-01-04", periods=D)]
-    tickers = [f"T{i:04d}" for i in range(K)]
-    S = rng.normal(0.0005, 0.02, (D, K))
-    S[5:10, 0] = np.nan
-    md = {"stock_simple_returns_df": pd.DataFrame(S, index=pd.DatetimeIndex(days), columns=tickers),
-          "risk_free_rate_df": pd.DataFrame({"rf": 0.01 + 0.02 * rng.random(D)}, index=pd.DatetimeIndex(days))}
-    return days, tickers, md
-
-
-def _universes(rng, R, k, K):
-    """[R x k] ticker indices: every date drops and adds some tickers and now and then reorders the rest; ticker 0 (the
-    one with missing returns) is held on three dates out of four."""
-    rows, cur = [], rng.permutation(np.arange(1, K))[:k]
-    for j in range(R):
-        cur = cur[cur != 0]
-        free = np.setdiff1d(np.arange(1, K), cur)
-        if cur.size < k:
-            cur = np.append(cur, rng.permutation(free)[:k - cur.size])
-        elif j > 0 and free.size:
-            n_swap = min(int(rng.integers(0, max(2, k // 4 + 1))), free.size)
-            at = rng.permutation(k)[:n_swap]
-            cur = cur.copy()
-            cur[at] = rng.permutation(free)[:n_swap]
-        if j % 3 == 1:
-            cur = rng.permutation(cur)
-        if j % 4 != 3:
-            cur = cur.copy()
-            cur[int(rng.integers(k))] = 0
-        rows.append(cur.copy())
-    cols = np.array(rows, dtype=np.int32)
-    assert all(np.unique(r).size == k for r in cols)
-    return cols
-
-
-def _items(rng, R, k, K, freq):
-    """Four portfolios over two universe tables: long / short and levered (the cash position is negative for some), long
-    only (no short side: max_short and avg_short are NaN), NaN entries in the caps, another cost and scaling."""
-    cols_a, cols_b = _universes(rng, R, k, K), _universes(rng, R, k, K)
-    caps_a = rng.lognormal(3, 1, (R, k))
-    caps_b = rng.lognormal(3, 1, (R, k))
-    caps_b[rng.random((R, k)) < 0.2] = np.nan
-    caps_b[0, 0] = np.nan
-    mixed = rng.normal(0.02, 0.4, (R, k))
-    mixed[0] = np.abs(mixed[0]) * 1.7 / np.abs(mixed[0]).sum() * np.sign(rng.normal(size=k) + 0.8)
-    long_only = np.abs(rng.normal(0.0, 1.0, (R, k)))
-    long_only *= rng.uniform(0.5, 1.6, (R, 1)) / long_only.sum(axis=1, keepdims=True)
-    return [(mixed, cols_a, caps_a, _spec("mixed", freq)),
-            (long_only, cols_a, caps_a, _spec("long_only", freq, cost=0)),
-            (rng.normal(0.0, 0.3, (R, k)), cols_b, caps_b, _spec("nan_caps", freq, cost=35, gamma=5)),
-            (mixed, cols_b, caps_b, _spec("other_universe", freq, cost=5, gamma=2.5))]
-
-
-CASES = [(k, freq, 64) for k in (1, 5, 63, 64, 65, 130) for freq in ("daily", "weekly", "monthly")] + [(300, "weekly", 12)]
 _case_cache = {}
 
 
@@ -105,10 +40,7 @@ def _case(pc, k, freq, D):
     """Inputs and the host's results of one case, computed once and shared."""
     key = (k, freq, D)
     if key not in _case_cache:
-        K = 2 * k + 7
-        days, tickers, md = _market(D, K, seed=1000 + k)
-        reb = pc.rebalancing_schedule(days, freq)
-        items = _items(np.random.default_rng(7 * k + len(reb)), len(reb), k, K, freq)
+        days, tickers, md, reb, items = case_inputs(k, freq, D)
         host = [pc._replay_backtest(days, reb, w, c, m, tickers, sp, md) for w, c, m, sp in items]
         _case_cache[key] = (days, tickers, md, reb, items, host)
     return _case_cache[key]
@@ -247,36 +179,6 @@ def test_goldens_through_the_device_replay(pc, monkeypatch, name, strats):
         np.testing.assert_allclose(r.to_numpy(), g[f"{strat}_returns"], rtol=1e-9, atol=1e-12, err_msg=strat)
         np.testing.assert_allclose(t.to_numpy(), g[f"{strat}_turnover"], rtol=1e-9, atol=1e-12, err_msg=strat)
         np.testing.assert_allclose(mdf.to_numpy(), g[f"{strat}_metrics"], rtol=1e-9, atol=1e-12, equal_nan=True, err_msg=strat)
-
-
-def _flat_call(rng, D, K, reb_day, ks, n_tables=3):
-    """Arguments of `Device.replay` for len(ks) portfolios of mixed size, cost and scaling, packed densely."""
-    R = len(reb_day)
-    S = rng.normal(0.0005, 0.02, (D, K))
-    S[3:6, 0] = np.nan
-    weights, cols, caps, w_off, u_off, tables = [], [], [], [], [], {}
-    w_len = u_len = 0
-    for p, k in enumerate(ks):
-        key = (k, p % n_tables)
-        if key not in tables:
-            tables[key] = u_len
-            cols.append(_universes(rng, R, k, K).reshape(-1))
-            caps.append(rng.lognormal(3, 1, R * k))
-            u_len += R * k
-        u_off.append(tables[key])
-        w_off.append(w_len)
-        weights.append(rng.normal(0.01, 0.3, R * k))
-        w_len += R * k
-    ks = np.array(ks, dtype=np.int32)
-    return dict(S=S, rf_daily=0.0001 * rng.random(D), reb_day=np.array(reb_day, dtype=np.int32), K=K, k=ks,
-                scaling=rng.choice([1.0, 2.5, 5.0], len(ks)), cost=rng.choice([0.0, 5.0, 15.0, 35.0], len(ks)),
-                w_off=np.array(w_off, dtype=np.int64), w_stride=ks.astype(np.int64),
-                u_off=np.array(u_off, dtype=np.int64), u_stride=ks.astype(np.int64),
-                weights=np.concatenate(weights), cols=np.concatenate(cols), caps=np.concatenate(caps))
-
-
-def _same_bytes(a, b):
-    return all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
 
 
 def test_portfolios_do_not_depend_on_their_launch(dev):
