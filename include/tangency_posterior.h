@@ -665,9 +665,54 @@ int tp_replay_run(tp_handle_t h, int64_t D, int32_t ld, const double* S /* [D x 
                   const int64_t* w_off /* [P] */, const int64_t* w_stride /* [P] */,
                   const int64_t* u_off /* [P] */, const int64_t* u_stride /* [P] */,
                   const double* weights, int64_t weights_len, const int32_t* cols, const double* caps, int64_t universe_len);
+/* tp_replay_run with the weights read where a batch's results already lie on the device: no download, no repacking, no upload
+ * of the weights - only the small inputs go up and tp_replay_download brings the results down.  The daily loop, the merge maps,
+ * the universe tables (cols, caps: HOST pointers, uploaded), the launch classes, the outputs on the handle of `b` and every
+ * argument tp_replay_run also has are tp_replay_run's.  What differs is where a weight row comes from.  `source` names the
+ * results - those of the batch's LAST call of that kind (TP_REPLAY_SRC_RUN: the pair the last tp_batch_run wrote) -, w_off /
+ * w_stride index its weights and s_off / s_stride its statuses, in elements, as the matching download lays them out.  For
+ * portfolio p, rebalancing date j and slot i < k[p]:
+ *   patched - (p, j) is (patch_port[q], patch_date[q]) for some q -: the weight is patch_weights[q patch_ld + i] as it is: no
+ *     scale, no status consulted.  Patches are HOST arrays, sorted by (patch_port, patch_date), strictly increasing; a portfolio
+ *     may have all R dates patched and then never touches the source;
+ *   otherwise: the weight is fl(w_scale[p] * src[w_off[p] + j w_stride[p] + i]) - ONE rounding (what the host forms as
+ *     1.0 / gamma * w when a batch ran with gamma = 1); w_scale == NULL means ones, and a scale of exactly 1.0 leaves the bits
+ *     alone.  The row's status is srcstatus[s_off[p] + j s_stride[p]]: when it is not TP_STATUS_OK, status[p] =
+ *     TP_REPLAY_BAD_WEIGHTS, bad_day[p] = reb_day[j], the portfolio's returns from that day on and its turnover and metrics from
+ *     date j on are NaN and its loop ends - the exit of the sum check, which wins when it trips on the same day (it comes first
+ *     in the day).  A row that is flagged may hold anything, NaN included: it is ordinary data.
+ * The patch lookup costs nothing per day: a wave keeps a cursor into its portfolio's sorted patches and compares once per
+ * rebalancing date.
+ * TP_ERR_INVALID, all checked before anything is uploaded or launched (a refused call leaves the last replay's results in
+ * place): everything tp_replay_run refuses; an unknown source; a source the batch has no results for (no run or sweep of that
+ * kind yet); a w_off / w_stride that runs past the source's weights or an s_off / s_stride that runs past its statuses (R rows
+ * of k[p], R rows of 1: patched dates included; without overflow); n_patch < 0; unsorted or repeated patches; a patch_port
+ * outside [0, P); a patch_date outside [0, R); patch_ld smaller than the k of a patched portfolio; a NULL array that is needed
+ * (w_scale may be NULL; the patch arrays when n_patch == 0).  TP_ERR_UNSUPPORTED, TP_ERR_HIP: as tp_replay_run.
+ * Streams: the call waits on entry for whatever is queued on the handle's stream - this is where the sweep finishes -, uploads
+ * the inputs, queues the launches and does not wait for them; a later run or sweep of the batch is ordered behind them by the
+ * stream, tp_batch_destroy drains it.  The call writes nothing into the batch: every tp_batch_download* returns afterwards the
+ * bytes it returned before.  kernel_ms, tp_region_steps and tp_last_launch: as tp_replay_run. */
+#define TP_REPLAY_SRC_RUN          0  /* tp_batch_run:                 weights [W x k],              status [W]            */
+#define TP_REPLAY_SRC_PRIOR_SWEEP  1  /* tp_batch_prior_sweep[_tiled]:  [W x P x k],                  [W x P]               */
+#define TP_REPLAY_SRC_SIZE_SWEEP   2  /* tp_batch_size_sweep[_tiled]:   [W x P x S x k],              [W x P x S]           */
+#define TP_REPLAY_SRC_WINDOW_SWEEP 3  /* tp_batch_window_sweep[_tiled]: [W x P x L x k],              [W x P x L]           */
+#define TP_REPLAY_SRC_GRID_SWEEP   4  /* tp_batch_grid_sweep[_tiled]:   [W x P x L x S x k],          [W x P x L x S]       */
+#define TP_REPLAY_BAD_WEIGHTS 2       /* status[p]: a weight row was read whose source status was not TP_STATUS_OK */
+int tp_replay_run_batch(tp_batch_t b, int source,
+                        int64_t D, int32_t ld, const double* S, const double* rf_daily,
+                        int64_t R, const int32_t* reb_day, int32_t K,
+                        int64_t P, const int32_t* k, const double* scaling, const double* cost,
+                        const double* w_scale /* [P] or NULL: ones */,
+                        const int64_t* w_off, const int64_t* w_stride,   /* into the SOURCE's weights on the device */
+                        const int64_t* s_off, const int64_t* s_stride,   /* into the SOURCE's statuses on the device */
+                        const int64_t* u_off, const int64_t* u_stride,
+                        const int32_t* cols, const double* caps, int64_t universe_len,
+                        int64_t n_patch, const int64_t* patch_port /* [n_patch] */, const int32_t* patch_date /* [n_patch] */,
+                        const double* patch_weights /* [n_patch x patch_ld] */, int32_t patch_ld);
 /* Waits for the replay and copies out returns [P x D] (returns[p][0] is NaN), turnover [P x R] (turnover[p][0] is NaN), metrics
- * [P x R x 5], status [P] (0 or TP_REPLAY_SUM_CHECK) and bad_day [P] (-1 without a status); each may be NULL.  Without a
- * tp_replay_run before it: TP_ERR_INVALID. */
+ * [P x R x 5], status [P] (0, TP_REPLAY_SUM_CHECK or - tp_replay_run_batch - TP_REPLAY_BAD_WEIGHTS) and bad_day [P] (-1 without
+ * a status); each may be NULL.  Without a tp_replay_run or tp_replay_run_batch before it: TP_ERR_INVALID. */
 int tp_replay_download(tp_handle_t h, double* returns, double* turnover, double* metrics, int32_t* status, int32_t* bad_day);
 
 int tp_synchronize(tp_handle_t h);

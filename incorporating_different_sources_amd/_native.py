@@ -34,8 +34,11 @@ FLAG_NO_CENTER = 2
 FLAG_NO_SHARED_GRAM = 4
 UNIQUE_ID_BYTES = 128
 SWEEP_MAX_RHS = 16
+ERR_INVALID = -1
 REPLAY_SUM_CHECK = 1
+REPLAY_BAD_WEIGHTS = 2
 REPLAY_METRICS = 5
+REPLAY_SRC_RUN, REPLAY_SRC_PRIOR_SWEEP, REPLAY_SRC_SIZE_SWEEP, REPLAY_SRC_WINDOW_SWEEP, REPLAY_SRC_GRID_SWEEP = 0, 1, 2, 3, 4
 
 # every symbol include/tangency_posterior.h declares (checked by tests/test_cabi_symbols.py)
 EXPORTS = [
@@ -52,7 +55,7 @@ EXPORTS = [
     "tp_batch_size_sweep", "tp_batch_size_sweep_tiled", "tp_batch_download_size_sweep",
     "tp_batch_window_sweep", "tp_batch_window_sweep_tiled", "tp_batch_download_window_sweep",
     "tp_batch_grid_sweep", "tp_batch_grid_sweep_tiled", "tp_batch_download_grid_sweep",
-    "tp_replay_merge_maps", "tp_replay_run", "tp_replay_download",
+    "tp_replay_merge_maps", "tp_replay_run", "tp_replay_run_batch", "tp_replay_download",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
     "tp_comm_count", "tp_comm_init_all", "tp_group_gather",
@@ -150,6 +153,11 @@ def _load():
                                   c_int32, c_int64, POINTER(c_int32), POINTER(c_double), POINTER(c_double),
                                   POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
                                   POINTER(c_double), c_int64, POINTER(c_int32), POINTER(c_double), c_int64]
+    lib.tp_replay_run_batch.argtypes = [c_void_p, c_int, c_int64, c_int32, POINTER(c_double), POINTER(c_double), c_int64,
+                                        POINTER(c_int32), c_int32, c_int64, POINTER(c_int32), POINTER(c_double), POINTER(c_double),
+                                        POINTER(c_double), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
+                                        POINTER(c_int64), POINTER(c_int64), POINTER(c_int32), POINTER(c_double), c_int64,
+                                        c_int64, POINTER(c_int64), POINTER(c_int32), POINTER(c_double), c_int32]
     lib.tp_replay_download.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32),
                                        POINTER(c_int32)]
     lib.tp_synchronize.argtypes = [c_void_p]
@@ -240,6 +248,71 @@ _live_devices: "weakref.WeakSet" = weakref.WeakSet()
 _live_pinned: "weakref.WeakSet" = weakref.WeakSet()
 _live_lock = threading.Lock()
 _closed_for_exit = False
+
+
+def _replay_real(name, a, ndim=None):
+    if a is None or np.asarray(a).dtype.kind not in "fiu":
+        raise ValueError(f"{name}: a real floating-point array is expected, got dtype {np.asarray(a).dtype}")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if ndim is not None and a.ndim != ndim:
+        raise ValueError(f"{name}: a {ndim}-D array is expected, got shape {tuple(a.shape)}")
+    return a
+
+
+def _replay_integer(name, a, dtype, shape=None):
+    if a is None or np.asarray(a).dtype.kind not in "iu":
+        raise ValueError(f"{name}: an integer array is expected")
+    wide = np.asarray(a)
+    if wide.size and (wide.min() < np.iinfo(dtype).min or wide.max() > np.iinfo(dtype).max):
+        raise ValueError(f"{name}: an entry does not fit {np.dtype(dtype).name}")
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if shape is not None and a.shape != shape:
+        raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
+    return a
+
+
+def _replay_schedule(S, rf_daily, reb_day, K, k, scaling, cost):
+    """The checks `Device.replay` and `Batch.replay` share - returns, risk-free rates, rebalancing days, sizes, scalings and
+    costs -: (S, D, ld, K, rf, reb, R, k, P, scaling, cost) as contiguous arrays of the library's types."""
+    S = _replay_real("S", S, 2)
+    D, ld = S.shape
+    if D < 1 or ld < 1:
+        raise ValueError(f"S: at least one day and one column expected, got shape {tuple(S.shape)}")
+    K = int(K)
+    if not 1 <= K <= ld:
+        raise ValueError(f"K={K}: within [1, {ld}] (the columns of S) expected")
+    rf = _replay_real("rf_daily", rf_daily)
+    if rf.shape != (D,):
+        raise ValueError(f"rf_daily: expected shape ({D},), got {tuple(rf.shape)}")
+    reb = _replay_integer("reb_day", reb_day, np.int32)
+    if reb.ndim != 1 or reb.size < 1:
+        raise ValueError(f"reb_day: a 1-D array of at least one day is expected, got shape {tuple(reb.shape)}")
+    if reb[0] != 0:
+        raise ValueError(f"reb_day[0]={int(reb[0])}: the first trading day rebalances")
+    if (np.diff(reb) <= 0).any() or reb[-1] >= D:
+        raise ValueError(f"reb_day: strictly increasing below D={D} expected")
+    R = int(reb.size)
+    kk = _replay_integer("k", k, np.int32)
+    if kk.ndim != 1:
+        raise ValueError(f"k: a 1-D array is expected, got shape {tuple(kk.shape)}")
+    P = int(kk.size)
+    if P and kk.min() < 1:
+        raise ValueError("k: every portfolio holds at least one asset")
+    if P and kk.max() > max_assets():
+        raise ValueError(f"k={int(kk.max())} exceeds the largest supported universe {max_assets()}")
+    sc, co = _replay_real("scaling", scaling), _replay_real("cost", cost)
+    for name, a in (("scaling", sc), ("cost", co)):
+        if a.shape != (P,):
+            raise ValueError(f"{name}: expected shape ({P},), got {tuple(a.shape)}")
+    return S, D, ld, K, rf, reb, R, kk, P, sc, co
+
+
+def _replay_rows_fit(name, off, stride, R, kk, n):
+    for p in range(kk.size):
+        o, s = int(off[p]), int(stride[p])          # (Python integers: no overflow)
+        if o < 0 or s < 0 or o + (R - 1) * s + int(kk[p]) > n:
+            raise ValueError(f"{name}_off[{p}]={o}, {name}_stride[{p}]={s}: {R} rows of {int(kk[p])} run past the buffer's "
+                             f"{n} elements")
 
 
 def _finalizing() -> bool:
@@ -468,79 +541,32 @@ class Device:
         check is made before any device call.  Returns (returns [P, D], turnover [P, R], metrics [P, R, 5], status [P],
         bad_day [P]); returns[:, 0] and turnover[:, 0] are NaN; status REPLAY_SUM_CHECK: the weights of that portfolio stopped
         summing to 1 on day bad_day (the host replay raises there)."""
-        def real(name, a, ndim=None):
-            if a is None or np.asarray(a).dtype.kind not in "fiu":
-                raise ValueError(f"{name}: a real floating-point array is expected, got dtype {np.asarray(a).dtype}")
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if ndim is not None and a.ndim != ndim:
-                raise ValueError(f"{name}: a {ndim}-D array is expected, got shape {tuple(a.shape)}")
-            return a
-
-        def integer(name, a, dtype, shape=None):
-            if a is None or np.asarray(a).dtype.kind not in "iu":
-                raise ValueError(f"{name}: an integer array is expected")
-            wide = np.asarray(a)
-            if wide.size and (wide.min() < np.iinfo(dtype).min or wide.max() > np.iinfo(dtype).max):
-                raise ValueError(f"{name}: an entry does not fit {np.dtype(dtype).name}")
-            a = np.ascontiguousarray(a, dtype=dtype)
-            if shape is not None and a.shape != shape:
-                raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
-            return a
-
-        S = real("S", S, 2)
-        D, ld = S.shape
-        if D < 1 or ld < 1:
-            raise ValueError(f"S: at least one day and one column expected, got shape {tuple(S.shape)}")
-        K = int(K)
-        if not 1 <= K <= ld:
-            raise ValueError(f"K={K}: within [1, {ld}] (the columns of S) expected")
-        rf = real("rf_daily", rf_daily)
-        if rf.shape != (D,):
-            raise ValueError(f"rf_daily: expected shape ({D},), got {tuple(rf.shape)}")
-        reb = integer("reb_day", reb_day, np.int32)
-        if reb.ndim != 1 or reb.size < 1:
-            raise ValueError(f"reb_day: a 1-D array of at least one day is expected, got shape {tuple(reb.shape)}")
-        if reb[0] != 0:
-            raise ValueError(f"reb_day[0]={int(reb[0])}: the first trading day rebalances")
-        if (np.diff(reb) <= 0).any() or reb[-1] >= D:
-            raise ValueError(f"reb_day: strictly increasing below D={D} expected")
-        R = int(reb.size)
-        kk = integer("k", k, np.int32)
-        if kk.ndim != 1:
-            raise ValueError(f"k: a 1-D array is expected, got shape {tuple(kk.shape)}")
-        P = int(kk.size)
-        if P and kk.min() < 1:
-            raise ValueError("k: every portfolio holds at least one asset")
-        if P and kk.max() > max_assets():
-            raise ValueError(f"k={int(kk.max())} exceeds the largest supported universe {max_assets()}")
-        sc, co = real("scaling", scaling), real("cost", cost)
-        for name, a in (("scaling", sc), ("cost", co)):
-            if a.shape != (P,):
-                raise ValueError(f"{name}: expected shape ({P},), got {tuple(a.shape)}")
-        wo, wst, uo, ust = (integer(name, a, np.int64, (P,)) for name, a in
+        S, D, ld, K, rf, reb, R, kk, P, sc, co = _replay_schedule(S, rf_daily, reb_day, K, k, scaling, cost)
+        wo, wst, uo, ust = (_replay_integer(name, a, np.int64, (P,)) for name, a in
                             (("w_off", w_off), ("w_stride", w_stride), ("u_off", u_off), ("u_stride", u_stride)))
-        wts = real("weights", weights).reshape(-1)
-        cl = integer("cols", cols, np.int32).reshape(-1)
-        cp = real("caps", caps).reshape(-1)
+        wts = _replay_real("weights", weights).reshape(-1)
+        cl = _replay_integer("cols", cols, np.int32).reshape(-1)
+        cp = _replay_real("caps", caps).reshape(-1)
         if cl.size != cp.size:
             raise ValueError(f"cols and caps: one shape expected, got {cl.size} and {cp.size} elements")
-        for name, off, stride, n in (("w", wo, wst, wts.size), ("u", uo, ust, cl.size)):
-            for p in range(P):
-                o, s = int(off[p]), int(stride[p])          # (Python integers: no overflow)
-                if o < 0 or s < 0 or o + (R - 1) * s + int(kk[p]) > n:
-                    raise ValueError(f"{name}_off[{p}]={o}, {name}_stride[{p}]={s}: {R} rows of {int(kk[p])} run past the buffer's "
-                                     f"{n} elements")
+        _replay_rows_fit("w", wo, wst, R, kk, wts.size)
+        _replay_rows_fit("u", uo, ust, R, kk, cl.size)
         # (the column indices themselves are checked by the library, on the host, while it builds the merge maps)
+        nz = lambda a, ct: _ptr(a if a.size else None, ct)   # noqa: E731
+        self._check(lib.tp_replay_run(self._h, D, ld, _ptr(S, c_double), _ptr(rf, c_double), R, _ptr(reb, c_int32), K, P,
+                                      nz(kk, c_int32), nz(sc, c_double), nz(co, c_double), nz(wo, c_int64), nz(wst, c_int64),
+                                      nz(uo, c_int64), nz(ust, c_int64), nz(wts, c_double), wts.size, nz(cl, c_int32),
+                                      nz(cp, c_double), cl.size))
+        return self._replay_download(P, D, R)
+
+    def _replay_download(self, P, D, R):
+        """`tp_replay_download`: the results of the last replay on this handle (`replay`, `Batch.replay`)."""
         returns = np.empty((P, D), dtype=np.float64)
         turnover = np.empty((P, R), dtype=np.float64)
         metrics = np.empty((P, R, REPLAY_METRICS), dtype=np.float64)
         status = np.empty(P, dtype=np.int32)
         bad_day = np.empty(P, dtype=np.int32)
         nz = lambda a, ct: _ptr(a if a.size else None, ct)   # noqa: E731
-        self._check(lib.tp_replay_run(self._h, D, ld, _ptr(S, c_double), _ptr(rf, c_double), R, _ptr(reb, c_int32), K, P,
-                                      nz(kk, c_int32), nz(sc, c_double), nz(co, c_double), nz(wo, c_int64), nz(wst, c_int64),
-                                      nz(uo, c_int64), nz(ust, c_int64), nz(wts, c_double), wts.size, nz(cl, c_int32),
-                                      nz(cp, c_double), cl.size))
         self._check(lib.tp_replay_download(self._h, nz(returns, c_double), nz(turnover, c_double), nz(metrics, c_double),
                                            nz(status, c_int32), nz(bad_day, c_int32)))
         return returns, turnover, metrics, status, bad_day
@@ -766,19 +792,21 @@ class Batch:
         self.dev._check(lib.tp_batch_download_sweep_rhs(self._b, _ptr(out if out.size else None, c_double)))
         return out
 
-    def prior_sweep(self, n0, w0, want_aux=True):
+    def prior_sweep(self, n0, w0, want_aux=True, want_weights=True):
         """`tp_batch_prior_sweep` + `tp_batch_download_prior_sweep`: the conjugate weights of every window for P priors
         `n0` [W x P] (> 0), `w0` [W x P x k] from ONE pair of Grams per window.  Returns (weights [W, P, k], status [W, P],
-        aux [W, P, 8] or None).  The batch's own w0 / n0, results, settings and kept arrays are left alone."""
-        return self._prior_sweep(lib.tp_batch_prior_sweep, n0, w0, want_aux)
+        aux [W, P, 8] or None).  The batch's own w0 / n0, results, settings and kept arrays are left alone.
+        `want_weights=False` (every sweep method): the weights stay on the device - for `replay` - and None is returned in
+        their place."""
+        return self._prior_sweep(lib.tp_batch_prior_sweep, n0, w0, want_aux, want_weights)
 
-    def prior_sweep_tiled(self, n0, w0, want_aux=True):
+    def prior_sweep_tiled(self, n0, w0, want_aux=True, want_weights=True):
         """`tp_batch_prior_sweep_tiled` + `tp_batch_download_prior_sweep`: `prior_sweep` for k above `sweep_max_assets()`,
         factorised by the large-k tiled pipeline (smaller k: TP_ERR_UNSUPPORTED).  The intraday scatter is centred through
         the raw moments: meant for returns, not for panels with a large common offset."""
-        return self._prior_sweep(lib.tp_batch_prior_sweep_tiled, n0, w0, want_aux)
+        return self._prior_sweep(lib.tp_batch_prior_sweep_tiled, n0, w0, want_aux, want_weights)
 
-    def _prior_sweep(self, call, n0, w0, want_aux):
+    def _prior_sweep(self, call, n0, w0, want_aux, want_weights=True):
         W, k = self.W, self.k
         for name, a in (("n0", n0), ("w0", w0)):
             if a is None:
@@ -792,35 +820,35 @@ class Batch:
         P = n0.shape[1]
         if w0.shape != (W, P, k):
             raise ValueError(f"w0: expected shape ({W}, {P}, {k}), got {tuple(w0.shape)}")
-        weights = np.empty((W, P, k), dtype=np.float64)
+        weights = np.empty((W, P, k), dtype=np.float64) if want_weights else None
         status = np.empty((W, P), dtype=np.int32)
         aux = np.empty((W, P, AUX_STRIDE), dtype=np.float64) if want_aux else None
         # (W = 0: the library still wants non-NULL prior arrays)
         n0p = n0 if n0.size else np.ones(1)
         w0p = w0 if w0.size else np.zeros(1)
         self.dev._check(call(self._b, P, _ptr(n0p, c_double), _ptr(w0p, c_double)))
-        self.dev._check(lib.tp_batch_download_prior_sweep(self._b, _ptr(weights if weights.size else None, c_double),
+        self.dev._check(lib.tp_batch_download_prior_sweep(self._b, _ptr(weights if weights is not None and weights.size else None, c_double),
                                                           _ptr(status if status.size else None, c_int32),
                                                           _ptr(aux if aux is not None and aux.size else None, c_double)))
         return weights, status, aux
 
-    def size_sweep(self, sizes, n0=None, w0=None, want_aux=True):
+    def size_sweep(self, sizes, n0=None, w0=None, want_aux=True, want_weights=True):
         """`tp_batch_size_sweep` + `tp_batch_download_size_sweep`: S nested universes per window - the first `sizes[s]`
         columns, strictly increasing within [1, k], at most SWEEP_MAX_RHS of them - from ONE factorisation per (window,
         prior).  Conjugate batch: `n0` [W x P] (> 0), `w0` [W x P x S x k] (only the first sizes[s] entries of a vector are
         read).  Jeffreys batch: no priors, P = 1.  Returns (weights [W, P, S, k] - zero beyond sizes[s] -, status [W, P, S],
         aux [W, P, S, 8] or None).  The batch's results, settings and kept arrays are left alone."""
-        return self._size_sweep(lib.tp_batch_size_sweep, sizes, n0, w0, want_aux)
+        return self._size_sweep(lib.tp_batch_size_sweep, sizes, n0, w0, want_aux, want_weights)
 
-    def size_sweep_tiled(self, sizes, n0=None, w0=None, want_aux=True):
+    def size_sweep_tiled(self, sizes, n0=None, w0=None, want_aux=True, want_weights=True):
         """`tp_batch_size_sweep_tiled` + `tp_batch_download_size_sweep`: `size_sweep` for k above `sweep_max_assets()`, every
         (window, prior) factorised once at k by the large-k tiled pipeline with the S right-hand sides riding along as
         columns k .. k+S-1 of the arena (smaller k, or k + S > max_assets() + 1: TP_ERR_UNSUPPORTED).  Same arguments, shape
         checks and return values; single sizes may lie below `sweep_max_assets()`.  A non-finite column j also spoils the
         sizes in (64 floor(j/64), j], which come back flagged; the intraday scatter is centred through the raw moments."""
-        return self._size_sweep(lib.tp_batch_size_sweep_tiled, sizes, n0, w0, want_aux)
+        return self._size_sweep(lib.tp_batch_size_sweep_tiled, sizes, n0, w0, want_aux, want_weights)
 
-    def _size_sweep(self, call, sizes, n0, w0, want_aux):
+    def _size_sweep(self, call, sizes, n0, w0, want_aux, want_weights=True):
         W, k = self.W, self.k
         if sizes is None or np.asarray(sizes).dtype.kind not in "iu":
             raise ValueError("sizes: a sequence of integers is expected")
@@ -844,7 +872,7 @@ class Batch:
             P = n0.shape[1]
             if w0.shape != (W, P, S, k):
                 raise ValueError(f"w0: expected shape ({W}, {P}, {S}, {k}), got {tuple(w0.shape)}")
-        weights = np.empty((W, P, S, k), dtype=np.float64)
+        weights = np.empty((W, P, S, k), dtype=np.float64) if want_weights else None
         status = np.empty((W, P, S), dtype=np.int32)
         aux = np.empty((W, P, S, AUX_STRIDE), dtype=np.float64) if want_aux else None
         if n0 is None:
@@ -854,21 +882,21 @@ class Batch:
             n0p = n0 if n0.size else np.ones(1)
             w0p = w0 if w0.size else np.zeros(1)
             self.dev._check(call(self._b, S, _ptr(sz, c_int32), P, _ptr(n0p, c_double), _ptr(w0p, c_double)))
-        self.dev._check(lib.tp_batch_download_size_sweep(self._b, _ptr(weights if weights.size else None, c_double),
+        self.dev._check(lib.tp_batch_download_size_sweep(self._b, _ptr(weights if weights is not None and weights.size else None, c_double),
                                                          _ptr(status if status.size else None, c_int32),
                                                          _ptr(aux if aux is not None and aux.size else None, c_double)))
         return weights, status, aux
 
-    def window_sweep(self, N, rows, n0=None, w0=None, delta=None, want_aux=True):
-        return self._window_sweep(lib.tp_batch_window_sweep, N, rows, n0, w0, delta, want_aux)
+    def window_sweep(self, N, rows, n0=None, w0=None, delta=None, want_aux=True, want_weights=True):
+        return self._window_sweep(lib.tp_batch_window_sweep, N, rows, n0, w0, delta, want_aux, want_weights)
 
-    def window_sweep_tiled(self, N, rows, n0=None, w0=None, delta=None, want_aux=True):
+    def window_sweep_tiled(self, N, rows, n0=None, w0=None, delta=None, want_aux=True, want_weights=True):
         """`tp_batch_window_sweep_tiled` + `tp_batch_download_window_sweep`: `window_sweep` for k > `sweep_max_assets()`, on the
         large-k tiled pipeline - the same arguments, checks (before any device call) and results; statuses as `run` gives
         them on the large-k path."""
-        return self._window_sweep(lib.tp_batch_window_sweep_tiled, N, rows, n0, w0, delta, want_aux)
+        return self._window_sweep(lib.tp_batch_window_sweep_tiled, N, rows, n0, w0, delta, want_aux, want_weights)
 
-    def _window_sweep(self, call, N, rows, n0, w0, delta, want_aux):
+    def _window_sweep(self, call, N, rows, n0, w0, delta, want_aux, want_weights=True):
         """`tp_batch_window_sweep` + `tp_batch_download_window_sweep`: L nested window lengths per window - length l uses the
         last `rows[w, l]` daily rows of the window as uploaded - from ONE pass over the rows.  `N` [L]: strictly increasing,
         replaces the batch's N per length; `rows` [W x L]: non-decreasing in l within [1, n_w]; `delta` [W x L x n_r] or None:
@@ -908,7 +936,7 @@ class Batch:
             P = n0.shape[1]
             if w0.shape != (W, P, k):
                 raise ValueError(f"w0: expected shape ({W}, {P}, {k}), got {tuple(w0.shape)}")
-        weights = np.empty((W, P, L, k), dtype=np.float64)
+        weights = np.empty((W, P, L, k), dtype=np.float64) if want_weights else None
         status = np.empty((W, P, L), dtype=np.int32)
         aux = np.empty((W, P, L, AUX_STRIDE), dtype=np.float64) if want_aux else None
         # (W = 0: the library still wants non-NULL arrays)
@@ -921,28 +949,29 @@ class Batch:
             w0p = w0 if w0.size else np.zeros(1)
             self.dev._check(call(self._b, L, _ptr(Nl, c_int32), _ptr(rwp, c_int32), _ptr(dp, c_double), P, _ptr(n0p, c_double),
                                  _ptr(w0p, c_double)))
-        self.dev._check(lib.tp_batch_download_window_sweep(self._b, _ptr(weights if weights.size else None, c_double),
+        self.dev._check(lib.tp_batch_download_window_sweep(self._b, _ptr(weights if weights is not None and weights.size else None, c_double),
                                                            _ptr(status if status.size else None, c_int32),
                                                            _ptr(aux if aux is not None and aux.size else None, c_double)))
         return weights, status, aux
 
-    def grid_sweep(self, sizes, N, rows, n0=None, w0=None, delta=None, want_aux=True):
-        return self._grid_sweep(lib.tp_batch_grid_sweep, sizes, N, rows, n0, w0, delta, want_aux)
+    def grid_sweep(self, sizes, N, rows, n0=None, w0=None, delta=None, want_aux=True, want_weights=True):
+        return self._grid_sweep(lib.tp_batch_grid_sweep, sizes, N, rows, n0, w0, delta, want_aux, want_weights)
 
-    def grid_sweep_tiled(self, sizes, N, rows, n0=None, w0=None, delta=None, want_aux=True):
+    def grid_sweep_tiled(self, sizes, N, rows, n0=None, w0=None, delta=None, want_aux=True, want_weights=True):
         """`tp_batch_grid_sweep_tiled` + `tp_batch_download_grid_sweep`: `grid_sweep` for k > `sweep_max_assets()`, on the
         large-k tiled pipeline - the same arguments, checks (before any device call) and results; single sizes may lie below
         that bound.  k + len(sizes) <= `max_assets()` + 1."""
-        return self._grid_sweep(lib.tp_batch_grid_sweep_tiled, sizes, N, rows, n0, w0, delta, want_aux)
+        return self._grid_sweep(lib.tp_batch_grid_sweep_tiled, sizes, N, rows, n0, w0, delta, want_aux, want_weights)
 
-    def _grid_sweep(self, call, sizes, N, rows, n0, w0, delta, want_aux):
+    def _grid_sweep(self, call, sizes, N, rows, n0, w0, delta, want_aux, want_weights=True):
         """`tp_batch_grid_sweep` + `tp_batch_download_grid_sweep`: S nested universes x L nested window lengths per window -
         entry (l, s) uses the first `sizes[s]` columns and the last `rows[w, l]` daily rows of the window as uploaded - from ONE
         pass over the rows and ONE factorisation per (window, prior, length).  `sizes` as in `size_sweep`; `N`, `rows` and
         `delta` as in `window_sweep`.  Conjugate batch: `n0` [W x P x L] (> 0), `w0` [W x P x S x k] (only the first sizes[s]
         entries of a vector are read).  Jeffreys batch: no priors, P = 1.  Returns (weights [W, P, L, S, k] - zero beyond
-        sizes[s] -, status [W, P, L, S], aux [W, P, L, S, 8] or None).  The batch's results, settings and kept arrays and the
-        other sweeps' results are left alone."""
+        sizes[s] -, status [W, P, L, S], aux [W, P, L, S, 8] or None; `want_weights=False`: None for the weights, which stay
+        on the device for `replay`).  The batch's results, settings and kept arrays and the other sweeps' results are left
+        alone."""
         W, k = self.W, self.k
         if sizes is None or np.asarray(sizes).dtype.kind not in "iu":
             raise ValueError("sizes: a sequence of integers is expected")
@@ -983,7 +1012,7 @@ class Batch:
             P = n0.shape[1]
             if w0.shape != (W, P, S, k):
                 raise ValueError(f"w0: expected shape ({W}, {P}, {S}, {k}), got {tuple(w0.shape)}")
-        weights = np.empty((W, P, L, S, k), dtype=np.float64)
+        weights = np.empty((W, P, L, S, k), dtype=np.float64) if want_weights else None
         status = np.empty((W, P, L, S), dtype=np.int32)
         aux = np.empty((W, P, L, S, AUX_STRIDE), dtype=np.float64) if want_aux else None
         # (W = 0: the library still wants non-NULL arrays)
@@ -997,10 +1026,59 @@ class Batch:
             w0p = w0 if w0.size else np.zeros(1)
             self.dev._check(call(self._b, S, _ptr(sz, c_int32), L, _ptr(Nl, c_int32), _ptr(rwp, c_int32), _ptr(dp, c_double), P,
                                  _ptr(n0p, c_double), _ptr(w0p, c_double)))
-        self.dev._check(lib.tp_batch_download_grid_sweep(self._b, _ptr(weights if weights.size else None, c_double),
+        self.dev._check(lib.tp_batch_download_grid_sweep(self._b, _ptr(weights if weights is not None and weights.size else None, c_double),
                                                          _ptr(status if status.size else None, c_int32),
                                                          _ptr(aux if aux is not None and aux.size else None, c_double)))
         return weights, status, aux
+
+    def replay(self, source, S, rf_daily, reb_day, K, k, scaling, cost, w_off, w_stride, s_off, s_stride, u_off, u_stride,
+               cols, caps, w_scale=None, patches=None):
+        """`tp_replay_run_batch` + `tp_replay_download`: `Device.replay` with the weights read where this batch's last run or
+        sweep of kind `source` (REPLAY_SRC_*) left them on the device - nothing but the small inputs goes up, nothing but the
+        results comes down.  At rebalancing date j portfolio p holds `w_scale[p] * src[w_off[p] + j * w_stride[p] + i]`
+        (`w_scale` [P] or None: ones; one rounding, 1.0 leaves the bits alone) and the row's status is
+        `srcstatus[s_off[p] + j * s_stride[p]]`, both in elements of the source's results as its download returns them
+        (the sweeps' methods take `want_weights=False`).  `patches` = (port [n], date [n], rows [n x patch_ld]) or None: date
+        `date[q]` of portfolio `port[q]` holds `rows[q, :k]` instead, unscaled and whatever the source's status; sorted by
+        (port, date), strictly.  The other arguments and the returns are `Device.replay`'s; status REPLAY_BAD_WEIGHTS: a row
+        was read whose source status was not STATUS_OK, at rebalancing day bad_day (NaN from there on).  Shapes and types are
+        checked here, before any device call; the library checks the source, the offsets against the source's counts and the
+        patches' order before it uploads or launches anything (TangencyError, code ERR_INVALID)."""
+        source = int(source)
+        S, D, ld, K, rf, reb, R, kk, P, sc, co = _replay_schedule(S, rf_daily, reb_day, K, k, scaling, cost)
+        wo, wst, so, sst, uo, ust = (_replay_integer(name, a, np.int64, (P,)) for name, a in
+                                     (("w_off", w_off), ("w_stride", w_stride), ("s_off", s_off), ("s_stride", s_stride),
+                                      ("u_off", u_off), ("u_stride", u_stride)))
+        cl = _replay_integer("cols", cols, np.int32).reshape(-1)
+        cp = _replay_real("caps", caps).reshape(-1)
+        if cl.size != cp.size:
+            raise ValueError(f"cols and caps: one shape expected, got {cl.size} and {cp.size} elements")
+        _replay_rows_fit("u", uo, ust, R, kk, cl.size)
+        ws = None
+        if w_scale is not None:
+            ws = _replay_real("w_scale", w_scale)
+            if ws.shape != (P,):
+                raise ValueError(f"w_scale: expected shape ({P},), got {tuple(ws.shape)}")
+        n_patch, pp, pd_, pr, patch_ld = 0, None, None, None, 0
+        if patches is not None:
+            if len(patches) != 3:
+                raise ValueError("patches: (port, date, rows) expected")
+            pp = _replay_integer("patches[0]", patches[0], np.int64)
+            pd_ = _replay_integer("patches[1]", patches[1], np.int32)
+            pr = _replay_real("patches[2]", patches[2], 2)
+            n_patch = int(pp.size)
+            if pp.ndim != 1 or pd_.shape != (n_patch,) or pr.shape[0] != n_patch:
+                raise ValueError(f"patches: port [n], date [n] and rows [n x ld] expected, got {tuple(pp.shape)}, "
+                                 f"{tuple(pd_.shape)}, {tuple(pr.shape)}")
+            patch_ld = int(pr.shape[1])
+        nz = lambda a, ct: _ptr(a if a is not None and a.size else None, ct)   # noqa: E731
+        dev = self.dev
+        dev._check(lib.tp_replay_run_batch(self._b, source, D, ld, _ptr(S, c_double), _ptr(rf, c_double), R, _ptr(reb, c_int32),
+                                           K, P, nz(kk, c_int32), nz(sc, c_double), nz(co, c_double), nz(ws, c_double),
+                                           nz(wo, c_int64), nz(wst, c_int64), nz(so, c_int64), nz(sst, c_int64),
+                                           nz(uo, c_int64), nz(ust, c_int64), nz(cl, c_int32), nz(cp, c_double), cl.size,
+                                           n_patch, nz(pp, c_int64), nz(pd_, c_int32), nz(pr, c_double), patch_ld))
+        return dev._replay_download(P, D, R)
 
     def download(self, want_aux=True, out=None):
         """(weights, status, aux).  `out=(weights, status[, aux])`: write into these arrays (e.g. `pinned_empty`)."""

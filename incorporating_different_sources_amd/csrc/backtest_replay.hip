@@ -14,6 +14,13 @@
 // Loads.  The returns of day d+1 (and rf[d+1]) do not depend on the weights: they are requested at the top of day d, ahead of
 // its reductions (the universe of the NEXT rebalancing date is kept in registers one rebalance ahead, so this also holds on a
 // rebalancing day); up to 8 slots per lane the rebalancing inputs are requested there too.
+//
+// Two forms, chosen at compile time.  FED = false: the weights are the caller's, uploaded (tp_replay_run).  FED = true: they
+// lie where a batch's run or sweep wrote them (tp_replay_run_batch): a row is scaled by the portfolio's w_scale and carries the
+// status of its source entry, or it is replaced by a patch row.  The patches of a portfolio are sorted by date and the dates of
+// the loop rise, so the wave keeps a cursor into them and the next patched date as wave-uniform scalars and compares once per
+// rebalancing date: no search, and the row pointer, the scale and the status are selected, not branched on - the control flow
+// around the reductions stays wave-uniform.
 #include "backtest_replay.h"
 #include "posterior_device_prims.h"
 
@@ -66,7 +73,16 @@ __device__ __forceinline__ double wave_min(double v) {
 __device__ __forceinline__ bool is_nan(double x) { return x != x; }
 __device__ __forceinline__ double nan_to_zero(double x) { return x != x ? 0.0 : x; }
 
-template <int SPL>
+// a value every lane holds alike, for the scalar unit
+__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ long long uniform(long long x) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)x & 0xffffffffull));
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)x >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double uniform(double x) { return __longlong_as_double(uniform(__double_as_longlong(x))); }
+
+template <int SPL, bool FED>
 __global__ __launch_bounds__(64 * TP_REPLAY_WAVES) void replay_kernel(const tp_replay_args_t a) {
     __shared__ double lds_all[TP_REPLAY_WAVES][SPL * 64];
     constexpr bool EARLY = SPL <= 8;          // rebalancing inputs requested ahead of the day's reductions
@@ -89,6 +105,32 @@ __global__ __launch_bounds__(64 * TP_REPLAY_WAVES) void replay_kernel(const tp_r
     const double nan = __builtin_nan("");
     const double inf = __builtin_inf();
     const double cost_frac = pt.cost / 10000.0;
+
+    // FED: the cursor into the portfolio's patches [pq, pend) and the rebalancing date of the patch under it (R: none left)
+    int pq = 0, pend = 0, pnext = 0;
+    long long src_off = 0, src_stride = 0, st_off = 0, st_stride = 0;
+    double w_scale = 1.0;
+    if (FED) {
+        pq = uniform(pt.patch_first);
+        pend = uniform(pt.patch_end);
+        pnext = pq < pend ? uniform(a.patch_date[pq]) : a.R;
+        src_off = uniform(pt.w_off); src_stride = uniform(pt.w_stride);
+        st_off = uniform(pt.s_off); st_stride = uniform(pt.s_stride);
+        w_scale = uniform(pt.w_scale);
+    }
+    // the row of rebalancing date j, the factor on it (raw: none) and whether its source entry is flagged
+    const double* wrow = wts;
+    bool raw = true;
+    int bad = 0;
+    auto resolve = [&](int j) {
+        const bool patched = pnext == j;
+        const double* src_row = a.weights + (src_off + (long long)j * src_stride);
+        const double* patch_row = a.patch_rows + (long long)pq * a.patch_ld;
+        wrow = patched ? patch_row : src_row;
+        raw = patched || w_scale == 1.0;
+        const int st = uniform(a.src_status[st_off + (long long)j * st_stride]);
+        bad = patched ? 0 : st;
+    };
 
     double w[SPL], rn[SPL];
     int col[SPL], cnext[SPL];
@@ -121,11 +163,17 @@ __global__ __launch_bounds__(64 * TP_REPLAY_WAVES) void replay_kernel(const tp_r
 #pragma unroll
         for (int s = 0; s < SPL; ++s) { an[s] = 0.0; cp[s] = 0.0; ps[s] = -1; ns[s] = 0; }
         if (EARLY && reb) {
+            if (FED) resolve(jn);
 #pragma unroll
             for (int s = 0; s < SPL; ++s) {
                 const int i = s * 64 + lane;
                 if (i < k) {
-                    an[s] = wts[(long long)jn * pt.w_stride + i];
+                    if (FED) {
+                        const double x = wrow[i];
+                        an[s] = raw ? x : w_scale * x;
+                    } else {
+                        an[s] = wts[(long long)jn * pt.w_stride + i];
+                    }
                     cp[s] = ucaps[(long long)jn * pt.u_stride + i];
                     if (jn > 0) {
                         ps[s] = prev[(long long)jn * k + i];
@@ -179,12 +227,27 @@ __global__ __launch_bounds__(64 * TP_REPLAY_WAVES) void replay_kernel(const tp_r
         }
 
         if (reb) {
+            if (FED && !EARLY) resolve(jn);
+            if (FED && bad != 0) {                                // the source flagged this row: the exit of the sum check
+                if (lane == 0) { a.status[p] = TP_REPLAY_KSTATUS_BAD_WEIGHTS; a.bad_day[p] = d; }
+                for (int t = d + lane; t < D; t += 64) ret[t] = nan;
+                for (int t = jn + lane; t < R; t += 64) {
+                    turn[t] = nan;
+                    for (int c = 0; c < TP_REPLAY_METRICS; ++c) met[(size_t)t * TP_REPLAY_METRICS + c] = nan;
+                }
+                break;
+            }
             if (!EARLY) {
 #pragma unroll
                 for (int s = 0; s < SPL; ++s) {
                     const int i = s * 64 + lane;
                     if (i < k) {
-                        an[s] = wts[(long long)jn * pt.w_stride + i];
+                        if (FED) {
+                            const double x = wrow[i];
+                            an[s] = raw ? x : w_scale * x;
+                        } else {
+                            an[s] = wts[(long long)jn * pt.w_stride + i];
+                        }
                         if (jn > 0) {
                             ps[s] = prev[(long long)jn * k + i];
                             ns[s] = next[(long long)(jn - 1) * k + i];
@@ -266,6 +329,10 @@ __global__ __launch_bounds__(64 * TP_REPLAY_WAVES) void replay_kernel(const tp_r
                 w[s] = an[s];
                 col[s] = cnext[s];
             }
+            if (FED && pnext == jn) {                             // this date was a patch: on to the portfolio's next one
+                ++pq;
+                pnext = pq < pend ? uniform(a.patch_date[pq]) : R;
+            }
             ++jn;
             reb_next = jn < R ? a.reb_day[jn] : D;
             if (jn < R) {
@@ -283,7 +350,8 @@ __global__ __launch_bounds__(64 * TP_REPLAY_WAVES) void replay_kernel(const tp_r
 template <int SPL>
 hipError_t launch_spl(const tp_replay_args_t& a, hipStream_t st) {
     const int grid = (a.count + TP_REPLAY_WAVES - 1) / TP_REPLAY_WAVES;
-    hipLaunchKernelGGL(replay_kernel<SPL>, dim3(grid), dim3(64 * TP_REPLAY_WAVES), 0, st, a);
+    if (a.src_status) hipLaunchKernelGGL((replay_kernel<SPL, true>), dim3(grid), dim3(64 * TP_REPLAY_WAVES), 0, st, a);
+    else hipLaunchKernelGGL((replay_kernel<SPL, false>), dim3(grid), dim3(64 * TP_REPLAY_WAVES), 0, st, a);
     return hipGetLastError();
 }
 

@@ -685,7 +685,9 @@ int tp_batch_run(tp_batch_t b) {
     }
     tp_kargs_t a = make_kargs(b);
     rc = launch(b, a, b->W, true);
-    return rc != TP_OK ? rc : end_launches(b);
+    if (rc != TP_OK) return rc;
+    b->has_run = true;
+    return end_launches(b);
 }
 
 int tp_synchronize(tp_handle_t h) {

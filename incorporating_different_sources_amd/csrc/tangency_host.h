@@ -24,10 +24,12 @@
 
 #define TP_REGION_MAX_STEPS 512
 
-// Backtest replay (tp_replay_run / tp_replay_download, tangency_replay.cpp): the inputs and results of the last run.  The
-// replay belongs to the handle, not to a batch; plain DevBufs, freed with the handle.
+// Backtest replay (tp_replay_run / tp_replay_run_batch / tp_replay_download, tangency_replay.cpp): the inputs and results of
+// the last run.  The replay belongs to the handle, not to a batch (tp_replay_run_batch reads a batch's results where they lie
+// and keeps no pointer to them); plain DevBufs, freed with the handle.
 struct ReplayWs {
     DevBuf S, rf, reb, weights, cols, caps, prev, next, port, order;
+    DevBuf patch_date, patch_rows;  // tp_replay_run_batch: the patches' dates [n_patch] and rows [n_patch x patch_ld]
     DevBuf ret, turnover, metrics, status, bad_day;
     int64_t P = 0, D = 0, R = 0;    // shape of the last run
     bool ran = false;               // a run completed its launches (tp_replay_download has something to copy)
@@ -161,6 +163,7 @@ struct tp_batch_s {
     DevBuf t_part;                                            // pieces of S0 w0 per (window, row block, column block)
     int64_t tiled_capacity = 0;                               // windows in flight per sub-batch
     bool uploaded = false;
+    bool has_run = false;                            // a tp_batch_run queued its launches: (out_weights, out_status) hold results
     bool gathered = false;
     bool rhs_valid = false;                          // out_rhs was allocated before the last run (tp_batch_keep_rhs)
     bool post_valid = false;                         // post was allocated before the last run (tp_batch_keep_posterior)

@@ -1201,27 +1201,16 @@ def _grid_family(portfolio_spec):
     return tuple(portfolio_spec.get(name) for name in ("rebalancing_frequency", "rolling_window_frequency"))
 
 
-def calculate_weights_for_grid(trading_dates, portfolio_specs_list, market_data):
-    """Weights of specs that differ in `size` AND in `rolling_window` (conjugate specs: also in the prior - vw / ew, VIX / EPU,
-    mcm_scaling) for the same dates with ONE host pack at (largest size, longest window) (`batch.pack_windows_grid`), ONE upload
-    and ONE grid sweep (`Batch.grid_sweep`): every daily row passes the device once, every (date, prior, length) is factorised
-    once at the largest size and each size solved over its prefix.  Conjugate specs only, or Jeffreys specs only, of one
-    (rebalancing frequency, window frequency) family.  (date, size, length) triples the pack cannot serve (its mask), sizes
-    above `_native.sweep_max_assets()`, more than `_native.SWEEP_MAX_RHS` sizes or lengths and a pack that raises go through
-    `_weights_for_dates` spec by spec, so the reference's exceptions surface where the reference raises them - unless
-    GRID_SWEEP_TILED is set: then, when the largest size exceeds that bound (and the sizes and lengths fit one tiled sweep), ALL
-    sizes are packed once at the largest and swept with `Batch.grid_sweep_tiled`.
-    Returns one (weights, labels, cols, caps) per spec, each at its own size - equal to `_weights_for_dates` spec by spec
-    within the solve's rounding - and remembers the conjugate ones in the cache slots `calculate_weights_for_specs` fills.
-    Opt-in: nothing calls it by default."""
-    specs = list(portfolio_specs_list)
-    if not specs:
-        return []
+def _grid_sweep_stage(trading_dates, specs, market_data, want_weights=True, keep_open=False):
+    """The pack-and-sweep stage of `calculate_weights_for_grid` (and of `backtest_portfolios_grid`): the family check, ONE host
+    pack at (largest size, longest window), ONE upload and ONE grid sweep.  Returns (sizes, windows, conj, same_gamma, swept, b):
+    `swept` = (weights, status, labels, cols, caps, mask, prior_keys), or None when no sweep serves the specs (the caller then
+    solves them one by one); `want_weights=False` leaves the weights on the device (None in their place).  `keep_open`: `b` is
+    the batch, still open - its results are on the device and the caller closes it - otherwise None."""
     conj = specs[0]["weighting_strategy"] in _CONJUGATE
     if (any((sp["weighting_strategy"] in _CONJUGATE) != conj or (not conj and sp["weighting_strategy"] != "jeffreys") for sp in specs)
             or len({_grid_family(sp) for sp in specs}) != 1):
         raise ValueError("calculate_weights_for_grid: conjugate specs, or Jeffreys specs, of equal frequencies expected")
-    trading_dates = list(trading_dates)
     n_dates = len(trading_dates)
     members_of = _members_provider(market_data)
     gammas = [sp["risk_aversion"] for sp in specs]
@@ -1238,38 +1227,63 @@ def calculate_weights_for_grid(trading_dates, portfolio_specs_list, market_data)
             packed = batch.pack_windows_grid(trading_dates, specs[0], sizes, windows, market_data, members_of=members_of)
         except (ValueError, AssertionError) as exc:      # the specs decide one by one what the caller sees
             logger.warning(f"grid sweep dropped ({exc}); solving the {len(specs)} specs one by one")
-    swept = None
-    if packed is not None:
-        k = sizes[-1]
-        kw, labels, caps, rows, delta, mask = packed
-        n0 = w0 = None
-        prior_keys = []
-        if conj:
-            prior_of = lambda sp: (sp["weighting_strategy"], sp["mcm_scaling"])
-            prior_keys = list(dict.fromkeys(prior_of(sp) for sp in specs if sp["size"] <= k))
-            n0 = np.empty((n_dates, len(prior_keys), len(windows)))
-            w0 = np.zeros((n_dates, len(prior_keys), len(sizes), k))
-            for p, key in enumerate(prior_keys):
-                sp = next(sp for sp in specs if prior_of(sp) == key)
-                wanted = {int(x["size"]) for x in specs if prior_of(x) == key}
-                for l, N in enumerate(windows):          # n0 reads the length (ref:112, 265), not the size
-                    n0[:, p, l] = batch.prior_inputs(trading_dates, dict(sp, size=k, rolling_window=N), market_data, caps)[1]
-                # w0 over the prefix (ref:692-695 / 670-672) reads the caps alone - neither the length nor the dates: one date is
-                # passed so that the n0 it returns next to it is not computed W times per size
-                for s, ks in enumerate(sizes):
-                    if ks in wanted:
-                        w0[:, p, s, :ks] = batch.prior_inputs(trading_dates[:1], dict(sp, size=ks), market_data, caps[:, :ks])[0]
-                    else:                                # no spec asks for this pair: any finite prior does, its result is not read
-                        w0[:, p, s, :ks] = 1.0 / ks
-        b = _native.Batch(_native.default_device(), "conjugate" if conj else "jeffreys", k, windows[-1], kw["n_r"],
-                          gammas[0] if same_gamma else 1.0, n_dates, kw.get("m") or 0)
-        try:
-            b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m")})
-            weights, status, _ = (b.grid_sweep_tiled if tiled else b.grid_sweep)(
-                sizes, windows, rows, n0, w0, delta=delta if delta.any() else None, want_aux=False)
-        finally:
-            b.close()
-        swept = (weights, status, labels, kw["col_idx"], caps, mask, prior_keys)
+    if packed is None:
+        return sizes, windows, conj, same_gamma, None, None
+    k = sizes[-1]
+    kw, labels, caps, rows, delta, mask = packed
+    n0 = w0 = None
+    prior_keys = []
+    if conj:
+        prior_of = lambda sp: (sp["weighting_strategy"], sp["mcm_scaling"])
+        prior_keys = list(dict.fromkeys(prior_of(sp) for sp in specs if sp["size"] <= k))
+        n0 = np.empty((n_dates, len(prior_keys), len(windows)))
+        w0 = np.zeros((n_dates, len(prior_keys), len(sizes), k))
+        for p, key in enumerate(prior_keys):
+            sp = next(sp for sp in specs if prior_of(sp) == key)
+            wanted = {int(x["size"]) for x in specs if prior_of(x) == key}
+            for l, N in enumerate(windows):          # n0 reads the length (ref:112, 265), not the size
+                n0[:, p, l] = batch.prior_inputs(trading_dates, dict(sp, size=k, rolling_window=N), market_data, caps)[1]
+            # w0 over the prefix (ref:692-695 / 670-672) reads the caps alone - neither the length nor the dates: one date is
+            # passed so that the n0 it returns next to it is not computed W times per size
+            for s, ks in enumerate(sizes):
+                if ks in wanted:
+                    w0[:, p, s, :ks] = batch.prior_inputs(trading_dates[:1], dict(sp, size=ks), market_data, caps[:, :ks])[0]
+                else:                                # no spec asks for this pair: any finite prior does, its result is not read
+                    w0[:, p, s, :ks] = 1.0 / ks
+    b = _native.Batch(_native.default_device(), "conjugate" if conj else "jeffreys", k, windows[-1], kw["n_r"],
+                      gammas[0] if same_gamma else 1.0, n_dates, kw.get("m") or 0)
+    try:
+        b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m")})
+        weights, status, _ = (b.grid_sweep_tiled if tiled else b.grid_sweep)(
+            sizes, windows, rows, n0, w0, delta=delta if delta.any() else None, want_aux=False, want_weights=want_weights)
+    except BaseException:
+        b.close()
+        raise
+    if not keep_open:
+        b.close()
+        b = None
+    return sizes, windows, conj, same_gamma, (weights, status, labels, kw["col_idx"], caps, mask, prior_keys), b
+
+
+def calculate_weights_for_grid(trading_dates, portfolio_specs_list, market_data):
+    """Weights of specs that differ in `size` AND in `rolling_window` (conjugate specs: also in the prior - vw / ew, VIX / EPU,
+    mcm_scaling) for the same dates with ONE host pack at (largest size, longest window) (`batch.pack_windows_grid`), ONE upload
+    and ONE grid sweep (`Batch.grid_sweep`): every daily row passes the device once, every (date, prior, length) is factorised
+    once at the largest size and each size solved over its prefix.  Conjugate specs only, or Jeffreys specs only, of one
+    (rebalancing frequency, window frequency) family.  (date, size, length) triples the pack cannot serve (its mask), sizes
+    above `_native.sweep_max_assets()`, more than `_native.SWEEP_MAX_RHS` sizes or lengths and a pack that raises go through
+    `_weights_for_dates` spec by spec, so the reference's exceptions surface where the reference raises them - unless
+    GRID_SWEEP_TILED is set: then, when the largest size exceeds that bound (and the sizes and lengths fit one tiled sweep), ALL
+    sizes are packed once at the largest and swept with `Batch.grid_sweep_tiled`.
+    Returns one (weights, labels, cols, caps) per spec, each at its own size - equal to `_weights_for_dates` spec by spec
+    within the solve's rounding - and remembers the conjugate ones in the cache slots `calculate_weights_for_specs` fills.
+    Opt-in: nothing calls it by default."""
+    specs = list(portfolio_specs_list)
+    if not specs:
+        return []
+    trading_dates = list(trading_dates)
+    n_dates = len(trading_dates)
+    sizes, windows, conj, same_gamma, swept, _ = _grid_sweep_stage(trading_dates, specs, market_data)
     out = []
     for sp in specs:
         ks = int(sp["size"])
@@ -1634,14 +1648,7 @@ def replay_backtests_device(trading_dates, rebalance_dates, items, market_data, 
         return []
     if tickers is None:
         tickers = batch.panels_for(market_data, items[0][3]["rolling_window_frequency"]).tickers
-    sr = market_data["stock_simple_returns_df"]
-    missing = [ts for ts in trading_dates[1:] if ts not in sr.index]
-    if missing:
-        raise KeyError(missing[0])                                        # ref:1134 `.loc[trading_date_ts]`
-    S = sr.reindex(index=pd.DatetimeIndex(trading_dates), columns=tickers).to_numpy(dtype=np.float64)
-    rf_daily = (_rf_asof(market_data["risk_free_rate_df"], trading_dates) + 1) ** (1 / 252) - 1         # ref:1140
-    day_of = {ts: d for d, ts in enumerate(trading_dates)}
-    reb_day = np.array([day_of[ts] for ts in rebalance_dates], dtype=np.int32)
+    S, rf_daily, reb_day = _device_replay_inputs(trading_dates, rebalance_dates, market_data, tickers)
     R = len(rebalance_dates)
     w_parts, c_parts, p_parts, w_at, u_at = [], [], [], {}, {}
     w_len = u_len = 0
@@ -1675,10 +1682,28 @@ def replay_backtests_device(trading_dates, rebalance_dates, items, market_data, 
     if np.any(np.asarray(status) != 0):
         logger.error("Weights do not sum to 1.")
         raise ValueError("Weights do not sum to 1.")
+    return _device_replay_results(trading_dates, rebalance_dates, [item[3] for item in items], returns, turnover, metrics)
+
+
+def _device_replay_inputs(trading_dates, rebalance_dates, market_data, tickers):
+    """(S [D x K] simple returns over `tickers`, rf_daily [D], reb_day [R]) as the device replays read them."""
+    sr = market_data["stock_simple_returns_df"]
+    missing = [ts for ts in trading_dates[1:] if ts not in sr.index]
+    if missing:
+        raise KeyError(missing[0])                                        # ref:1134 `.loc[trading_date_ts]`
+    S = sr.reindex(index=pd.DatetimeIndex(trading_dates), columns=tickers).to_numpy(dtype=np.float64)
+    rf_daily = (_rf_asof(market_data["risk_free_rate_df"], trading_dates) + 1) ** (1 / 252) - 1         # ref:1140
+    day_of = {ts: d for d, ts in enumerate(trading_dates)}
+    reb_day = np.array([day_of[ts] for ts in rebalance_dates], dtype=np.int32)
+    return S, rf_daily, reb_day
+
+
+def _device_replay_results(trading_dates, rebalance_dates, specs, returns, turnover, metrics):
+    """The dicts of `_replay_backtest`, one per spec, from a device replay's arrays."""
     days = pd.DatetimeIndex(trading_dates)
     reb = pd.DatetimeIndex(rebalance_dates)
     out = []
-    for p, (_w, _c, _m, spec) in enumerate(items):
+    for p, spec in enumerate(specs):
         name = spec["display_name"]
         out.append({"portfolio_simple_returns_series": pd.Series(returns[p, 1:], index=days[1:], name=name, dtype="float64"),
                     "portfolio_turnover_series": pd.Series(turnover[p, 1:], index=reb[1:], name=name, dtype="float64"),
@@ -1686,6 +1711,144 @@ def replay_backtests_device(trading_dates, rebalance_dates, items, market_data, 
                         metrics[p], index=reb, dtype="float64",
                         columns=["max_long", "max_short", "avg_long", "avg_short", "average_distance_to_comparison_portfolio"])})
     return out
+
+
+def _grid_replay_plan(specs, sizes, windows, prior_keys, mask, k):
+    """Where every spec of a grid family reads its weights in a grid sweep's results on the device - weights [W x P x L x S x k],
+    status [W x P x L x S], P = len(prior_keys) (Jeffreys: no keys, P = 1) - and which (spec, date) pairs the sweep does not
+    serve.  A pure function (no device, no market data).  Spec i with size sizes[s], window windows[l] and prior p reads, at
+    date j, the row at w_off[i] + j * w_stride[i] = ((j P + p) L + l) S + s) k and the status at s_off[i] + j * s_stride[i];
+    `w_scale[i]` is 1.0 when the risk aversions agree and 1.0 / risk_aversion otherwise (the sweep then ran with gamma = 1).
+    The dates `mask[:, s, l]` does not serve, and every date of a spec whose size is outside `sizes`, become patches: their
+    offsets are 0 with stride 0 for such a spec.  Returns a dict of arrays: w_off, w_stride, s_off, s_stride (int64 [n]),
+    w_scale (float64 [n]), swept (bool [n]: the spec's size is in the sweep) and patch_port (int64), patch_date (int32), sorted
+    by (spec, date)."""
+    specs = list(specs)
+    mask = np.asarray(mask, dtype=bool)
+    W = mask.shape[0]
+    P, L, S = max(len(prior_keys), 1), len(windows), len(sizes)
+    gammas = [sp["risk_aversion"] for sp in specs]
+    same_gamma = all(g == gammas[0] for g in gammas)
+    n = len(specs)
+    plan = {"w_off": np.zeros(n, dtype=np.int64), "w_stride": np.zeros(n, dtype=np.int64),
+            "s_off": np.zeros(n, dtype=np.int64), "s_stride": np.zeros(n, dtype=np.int64),
+            "w_scale": np.ones(n, dtype=np.float64), "swept": np.zeros(n, dtype=bool)}
+    patch_port, patch_date = [], []
+    for i, sp in enumerate(specs):
+        ks = int(sp["size"])
+        if not same_gamma:
+            plan["w_scale"][i] = 1.0 / sp["risk_aversion"]
+        if ks not in sizes:
+            missed = range(W)
+        else:
+            s, l = sizes.index(ks), windows.index(int(sp["rolling_window"]))
+            p = prior_keys.index((sp["weighting_strategy"], sp["mcm_scaling"])) if prior_keys else 0
+            entry = (p * L + l) * S + s
+            plan["swept"][i] = True
+            plan["s_off"][i], plan["s_stride"][i] = entry, P * L * S
+            plan["w_off"][i], plan["w_stride"][i] = entry * k, P * L * S * k
+            missed = np.flatnonzero(~mask[:, s, l])
+        for j in missed:
+            patch_port.append(i)
+            patch_date.append(int(j))
+    plan["patch_port"] = np.array(patch_port, dtype=np.int64)
+    plan["patch_date"] = np.array(patch_date, dtype=np.int32)
+    return plan
+
+
+def backtest_portfolios_grid(portfolio_specs_list, ts_start_date, ts_end_date, market_data):
+    """`backtest_portfolio` for ONE grid family - the specs `calculate_weights_for_grid` accepts, all of one rebalancing
+    frequency - with the weights never leaving the device: the pack, the upload and the grid sweep of
+    `calculate_weights_for_grid` (`_grid_sweep_stage`, weights not downloaded), then ONE `Batch.replay` of all specs that reads
+    the sweep's results where they lie; only statuses, P&L, turnover and metrics cross to the host.  Per spec, as there: the
+    statuses of the served entries are checked (`_raise_on_status`), the dates the pack does not serve and the specs whose size
+    is outside the sweep are solved by `_weights_for_dates` and go up as patch rows with that spec's own copy of the universe
+    rows; different risk aversions become a per-spec scale 1.0 / risk_aversion on the device, the host's `1.0 / g * w`.
+    Returns {display_name: dict}, the dicts of `_replay_backtest` - equal bit for bit to `calculate_weights_for_grid` followed by
+    `replay_backtests_device`.  "Weights do not sum to 1." raises the reference's ValueError.  Without a sweep that serves the
+    family (a pack that raises, no size within the sweep) it is exactly that pair of calls.
+    Opt-in: nothing calls it by default.  It does not fill the spec caches `calculate_weights_for_grid` fills: the weights are
+    never on the host."""
+    specs = list(portfolio_specs_list)
+    if not specs:
+        return {}
+    trading_dates = [pd.Timestamp(ts) for ts in market_data["stock_prices_df"].index]
+    trading_dates = [ts for ts in trading_dates if ts_start_date <= ts <= ts_end_date]
+    rebalance_dates = rebalancing_schedule(trading_dates, specs[0]["rebalancing_frequency"])
+    tickers = batch.panels_for(market_data, specs[0]["rolling_window_frequency"]).tickers
+    sizes, windows, conj, same_gamma, swept, b = _grid_sweep_stage(rebalance_dates, specs, market_data, want_weights=False,
+                                                                   keep_open=True)
+    try:
+        R = len(rebalance_dates)
+        fits = swept is not None and any(int(sp["size"]) in sizes for sp in specs)
+        if fits:
+            _none, status, labels, cols, caps, mask, prior_keys = swept
+            k = sizes[-1]
+            # (an unswept spec reads no source row, but its k rows at offset 0 must lie inside the source all the same)
+            fits = max(int(sp["size"]) for sp in specs) <= status.size * k
+        if not fits:
+            if b is not None:
+                b.close()
+                b = None
+            found = calculate_weights_for_grid(rebalance_dates, specs, market_data)
+            results = replay_backtests_device(trading_dates, rebalance_dates,
+                                              [(res[0], res[2], res[3], sp) for res, sp in zip(found, specs)], market_data,
+                                              tickers=tickers)
+            return {sp["display_name"]: res for sp, res in zip(specs, results)}
+        plan = _grid_replay_plan(specs, sizes, windows, prior_keys, mask, k)
+        # universe tables: the pack's [R x k] first (a served spec holds its prefix, stride k); a patched spec's own copy after it
+        c_parts, p_parts = [np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)], [np.ascontiguousarray(caps, dtype=np.float64).reshape(-1)]
+        u_len = R * k
+        u_off, u_stride, rows = [], [], []
+        for i, sp in enumerate(specs):
+            ks = int(sp["size"])
+            miss = plan["patch_date"][plan["patch_port"] == i]
+            if plan["swept"][i]:
+                served = mask[:, sizes.index(ks), windows.index(int(sp["rolling_window"]))]
+                _raise_on_status(status.reshape(R, -1)[served, plan["s_off"][i]])
+            if not miss.size:
+                u_off.append(0)
+                u_stride.append(k)
+                continue
+            alone = _weights_for_dates([rebalance_dates[j] for j in miss], sp, market_data)
+            if plan["swept"][i]:
+                own_cols, own_caps = cols[:, :ks].copy(), caps[:, :ks].copy()
+            else:
+                own_cols, own_caps = np.empty((R, ks), dtype=np.int32), np.empty((R, ks), dtype=np.float64)
+            for q, j in enumerate(miss):
+                own_cols[j], own_caps[j] = alone[2][q], alone[3][q]
+                rows.append(np.asarray(alone[0][q], dtype=np.float64))
+            u_off.append(u_len)
+            u_stride.append(ks)
+            c_parts.append(np.ascontiguousarray(own_cols, dtype=np.int32).reshape(-1))
+            p_parts.append(np.ascontiguousarray(own_caps, dtype=np.float64).reshape(-1))
+            u_len += R * ks
+        patches = None
+        if rows:
+            patch_rows = np.zeros((len(rows), max(r.size for r in rows)), dtype=np.float64)
+            for q, r in enumerate(rows):
+                patch_rows[q, :r.size] = r
+            patches = (plan["patch_port"], plan["patch_date"], patch_rows)
+        S, rf_daily, reb_day = _device_replay_inputs(trading_dates, rebalance_dates, market_data, tickers)
+        returns, turnover, metrics, rstatus, _bad_day = b.replay(
+            _native.REPLAY_SRC_GRID_SWEEP, S, rf_daily, reb_day, len(tickers), np.array([int(sp["size"]) for sp in specs], dtype=np.int32),
+            np.array([sp["risk_aversion"] if sp.get("risk_aversion") is not None else 1 for sp in specs], dtype=np.float64),
+            np.array([sp["turnover_cost"] for sp in specs], dtype=np.float64),
+            plan["w_off"], plan["w_stride"], plan["s_off"], plan["s_stride"], np.array(u_off, dtype=np.int64),
+            np.array(u_stride, dtype=np.int64), np.concatenate(c_parts), np.concatenate(p_parts),
+            w_scale=plan["w_scale"], patches=patches)
+    finally:
+        if b is not None:
+            b.close()
+    rstatus = np.asarray(rstatus)
+    if np.any(rstatus == _native.REPLAY_BAD_WEIGHTS):
+        raise RuntimeError("backtest_portfolios_grid: the replay read a weight row its sweep flagged, although every served status "
+                           "was checked")
+    if np.any(rstatus != 0):
+        logger.error("Weights do not sum to 1.")
+        raise ValueError("Weights do not sum to 1.")
+    results = _device_replay_results(trading_dates, rebalance_dates, specs, returns, turnover, metrics)
+    return {sp["display_name"]: res for sp, res in zip(specs, results)}
 
 
 def backtest_portfolio(portfolio_spec, ts_start_date, ts_end_date, market_data):
