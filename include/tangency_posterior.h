@@ -715,6 +715,53 @@ int tp_replay_run_batch(tp_batch_t b, int source,
  * a status); each may be NULL.  Without a tp_replay_run or tp_replay_run_batch before it: TP_ERR_INVALID. */
 int tp_replay_download(tp_handle_t h, double* returns, double* turnover, double* metrics, int32_t* status, int32_t* bad_day);
 
+/* Performance summary of the last replay on the handle (tp_replay_run or tp_replay_run_batch) over a grid of C trading costs:
+ * the statistics the evaluation of ref:464-701 (performance_metrics) takes from a strategy's daily returns, reduced on the
+ * device to one record of TP_SUMMARY_STATS doubles per (portfolio, cost), one wavefront each; only the records come down.  A
+ * cost never touches the holdings - it enters a replay only through ref:1212 - so ONE replay at cost 0 carries every cost.
+ * All operations in double, one rounding each.  For portfolio p, cost c and n = D - 1 (day 0 is never read), d = 1 .. D-1:
+ *   net return x_d = returns[p][d] as stored; on a day d = reb_day[j] with j >= 1 it is
+ *     fl(returns[p][d] - fl(fl(cost_bp[c] / 10000) turnover[p][j])) - with the replay run at cost 0, bit for bit the returns of a
+ *     replay run at cost c.  On every other day the stored value is selected: no turnover reaches it;
+ *   excess return e_d = fl(x_d - rf_excess[d]) (ref:712-713; the caller forms rf_excess);
+ *   adjust_returns (ref:46-72), applied to x and to e separately (ref:484, 488): with W_i = prod_{d <= i} (1 + a_d), at the first i
+ *     with W_i - 1 < -1: a_i = -1 if i is day 1, else a_i = 0.000001 / (W_{i-1} - 1) - 1 (as the reference wrote it, a division
+ *     by zero included); every later day is 0.  The adjusted series are a (from x) and b (from e);
+ *   insolvency (ref:27-33): the first d with W_d - 1 < -0.99 on a.
+ * The record, in this order:
+ *    0 N_OBS n;  1 ADJ_DAY the trading day adjust_returns changed in a, -1: none;  2 INSOLVENT_DAY, -1: none;
+ *    3 COMP W_{D-1} - 1 of a;  4 MEAN, 5 STD of a (two passes, ddof = 1, NaN for n < 2);
+ *    6 MAX_DD min_d W_d / max_{d' <= d} W_d' - 1, the running peak starting at W_1 (NaN when that peak is 0: day 1 was
+ *      adjusted and every quotient is 0 / 0);  7 BEST, 8 WORST of a (selections);
+ *    9 SUM_WIN, 10 N_WIN over a > 0;  11 SUM_LOSS, 12 N_LOSS over a < 0;
+ *   13 N_PRE, 14 MEAN_PRE, 15 STD_PRE, 16 WORST_PRE over the days d < INSOLVENT_DAY (ref:644, 660, 670; all days without one;
+ *      NaN where N_PRE is too small);  17 SUM_NONZERO, 18 N_NONZERO over |a| > 1e-7 (ref:612);
+ *   19 ADJ_DAY_E as ADJ_DAY, for b;  20 MEAN_E, 21 STD_E (ddof = 1) of b;  22-24 M2_E, M3_E, M4_E = sum (b - MEAN_E)^k / n, the
+ *      biased central moments;  25 DOWNSIDE_E sum_{b < 0} b^2 / n;
+ *   26 TURNOVER_SUM, 27 TURNOVER_N over j = 1 .. R-1 with reb_day[j] <= INSOLVENT_DAY (ref:696; all j without one);
+ *   28-31 reserved, 0.0.
+ * status[p][c]: TP_SUMMARY_OK; TP_SUMMARY_NO_REPLAY - the replay's status[p] is set: fields 0-27 are NaN; TP_SUMMARY_NONFINITE - a
+ * or b holds a NaN or an infinity: fields 0, 1, 2 and 19 are kept, the other fields below 28 are NaN (no NaN-skipping).
+ * Days go through in tiles of 64, the products are a six-step scan across the wave times the carry of the tile before, every
+ * sum is a lane-local partial in tile order and the replay's fixed 64-lane tree: a record is the same bit for bit from run to
+ * run, for a portfolio alone or among others, for a cost alone or among others.  Against a sequential host loop it agrees to
+ * rounding.
+ * TP_ERR_INVALID, all checked before anything is waited for, uploaded or launched (a refused call leaves the last replay's and
+ * the last summary's results in place): no replay before it; a replay of D < 2 days; C < 1 or C > TP_SUMMARY_MAX_COSTS; a NULL
+ * array; a cost that is not finite (rf_excess may hold NaN: TP_SUMMARY_NONFINITE).
+ * The call waits on entry for whatever is queued on the handle's stream - the replay ends here -, uploads cost_bp and
+ * rf_excess (HOST pointers, not kept) and queues one launch without waiting for it.  The replay's results are not written:
+ * tp_replay_download returns the same bytes before and after.  kernel_ms, tp_region_steps and tp_last_launch: as tp_replay_run. */
+#define TP_SUMMARY_STATS 32
+#define TP_SUMMARY_MAX_COSTS 64
+#define TP_SUMMARY_OK 0
+#define TP_SUMMARY_NO_REPLAY 1
+#define TP_SUMMARY_NONFINITE 2
+int tp_replay_summary(tp_handle_t h, int32_t C, const double* cost_bp /* [C] */, const double* rf_excess /* [D] */);
+/* Waits for the summary and copies out stats [P x C x TP_SUMMARY_STATS] and status [P x C]; each may be NULL.  TP_ERR_INVALID
+ * without a tp_replay_summary before it, or when a newer replay has replaced the one it read. */
+int tp_replay_download_summary(tp_handle_t h, double* stats, int32_t* status);
+
 int tp_synchronize(tp_handle_t h);
 /* Timings of the most recent call of each kind on this handle, in milliseconds (HIP events on the
  * handle's stream): posterior kernel, H2D upload, D2H download, RCCL gather. */

@@ -39,6 +39,9 @@ REPLAY_SUM_CHECK = 1
 REPLAY_BAD_WEIGHTS = 2
 REPLAY_METRICS = 5
 REPLAY_SRC_RUN, REPLAY_SRC_PRIOR_SWEEP, REPLAY_SRC_SIZE_SWEEP, REPLAY_SRC_WINDOW_SWEEP, REPLAY_SRC_GRID_SWEEP = 0, 1, 2, 3, 4
+SUMMARY_STATS = 32
+SUMMARY_MAX_COSTS = 64
+SUMMARY_OK, SUMMARY_NO_REPLAY, SUMMARY_NONFINITE = 0, 1, 2
 
 # every symbol include/tangency_posterior.h declares (checked by tests/test_cabi_symbols.py)
 EXPORTS = [
@@ -56,6 +59,7 @@ EXPORTS = [
     "tp_batch_window_sweep", "tp_batch_window_sweep_tiled", "tp_batch_download_window_sweep",
     "tp_batch_grid_sweep", "tp_batch_grid_sweep_tiled", "tp_batch_download_grid_sweep",
     "tp_replay_merge_maps", "tp_replay_run", "tp_replay_run_batch", "tp_replay_download",
+    "tp_replay_summary", "tp_replay_download_summary",
     "tp_batch_debug_stamps", "tp_batch_destroy", "tp_posterior_batch", "tp_synchronize", "tp_last_timing",
     "tp_region_begin", "tp_region_end", "tp_region_steps", "tp_last_launch", "tp_comm_unique_id", "tp_comm_init", "tp_comm_destroy",
     "tp_comm_count", "tp_comm_init_all", "tp_group_gather",
@@ -160,6 +164,8 @@ def _load():
                                         c_int64, POINTER(c_int64), POINTER(c_int32), POINTER(c_double), c_int32]
     lib.tp_replay_download.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32),
                                        POINTER(c_int32)]
+    lib.tp_replay_summary.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
+    lib.tp_replay_download_summary.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32)]
     lib.tp_synchronize.argtypes = [c_void_p]
     lib.tp_last_timing.argtypes = [c_void_p] + [POINTER(c_double)] * 4
     lib.tp_region_begin.argtypes = [c_void_p]
@@ -404,6 +410,7 @@ class Device:
     def __init__(self, device_id: int = 0):
         self._h = c_void_p()
         self._batches = weakref.WeakSet()
+        self._replay_shape = None      # (P, D, R) of the last replay on this handle (replay_summary sizes its arrays by it)
         rc = lib.tp_create(int(device_id), ctypes.byref(self._h))
         if rc != TP_OK:
             raise TangencyError(rc, lib.tp_last_error(None).decode())
@@ -532,7 +539,8 @@ class Device:
         return out
 
     # ---- backtest replay ----------------------------------------------------------------------
-    def replay(self, S, rf_daily, reb_day, K, k, scaling, cost, w_off, w_stride, u_off, u_stride, weights, cols, caps):
+    def replay(self, S, rf_daily, reb_day, K, k, scaling, cost, w_off, w_stride, u_off, u_stride, weights, cols, caps,
+               download=True):
         """`tp_replay_run` + `tp_replay_download`: daily P&L, weight drift, turnover and weight metrics of P portfolios that
         share trading days and a rebalancing schedule, one wavefront each.  `S` [D x ld] simple returns (the first `K` columns
         are tickers), `rf_daily` [D], `reb_day` [R] trading-day indices (strictly increasing from 0, below D).  Portfolio p
@@ -540,7 +548,8 @@ class Device:
         and their caps `cols.flat[...]` / `caps.flat[u_off[p] + j * u_stride[p] + i]` (cols and caps have one shape).  Every
         check is made before any device call.  Returns (returns [P, D], turnover [P, R], metrics [P, R, 5], status [P],
         bad_day [P]); returns[:, 0] and turnover[:, 0] are NaN; status REPLAY_SUM_CHECK: the weights of that portfolio stopped
-        summing to 1 on day bad_day (the host replay raises there)."""
+        summing to 1 on day bad_day (the host replay raises there).  `download=False`: nothing is returned and nothing is
+        copied; the results stay on the device for `replay_summary` (and `_replay_download`)."""
         S, D, ld, K, rf, reb, R, kk, P, sc, co = _replay_schedule(S, rf_daily, reb_day, K, k, scaling, cost)
         wo, wst, uo, ust = (_replay_integer(name, a, np.int64, (P,)) for name, a in
                             (("w_off", w_off), ("w_stride", w_stride), ("u_off", u_off), ("u_stride", u_stride)))
@@ -557,7 +566,34 @@ class Device:
                                       nz(kk, c_int32), nz(sc, c_double), nz(co, c_double), nz(wo, c_int64), nz(wst, c_int64),
                                       nz(uo, c_int64), nz(ust, c_int64), nz(wts, c_double), wts.size, nz(cl, c_int32),
                                       nz(cp, c_double), cl.size))
-        return self._replay_download(P, D, R)
+        self._replay_shape = (P, D, R)
+        return self._replay_download(P, D, R) if download else None
+
+    def replay_summary(self, cost_bp, rf_excess):
+        """`tp_replay_summary` + `tp_replay_download_summary` of the last replay on this handle (`replay`, `Batch.replay`, with
+        `download=False` or not): the performance statistics of every portfolio's daily returns at every trading cost of
+        `cost_bp` [C] (basis points, finite, C <= SUMMARY_MAX_COSTS), with `rf_excess` [D] the daily risk-free rate the excess
+        returns subtract (NaN allowed: SUMMARY_NONFINITE).  The costs are applied on the device to the replay's own returns and
+        turnover - replay at cost 0.  Returns (stats [P, C, SUMMARY_STATS], status [P, C]); include/tangency_posterior.h
+        defines the fields, `portfolio_evaluation.performance_table` turns them into the reference's metrics."""
+        if self._replay_shape is None:
+            raise ValueError("replay_summary: no replay on this device yet")
+        P, D, _R = self._replay_shape
+        co = _replay_real("cost_bp", cost_bp)
+        rf = _replay_real("rf_excess", rf_excess)
+        if co.ndim != 1 or not 1 <= co.size <= SUMMARY_MAX_COSTS:
+            raise ValueError(f"cost_bp: 1 to {SUMMARY_MAX_COSTS} costs in a 1-D array expected, got shape {tuple(co.shape)}")
+        if not np.isfinite(co).all():
+            raise ValueError("cost_bp: finite costs expected")
+        if rf.shape != (D,):
+            raise ValueError(f"rf_excess: expected shape ({D},), got {tuple(rf.shape)}")
+        C = int(co.size)
+        self._check(lib.tp_replay_summary(self._h, C, _ptr(co, c_double), _ptr(rf, c_double)))
+        stats = np.empty((P, C, SUMMARY_STATS), dtype=np.float64)
+        status = np.empty((P, C), dtype=np.int32)
+        nz = lambda a, ct: _ptr(a if a.size else None, ct)   # noqa: E731
+        self._check(lib.tp_replay_download_summary(self._h, nz(stats, c_double), nz(status, c_int32)))
+        return stats, status
 
     def _replay_download(self, P, D, R):
         """`tp_replay_download`: the results of the last replay on this handle (`replay`, `Batch.replay`)."""
@@ -1032,7 +1068,7 @@ class Batch:
         return weights, status, aux
 
     def replay(self, source, S, rf_daily, reb_day, K, k, scaling, cost, w_off, w_stride, s_off, s_stride, u_off, u_stride,
-               cols, caps, w_scale=None, patches=None):
+               cols, caps, w_scale=None, patches=None, download=True):
         """`tp_replay_run_batch` + `tp_replay_download`: `Device.replay` with the weights read where this batch's last run or
         sweep of kind `source` (REPLAY_SRC_*) left them on the device - nothing but the small inputs goes up, nothing but the
         results comes down.  At rebalancing date j portfolio p holds `w_scale[p] * src[w_off[p] + j * w_stride[p] + i]`
@@ -1043,7 +1079,8 @@ class Batch:
         (port, date), strictly.  The other arguments and the returns are `Device.replay`'s; status REPLAY_BAD_WEIGHTS: a row
         was read whose source status was not STATUS_OK, at rebalancing day bad_day (NaN from there on).  Shapes and types are
         checked here, before any device call; the library checks the source, the offsets against the source's counts and the
-        patches' order before it uploads or launches anything (TangencyError, code ERR_INVALID)."""
+        patches' order before it uploads or launches anything (TangencyError, code ERR_INVALID).  `download=False`: as
+        `Device.replay`."""
         source = int(source)
         S, D, ld, K, rf, reb, R, kk, P, sc, co = _replay_schedule(S, rf_daily, reb_day, K, k, scaling, cost)
         wo, wst, so, sst, uo, ust = (_replay_integer(name, a, np.int64, (P,)) for name, a in
@@ -1078,7 +1115,8 @@ class Batch:
                                            nz(wo, c_int64), nz(wst, c_int64), nz(so, c_int64), nz(sst, c_int64),
                                            nz(uo, c_int64), nz(ust, c_int64), nz(cl, c_int32), nz(cp, c_double), cl.size,
                                            n_patch, nz(pp, c_int64), nz(pd_, c_int32), nz(pr, c_double), patch_ld))
-        return dev._replay_download(P, D, R)
+        dev._replay_shape = (P, D, R)
+        return dev._replay_download(P, D, R) if download else None
 
     def download(self, want_aux=True, out=None):
         """(weights, status, aux).  `out=(weights, status[, aux])`: write into these arrays (e.g. `pinned_empty`)."""

@@ -21,6 +21,7 @@
 #include "posterior_window_sweep.h"
 
 #include "backtest_replay.h"
+#include "replay_summary.h"
 
 #define TP_REGION_MAX_STEPS 512
 
@@ -33,6 +34,12 @@ struct ReplayWs {
     DevBuf ret, turnover, metrics, status, bad_day;
     int64_t P = 0, D = 0, R = 0;    // shape of the last run
     bool ran = false;               // a run completed its launches (tp_replay_download has something to copy)
+    // tp_replay_summary / tp_replay_download_summary (replay_summary.hip): the costs, the excess risk-free rates, the
+    // rebalancing date of every trading day, and the records and statuses of the last summary [P x C]
+    DevBuf sum_cost, sum_rf, sum_day, sum_stats, sum_status;
+    std::vector<int32_t> h_reb;     // host copy of reb_day of the last run (the summary's table of days is built from it)
+    int32_t C = 0;                  // costs of the last summary
+    bool summarised = false;        // a summary of the last run completed its launch
 };
 
 // Members are destroyed in reverse order of declaration: the kernel stream is declared before every other stream and

@@ -1,8 +1,10 @@
 // tangency_replay.cpp - the backtest replay of the C-ABI of libtangency.so (include/tangency_posterior.h):
-// tp_replay_merge_maps (host only), tp_replay_run, tp_replay_run_batch, tp_replay_download.  A run is: checks of every offset,
+// tp_replay_merge_maps (host only), tp_replay_run, tp_replay_run_batch, tp_replay_download, and the summary of a run's returns
+// over a grid of trading costs, tp_replay_summary / tp_replay_download_summary (replay_summary.hip).  A run is: checks of every offset,
 // stride and index on the host, the merge maps of every distinct universe table, the uploads, then one launch per
 // slots-per-lane class of the portfolios inside one timed span (backtest_replay.hip).  The buffers live on the handle (ReplayWs,
 // tangency_host.h).  tp_replay_run_batch is the same run with the weights left where a batch's run or sweep wrote them.
+#include <cmath>
 #include <cstring>
 #include <algorithm>
 #include <map>
@@ -15,6 +17,9 @@ using namespace tp_host;
 
 static_assert(TP_REPLAY_SUM_CHECK == TP_REPLAY_KSTATUS_SUM_CHECK, "replay status codes out of sync");
 static_assert(TP_REPLAY_BAD_WEIGHTS == TP_REPLAY_KSTATUS_BAD_WEIGHTS, "replay status codes out of sync");
+static_assert(TP_SUMMARY_STATS == TP_SUMMARY_NSTATS, "summary record sizes out of sync");
+static_assert(TP_SUMMARY_NO_REPLAY == TP_SUMMARY_KSTATUS_NO_REPLAY && TP_SUMMARY_NONFINITE == TP_SUMMARY_KSTATUS_NONFINITE,
+              "summary status codes out of sync");
 
 namespace {
 
@@ -192,6 +197,7 @@ int run_replay(tp_handle_t h, const char* name, int64_t D, int32_t ld, const dou
     int rc = harvest_kernel_time(h);
     if (rc != TP_OK) return rc;
     ws.ran = false;
+    ws.summarised = false;                                // (a summary belongs to the run it read)
     struct Up { DevBuf* b; const void* src; size_t bytes; const char* what; };
     const size_t flat = P > 0 ? 1 : 0;                    // (no portfolio: the flat buffers may be absent)
     const size_t n_patch = feed ? (size_t)feed->n_patch : 0;
@@ -248,6 +254,7 @@ int run_replay(tp_handle_t h, const char* name, int64_t D, int32_t ld, const dou
     rc = timed_done(h, span);
     if (rc != TP_OK) return rc;
     ws.P = P; ws.D = D; ws.R = R;
+    ws.h_reb.assign(reb_day, reb_day + R);
     ws.ran = true;
     return TP_OK;
 }
@@ -329,6 +336,64 @@ int tp_replay_download(tp_handle_t h, double* returns, double* turnover, double*
                         {metrics, ws.metrics.p, P * R * TP_REPLAY_METRICS * sizeof(double)},
                         {status, ws.status.p, P * sizeof(int32_t)},
                         {bad_day, ws.bad_day.p, P * sizeof(int32_t)}});
+}
+
+int tp_replay_summary(tp_handle_t h, int32_t C, const double* cost_bp, const double* rf_excess) {
+    if (!h) return TP_ERR_INVALID;
+    ReplayWs& ws = h->replay;
+    // ---- checks, all before the drain: a refused call leaves the last replay's and the last summary's results in place
+    if (!ws.ran) return fail(h, TP_ERR_INVALID, "tp_replay_summary without a tp_replay_run or tp_replay_run_batch before it");
+    if (C < 1 || C > TP_SUMMARY_MAX_COSTS)
+        return fail(h, TP_ERR_INVALID, "tp_replay_summary: C=%d outside [1, %d]", C, TP_SUMMARY_MAX_COSTS);
+    if (!cost_bp || !rf_excess) return fail(h, TP_ERR_INVALID, "tp_replay_summary: cost_bp or rf_excess is NULL");
+    for (int32_t c = 0; c < C; ++c)
+        if (!std::isfinite(cost_bp[c])) return fail(h, TP_ERR_INVALID, "tp_replay_summary: cost_bp[%d] is not finite", c);
+    if (ws.D < 2) return fail(h, TP_ERR_INVALID, "tp_replay_summary: D=%lld: a replay of at least two trading days (one return) is expected", (long long)ws.D);
+    const size_t P = (size_t)ws.P, D = (size_t)ws.D, R = (size_t)ws.R;
+    // the rebalancing date of every trading day (date 0, on day 0, charges nothing: ref:1212 needs a portfolio before it)
+    std::vector<int32_t> day_date(D, -1);
+    for (size_t j = 1; j < R; ++j) day_date[(size_t)ws.h_reb[j]] = (int32_t)j;
+    // ---- device: drain (the replay ends here; its span is read), upload, one launch that is not awaited
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int rc = harvest_kernel_time(h);
+    if (rc != TP_OK) return rc;
+    ws.summarised = false;
+    if ((rc = upload(h, ws.sum_cost, cost_bp, (size_t)C * sizeof(double), "summary costs")) != TP_OK) return rc;
+    if ((rc = upload(h, ws.sum_rf, rf_excess, D * sizeof(double), "summary excess risk-free rates")) != TP_OK) return rc;
+    if ((rc = upload(h, ws.sum_day, day_date.data(), D * sizeof(int32_t), "summary days")) != TP_OK) return rc;
+    if ((rc = ensure(h, ws.sum_stats, P * (size_t)C * TP_SUMMARY_STATS * sizeof(double), "summary records")) != TP_OK) return rc;
+    if ((rc = ensure(h, ws.sum_status, P * (size_t)C * sizeof(int32_t), "summary statuses")) != TP_OK) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));          // the host arrays are free again
+    tp_summary_args_t a;
+    memset(&a, 0, sizeof a);
+    a.ret = (const double*)ws.ret.p; a.turnover = (const double*)ws.turnover.p; a.rstatus = (const int*)ws.status.p;
+    a.reb_day = (const int*)ws.reb.p; a.day_date = (const int*)ws.sum_day.p;
+    a.cost_bp = (const double*)ws.sum_cost.p; a.rf_excess = (const double*)ws.sum_rf.p;
+    a.stats = (double*)ws.sum_stats.p; a.status = (int*)ws.sum_status.p;
+    a.P = (int)ws.P; a.D = (int)ws.D; a.R = (int)ws.R; a.C = C;
+    const tp_launch_info_t keep_launch = h->last_launch;  // tp_last_launch keeps describing tp_batch_run
+    Span& span = timed_span(h);
+    HIP_TRY(h, span.begin(h->stream));
+    const hipError_t e = tp_summary_launch(a, h->stream);
+    if (e != hipSuccess) return fail(h, TP_ERR_HIP, "replay summary kernel launch failed: %s", hipGetErrorString(e));
+    h->last_launch = keep_launch;
+    rc = timed_done(h, span);
+    if (rc != TP_OK) return rc;
+    ws.C = C;
+    ws.summarised = true;
+    return TP_OK;
+}
+
+int tp_replay_download_summary(tp_handle_t h, double* stats, int32_t* status) {
+    if (!h) return TP_ERR_INVALID;
+    const ReplayWs& ws = h->replay;
+    if (!ws.ran || !ws.summarised)
+        return fail(h, TP_ERR_INVALID, "tp_replay_download_summary without a tp_replay_summary of the last replay before it");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)ws.P * (size_t)ws.C;
+    return download(h, {{stats, ws.sum_stats.p, n * TP_SUMMARY_STATS * sizeof(double)},
+                        {status, ws.sum_status.p, n * sizeof(int32_t)}});
 }
 
 }  // extern "C"

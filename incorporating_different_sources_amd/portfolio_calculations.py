@@ -31,10 +31,11 @@ import numpy as np
 import pandas as pd
 
 try:  # importable both as a package module and as a top-level `portfolio_calculations` (main.py style)
-    from . import _native, batch, portfolio_specs, shard
+    from . import _native, batch, portfolio_evaluation, portfolio_specs, shard
 except ImportError:  # pragma: no cover - top-level import with the package directory on sys.path
     import _native  # type: ignore
     import batch  # type: ignore
+    import portfolio_evaluation  # type: ignore
     import portfolio_specs  # type: ignore
     import shard  # type: ignore
 
@@ -1646,6 +1647,57 @@ def replay_backtests_device(trading_dates, rebalance_dates, items, market_data, 
     items = list(items)
     if not items:
         return []
+    _dev, (returns, turnover, metrics, status, _bad_day) = _replay_items(trading_dates, rebalance_dates, items, market_data,
+                                                                         tickers, device)
+    if np.any(np.asarray(status) != 0):
+        logger.error("Weights do not sum to 1.")
+        raise ValueError("Weights do not sum to 1.")
+    return _device_replay_results(trading_dates, rebalance_dates, [item[3] for item in items], returns, turnover, metrics)
+
+
+def summarise_backtests_device(trading_dates, rebalance_dates, items, market_data, turnover_costs, tickers=None, device=None):
+    """The metrics table of ref:464-701 for the `items` of `replay_backtests_device` at every trading cost of `turnover_costs`
+    (basis points), without the P&L ever leaving the device: ONE replay at cost 0 (a cost never touches the holdings, ref:1212;
+    the specs' own `turnover_cost` is not read), its results kept on the device (`download=False`), then
+    `Device.replay_summary` over the costs; 256 bytes per (spec, cost) come down.  Returns the frame of
+    `portfolio_evaluation.performance_table`, indexed by (display_name, cost); Prob. Sharpe against the 'S&P 500' column of
+    market_data["sp500_simple_returns_df"] when the market data has one (ref:555), NaN otherwise.  "Weights do not sum to 1."
+    raises the reference's ValueError."""
+    items = list(items)
+    if not items:
+        return portfolio_evaluation.performance_table(np.zeros((0, len(turnover_costs), _native.SUMMARY_STATS)),
+                                                      np.zeros((0, len(turnover_costs)), dtype=np.int32), trading_dates, [],
+                                                      turnover_costs)
+    dev, _none = _replay_items(trading_dates, rebalance_dates, items, market_data, tickers, device, cost_all=0.0, download=False)
+    table = _summary_table(dev, trading_dates, [item[3] for item in items], market_data, turnover_costs)
+    if table is None:
+        logger.error("Weights do not sum to 1.")
+        raise ValueError("Weights do not sum to 1.")
+    return table
+
+
+def _summary_table(dev, trading_dates, specs, market_data, turnover_costs):
+    """`Device.replay_summary` of the replay just queued on `dev` and the frame of `performance_table` for `specs`; None when
+    the replay set a status (the caller raises what that status means)."""
+    rates = market_data["risk_free_rate_df"]
+    if "DTB3" not in rates:                                   # (`_rf_asof` reads the first column, whatever its name)
+        rates = rates.rename(columns={rates.columns[0]: "DTB3"})
+    rf_excess = portfolio_evaluation.rf_excess_for(trading_dates, rates)
+    stats, status = dev.replay_summary(turnover_costs, rf_excess)
+    if np.any(status == _native.SUMMARY_NO_REPLAY):
+        return None
+    benchmark = None
+    sp500 = market_data.get("sp500_simple_returns_df")
+    if sp500 is not None:
+        series = sp500.iloc[:, 0].reindex(pd.DatetimeIndex(trading_dates)[1:])
+        benchmark = (series.to_numpy(dtype=np.float64) - rf_excess[1:])
+    return portfolio_evaluation.performance_table(stats, status, trading_dates, [sp["display_name"] for sp in specs],
+                                                  turnover_costs, benchmark_excess=benchmark)
+
+
+def _replay_items(trading_dates, rebalance_dates, items, market_data, tickers, device, cost_all=None, download=True):
+    """Packs `items` and replays them in one `Device.replay`: (device, what the replay returned).  `cost_all`: one trading cost
+    for every item instead of its spec's."""
     if tickers is None:
         tickers = batch.panels_for(market_data, items[0][3]["rolling_window_frequency"]).tickers
     S, rf_daily, reb_day = _device_replay_inputs(trading_dates, rebalance_dates, market_data, tickers)
@@ -1669,20 +1721,17 @@ def replay_backtests_device(trading_dates, rebalance_dates, items, market_data, 
             u_len += R * k
         ks.append(k)
         scaling.append(spec["risk_aversion"] if spec.get("risk_aversion") is not None else 1)
-        cost.append(spec["turnover_cost"])
+        cost.append(spec["turnover_cost"] if cost_all is None else cost_all)
         w_off.append(w_at[id(weights)])
         u_off.append(u_at[(id(cols), id(caps))])
     ks = np.array(ks, dtype=np.int32)
     stride = ks.astype(np.int64)
     dev = device if device is not None else _native.default_device()
-    returns, turnover, metrics, status, _bad_day = dev.replay(
+    keep = {} if download else {"download": False}            # (the downloading call is the one `device` objects always took)
+    return dev, dev.replay(
         S, rf_daily, reb_day, len(tickers), ks, np.array(scaling, dtype=np.float64), np.array(cost, dtype=np.float64),
         np.array(w_off, dtype=np.int64), stride, np.array(u_off, dtype=np.int64), stride,
-        np.concatenate(w_parts), np.concatenate(c_parts), np.concatenate(p_parts))
-    if np.any(np.asarray(status) != 0):
-        logger.error("Weights do not sum to 1.")
-        raise ValueError("Weights do not sum to 1.")
-    return _device_replay_results(trading_dates, rebalance_dates, [item[3] for item in items], returns, turnover, metrics)
+        np.concatenate(w_parts), np.concatenate(c_parts), np.concatenate(p_parts), **keep)
 
 
 def _device_replay_inputs(trading_dates, rebalance_dates, market_data, tickers):
@@ -1756,7 +1805,7 @@ def _grid_replay_plan(specs, sizes, windows, prior_keys, mask, k):
     return plan
 
 
-def backtest_portfolios_grid(portfolio_specs_list, ts_start_date, ts_end_date, market_data):
+def backtest_portfolios_grid(portfolio_specs_list, ts_start_date, ts_end_date, market_data, turnover_costs=None):
     """`backtest_portfolio` for ONE grid family - the specs `calculate_weights_for_grid` accepts, all of one rebalancing
     frequency - with the weights never leaving the device: the pack, the upload and the grid sweep of
     `calculate_weights_for_grid` (`_grid_sweep_stage`, weights not downloaded), then ONE `Batch.replay` of all specs that reads
@@ -1768,7 +1817,10 @@ def backtest_portfolios_grid(portfolio_specs_list, ts_start_date, ts_end_date, m
     `replay_backtests_device`.  "Weights do not sum to 1." raises the reference's ValueError.  Without a sweep that serves the
     family (a pack that raises, no size within the sweep) it is exactly that pair of calls.
     Opt-in: nothing calls it by default.  It does not fill the spec caches `calculate_weights_for_grid` fills: the weights are
-    never on the host."""
+    never on the host.
+    `turnover_costs` (basis points): instead of the dicts, the metrics table of `summarise_backtests_device` for the family at
+    every one of these costs - the replay runs once at cost 0 and keeps its results on the device (`download=False`), so only
+    statuses and 256 bytes per (spec, cost) come down; the specs' own `turnover_cost` is not read."""
     specs = list(portfolio_specs_list)
     if not specs:
         return {}
@@ -1791,9 +1843,10 @@ def backtest_portfolios_grid(portfolio_specs_list, ts_start_date, ts_end_date, m
                 b.close()
                 b = None
             found = calculate_weights_for_grid(rebalance_dates, specs, market_data)
-            results = replay_backtests_device(trading_dates, rebalance_dates,
-                                              [(res[0], res[2], res[3], sp) for res, sp in zip(found, specs)], market_data,
-                                              tickers=tickers)
+            items = [(res[0], res[2], res[3], sp) for res, sp in zip(found, specs)]
+            if turnover_costs is not None:
+                return summarise_backtests_device(trading_dates, rebalance_dates, items, market_data, turnover_costs, tickers=tickers)
+            results = replay_backtests_device(trading_dates, rebalance_dates, items, market_data, tickers=tickers)
             return {sp["display_name"]: res for sp, res in zip(specs, results)}
         plan = _grid_replay_plan(specs, sizes, windows, prior_keys, mask, k)
         # universe tables: the pack's [R x k] first (a served spec holds its prefix, stride k); a patched spec's own copy after it
@@ -1830,13 +1883,19 @@ def backtest_portfolios_grid(portfolio_specs_list, ts_start_date, ts_end_date, m
                 patch_rows[q, :r.size] = r
             patches = (plan["patch_port"], plan["patch_date"], patch_rows)
         S, rf_daily, reb_day = _device_replay_inputs(trading_dates, rebalance_dates, market_data, tickers)
-        returns, turnover, metrics, rstatus, _bad_day = b.replay(
+        table = None
+        replayed = b.replay(
             _native.REPLAY_SRC_GRID_SWEEP, S, rf_daily, reb_day, len(tickers), np.array([int(sp["size"]) for sp in specs], dtype=np.int32),
             np.array([sp["risk_aversion"] if sp.get("risk_aversion") is not None else 1 for sp in specs], dtype=np.float64),
-            np.array([sp["turnover_cost"] for sp in specs], dtype=np.float64),
+            np.array([sp["turnover_cost"] if turnover_costs is None else 0.0 for sp in specs], dtype=np.float64),
             plan["w_off"], plan["w_stride"], plan["s_off"], plan["s_stride"], np.array(u_off, dtype=np.int64),
             np.array(u_stride, dtype=np.int64), np.concatenate(c_parts), np.concatenate(p_parts),
-            w_scale=plan["w_scale"], patches=patches)
+            w_scale=plan["w_scale"], patches=patches, download=turnover_costs is None)
+        if turnover_costs is not None:
+            table = _summary_table(b.dev, trading_dates, specs, market_data, turnover_costs)
+            if table is None:                                     # a replay status: which one decides what is raised, below
+                replayed = b.dev._replay_download(len(specs), len(trading_dates), R)
+        returns, turnover, metrics, rstatus, _bad_day = replayed if replayed is not None else (None, None, None, 0, None)
     finally:
         if b is not None:
             b.close()
@@ -1847,6 +1906,8 @@ def backtest_portfolios_grid(portfolio_specs_list, ts_start_date, ts_end_date, m
     if np.any(rstatus != 0):
         logger.error("Weights do not sum to 1.")
         raise ValueError("Weights do not sum to 1.")
+    if table is not None:
+        return table
     results = _device_replay_results(trading_dates, rebalance_dates, specs, returns, turnover, metrics)
     return {sp["display_name"]: res for sp, res in zip(specs, results)}
 
