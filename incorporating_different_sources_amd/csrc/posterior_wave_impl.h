@@ -278,18 +278,28 @@ struct WRows {
 //  arrive UNDEFINED and start as the table slot at `slot`, loaded behind the first two k-steps' row loads; the shifted rows
 //  are scaled by `rsc` (subtract, then multiply: a constant column stays exactly zero), column k stays zero (it holds the
 //  slot's t) and u_r goes to column k+2
-template <int NT, int NWV, int WV, bool HF, bool LEAN, bool PRE = false>
+//  TROW (one-wave kernel, !HF, LEAN: the preloaded form's edge rows; defaults to off - every other caller compiles to what it
+//  was): ONE more row behind the last, with DIFFERENT operands on the two sides - acc(I,J) += ta[I] tb[J] in row slot
+//  src.count (the centring's rank-one term, wave_window_body).  The pass is src.count + 1 slots long, so that slot is always
+//  in the LAST k-step, which is always one of the (at most three) k-steps behind the main loop; `ta` / `tb` arrive non-zero
+//  only in the lanes of that slot (fq == src.count & 3).  Those k-steps take their masked-out lanes from ta / tb instead of
+//  zero: nothing in the k-steps in front of the last (every lane holds a row), the row and zeros behind it in the last.  When
+//  src.count = 0 (mod 4) - zero rows included - the row has a k-step of its own.  Its load re-reads the last row (row 0 of
+//  the window when there is none), as the padding slots do.
+template <int NT, int NWV, int WV, bool HF, bool LEAN, bool PRE = false, bool TROW = false>
 __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&coff)[NT], int k, int lane,
                                           double (&shift)[NT], double (&w0v)[NT], bool ones, bool lazy_mask,
                                           d4 (&acc)[w2_count<NT, NWV>(WV)], const int* lds_rows, const double* lds_sub,
-                                          double (&csum)[NT], double& usum, double rsc = 1.0, const double* slot = nullptr) {
+                                          double (&csum)[NT], double& usum, double rsc = 1.0, const double* slot = nullptr,
+                                          const double* ta = nullptr, const double* tb = nullptr) {
     static_assert(!PRE || (HF && LEAN && NWV == 1), "the preloaded form exists for the one-wave kernel's intraday pass only");
+    static_assert(!TROW || (!HF && LEAN && NWV == 1 && !PRE), "the trailing row exists for the preloaded form's edge rows only");
     constexpr int kI = NT - 1;
     const int fr = lane & 15, fq = lane >> 4;
     const int kc = k - 16 * kI;
     const bool cvl = fr < kc;
     const double border = HF ? ((ones && fr == kc + 1) ? 1.0 : 0.0) : ((fr == kc) ? 1.0 : 0.0);
-    const int nks = (src.count + 3) >> 2;
+    const int nks = (src.count + (TROW ? 1 : 0) + 3) >> 2;
     const bool has_sub = !HF && src.sub_row != nullptr;
 
     // general layout: the pass's panel rows (and subtrahends) come from LDS; the values of the NEXT load are fetched right
@@ -315,6 +325,7 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
     auto load = [&](double (&v)[NT], double& sub, int ks) __attribute__((always_inline)) {
         int r = 4 * ks + fq;
         r = r < src.count ? r : src.count - 1;                      // rows past the end re-read the last row (masked below)
+        if constexpr (TROW) r = r < 0 ? 0 : r;                      // (no row at all: row 0 of the window)
         if (LEAN || src.off32) {
             unsigned row;
             if constexpr (LEAN) row = (unsigned)(r + (r >= src.count0 ? src.jump : 0));
@@ -392,6 +403,29 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
             });
         });
     };
+    // TROW: a k-step behind the main loop - lanes without a row take ta (A side) and tb (B side) in place of zero
+    [[maybe_unused]] auto step_t = [&](double (&v)[NT], double sub, int ks) __attribute__((always_inline)) {
+        if (has_sub) {
+#pragma unroll
+            for (int i = 0; i < NT; ++i) v[i] -= sub;
+        }
+        v[kI] = cvl ? v[kI] : border;
+        const bool rv = 4 * ks + fq < src.count;
+        double vt[NT];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            vt[i] = rv ? v[i] : tb[i];
+            v[i] = rv ? v[i] : ta[i];
+        }
+        static_for<0, NT>([&](auto Ic) __attribute__((always_inline)) {
+            constexpr int I = decltype(Ic)::value;
+            static_for<I, NT>([&](auto Jc) __attribute__((always_inline)) {
+                constexpr int J = decltype(Jc)::value;
+                constexpr int t = w2_slot<NT, NWV>(I, J);
+                wave_mfma_agpr<t>(acc[t], v[I], vt[J]);
+            });
+        });
+    };
 
     if constexpr (!PRE) {
         if (nks <= 0) return;
@@ -427,7 +461,12 @@ __device__ __forceinline__ void wave_gram(const WRows& src, const long long (&co
         load(vb, sb, ks + 4);
         step(vc, sc, ks + 2, ic<0>{});
     }
-    if (ks < nks) {
+    if constexpr (TROW) {
+        if (ks + 2 < nks) load(vc, sc, ks + 2);
+        step_t(va, sa, ks);
+        if (ks + 1 < nks) step_t(vb, sb, ks + 1);
+        if (ks + 2 < nks) step_t(vc, sc, ks + 2);
+    } else if (ks < nks) {
         if (ks + 2 < nks) load(vc, sc, ks + 2);
         step(va, sa, ks, ic<1>{});
         if (ks + 1 < nks) step(vb, sb, ks + 1, ic<1>{});
@@ -459,9 +498,11 @@ __device__ __forceinline__ void wave_stage_rows(const WRows& src, int lane, int*
 // on the multi-wave kernel (wave_mode / launch_one).
 // PRE (plain conjugate, LEAN, a batch with shared tables, kc <= 13; wave_launch_variant decides): the accumulators START as
 // the window's table slot Q_L[b0] (wave_gram, PRE), the intraday rows are accumulated on top of it already scaled by
-// sqrt(sc), the rank-one term of the centring is one more k-step of MFMAs, and only tile column kI visits the VGPR half
-// between the row loops - no pass over all tiles (phase C) and no table addition (phase D).  Columns: k the slot's t, k+1
-// ones, k+2 u.  Windows of such a batch without a slot of their own start from the tables' all-zero slot.
+// sqrt(sc), and the rank-one term of the centring is ONE row behind the last daily edge row, in that pass's last k-step
+// (wave_gram, TROW): between the row loops only the term's operands are read out of tile column kI (phase C), and the border
+// pass over that tile column (q0, c, column k += c column k+2) follows the edge rows - no pass over all tiles and no table
+// addition.  Columns: k the slot's t, k+1 ones, k+2 u.  Windows of such a batch without a slot of their own start from the
+// tables' all-zero slot.
 template <int NT, bool LEAN, int MODE, bool PRE = false>
 __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* lds) {
     static_assert(!PRE || (LEAN && (MODE == 0 || MODE == 3)), "preloaded accumulators: plain conjugate, contiguous layout");
@@ -592,6 +633,8 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
             ds.count0 = shared ? c0 : 0x7fffffff;
             ds.jump = shared ? (int)(BLK * b1 - ds.first) - c0 : 0;
             ds.count = shared ? c0 + (int)(ds.first + ds.count - BLK * b1) : ds.count;
+            // no edge row at all: the centring row's load re-reads row 0 of the window, not the row behind its last block
+            ds.count0 = ds.count > 0 ? ds.count0 : 0x7fffffff;
             q = shared ? A.winsum + ((long long)li * A.prefix_nblk + b0) * ((long long)C::NTILES * 256) : A.winsum_zero;
         }
         // ---- phase A: the shift row (the window's first intraday row), w0
@@ -616,9 +659,11 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
         hs.first += 1; hs.count -= 1;
         wave_gram<NT, 1, 0, true, true, true>(hs, coff, k, lane, shift, w0v, true, true, acc, nullptr, nullptr, csum, usum, rsc, q);
         TP_MARK(2);
-        // ---- phase C: the rank-one term of the centring as ONE k-step, acc(I,J) += (-tau_I / m) tau_J in row 0 of the step.
-        // tau = column k+1 (sqrt(sc) sums of the shifted rows) over the asset rows, zero at k and k+1, and at k+2 the
-        // sum of u - element (k+1, k+2).  Afterwards column k+2 is sc C w0 and element (k+2, k+2) is q0.
+        // ---- phase C: tau, the operands of the centring's rank-one term acc(I,J) += (-tau_I / m) tau_J, handed over through
+        // OFF_VEC.  tau = column k+1 (sqrt(sc) sums of the shifted rows) over the asset rows, zero at k and k+1, and at k+2 the
+        // sum of u - element (k+1, k+2).  The term itself rides in the edge rows' last k-step (wave_gram, TROW): the edge rows
+        // are zero at k+1 and k+2 and tau is zero at k and k+1, so the two touch no common element but the asset block, where
+        // they only add.  Behind phase D column k+2 is sc C w0 and element (k+2, k+2) is q0.
         static_for<0, NT>([&](auto Ic) __attribute__((always_inline)) {
             constexpr int I = decltype(Ic)::value;
             constexpr int t = wtile(NT, I, kI);
@@ -638,24 +683,26 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
         });
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
+        // the row slot behind the last edge row: slot ds.count, lanes fq == ds.count & 3 of the pass's last k-step
+        double ta[NT], tb[NT];
         {
-            double ta[NT], tb[NT];
+            const int tq = ds.count & 3;
 #pragma unroll
             for (int J = 0; J < NT; ++J) {
                 const double tv = lds[C::OFF_VEC + 16 * J + fr];
-                tb[J] = fq == 0 ? tv : 0.0;
-                ta[J] = fq == 0 ? -(tv * invm) : 0.0;
+                tb[J] = fq == tq ? tv : 0.0;
+                ta[J] = fq == tq ? -(tv * invm) : 0.0;
             }
-            static_for<0, NT>([&](auto Ic) __attribute__((always_inline)) {
-                constexpr int I = decltype(Ic)::value;
-                static_for<I, NT>([&](auto Jc) __attribute__((always_inline)) {
-                    constexpr int J = decltype(Jc)::value;
-                    constexpr int t = wtile(NT, I, J);
-                    wave_mfma_agpr<t>(acc[t], ta[I], tb[J]);
-                });
-            });
-            wave_settle<true>(acc);
         }
+        TP_MARK(3);
+        // ---- phase D: the daily edge rows (ref:180), ones in the border column (t, ref:222), and the centring row behind
+        // them; the whole blocks came with the slot
+        TP_MARK(32);
+        double none[NT] = {};
+        double nosum = 0.0;
+        wave_gram<NT, 1, 0, false, true, false, true>(ds, coff, k, lane, none, none, false, false, acc, nullptr, nullptr, none, nosum,
+                                                      1.0, nullptr, ta, tb);
+        TP_MARK(33);
         // scalars (ref:415-418): q0 = w0'S0 w0 is the element (k+2, k+2) - all four registers read, see `corner`
         {
             constexpr int t = wtile(NT, kI, kI);
@@ -666,7 +713,11 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
             const int rr = kx >> 2;
             q0 = rr == 0 ? x0 : rr == 1 ? x1 : rr == 2 ? x2 : x3;
         }
-        const double a = n0 + k + 2;
+        // (k through an opaque scalar copy: merged with phase H's own conversion of k, the double lived in a VGPR pair across
+        // the whole factorisation - and was spilled, 12 bytes of scratch at seven tiles per side)
+        int kq = k;
+        asm("" : "+s"(kq));
+        const double a = n0 + kq + 2;
         cc = (2 * n0) / (a + sqrt(a * a + 4 * n0 * q0));
         // border pass, tile column kI only: column k (the slot's t) += c * column k+2 (two lanes up in the row group),
         // columns beyond k cleared
@@ -683,13 +734,6 @@ __device__ __forceinline__ void wave_window_body(const tp_kargs_t& A, double* ld
             wave_pin1<t>(acc[t]);
         });
         __builtin_amdgcn_sched_barrier(0);
-        TP_MARK(3);
-        // ---- phase D: the daily edge rows (ref:180), ones in the border column (t, ref:222); the whole blocks came with the slot
-        TP_MARK(32);
-        double none[NT] = {};
-        double nosum = 0.0;
-        wave_gram<NT, 1, 0, false, true>(ds, coff, k, lane, none, none, false, false, acc, nullptr, nullptr, none, nosum);
-        TP_MARK(33);
     } else {
     if (conj && dbg != 2) {
         n0 = A.n0[w];
@@ -1209,6 +1253,8 @@ __global__ void __launch_bounds__(64, wave_occupancy(NT)) posterior_wave_kernel_
 // profiles/r19_wave_preload_bench.txt).  It pays where the form with the two passes over the tiles spills - 5 tiles per side
 // (k = 77: -15 %), 7 (k = 100: -3 %), 8 and 9 (k = 120, 140: -21 %, -23 %) - and is +- 0 where neither form spills (k = 55,
 // 90: 4 and 6 tiles); 1 to 3 tiles per side were not measured.  wave_preload = 1 runs it wherever the batch is eligible.
+// With the centring row inside the edge rows' last k-step (profiles/r26_centring_row_bench.txt) wave_preload = 1 gains 1.7 %
+// and 1.9 % at 4 and 6 tiles per side as well; the automatic choice there is left as it was until the suite has run on it.
 constexpr bool wave_preload_pays(int nt) { return nt == 5 || nt >= 7; }
 template <int NT>
 inline bool wave_preload_eligible(const tp_kargs_t& a) {

@@ -30,6 +30,11 @@ st = st[:, :8]
 d = np.diff(st, axis=1).astype(np.float64)
 names = ["A means", "B hf gram", "C scale", "D daily gram", "F cholesky", "G backsolve", "H output"]
 tot = (st[:, 7] - st[:, 0]).astype(np.float64)
+# the one-wave kernel's preloaded form (plain conjugate batches with shared tables, option wave_preload) keeps the marks
+# but fills the phases differently
+print("one-wave preloaded form, if that is what ran: B = slot + scaled intraday rows; C = hand-over of the centring's "
+      "operands (tau) only; D = edge rows with the centring row in their last k-step (split below: 'edge rows'), then "
+      "q0, c and the border pass over tile column kI (split below: 'table slot')")
 print(f"per-window wall (s_memtime ticks @100MHz): median {np.median(tot):.0f} ticks = {np.median(tot)*10:.0f} ns")
 for i, n in enumerate(names):
     print(f"  {n:14s} median {np.median(d[:, i]):8.0f} ticks  share {np.median(d[:, i]) / np.median(tot) * 100:5.1f}%")
