@@ -295,6 +295,50 @@ int tp_batch_download_sweep(tp_batch_t b, double* x, int32_t* status);
  * sweep solved for them (tp_batch_download_rhs keeps answering for the last tp_batch_run).  Waits like
  * tp_batch_download_sweep; without a sweep before it: TP_ERR_INVALID. */
 int tp_batch_download_sweep_rhs(tp_batch_t b, double* rhs_out);
+/* Sweep finish: the Greyserman (ref:928-931) or Jorion (ref:880-893) weights from the solutions the batch's LAST solve sweep
+ * of either kind left on the device - no download of the W x S x 2 x k solutions; the results [W x k] stay on the device, where
+ * tp_replay_run_batch reads them (TP_REPLAY_SRC_SWEEP_FINISH).  The sweep must have had R = 2: default_rhs (slot 0, u_t = M^-1 t)
+ * and ONE caller column (slot 1, u_one), which MUST be the ones vector - the call cannot see that it is.  The batch must have
+ * been created with gamma = 1 (the sweep divides by the batch's gamma; the finish takes `gamma` itself).
+ * Definitions, all in double, ONE rounding per operation, in this order.  For window w and shift s, with u_one, u_t the two
+ * solution rows, t the sweep's default right-hand side (tp_batch_download_sweep_rhs), N = k:
+ *   s1 = sum_j u_one_j,  s2 = sum_j u_t_j,  s3 = sum_j fl(t_j u_t_j): lane l of a wavefront adds its columns l, l + 64, ... in
+ *     ascending order starting from 0, then the 64 partials go through a fixed tree (rotations by 8, 4, 2, 1 inside each row of
+ *     16 lanes, then (r0 + r1) + (r2 + r3) over the four rows).
+ *   TP_FINISH_GREYSERMAN, with n = n[w], kappa = kappa[w], (xi, eta) = hyper[w][s]:
+ *     beta = eta / 2 + kappa (xi xi);  K11 = 1 / beta + s1;  K12 = s2 - (kappa xi) / beta;
+ *     K22 = (s3 - n) - (kappa eta) / (2 beta);  det = K11 K22 - K12 K12;
+ *     c = ((1 / gamma) ((N + n) + 1)) (1 - 1 / n);  cA = c (K12 / det);  cB = c (K11 / det);
+ *     term_sj = cA u_one_sj - cB u_t_sj.
+ *   TP_FINISH_JORION (S = 1), with T = n[w]:
+ *     kJ = (((T - N) - 2) (T - 1)) / T;  s_bb = kJ s1;  s_ab = (kJ s2) / T;  s_aa = (kJ s3) / (T T);  mu_g = s_ab / s_bb;
+ *     q = (s_aa - (2 mu_g) s_ab) + (mu_g mu_g) s_bb;  lam = (N + 2) / q;  v = (N + 2) / ((N + 2) + T q);
+ *     alpha = 1 + 1 / (T + lam);  beta = (lam / (T ((T + 1) + lam))) / s_bb;  g = (1 - v) s_ab + (v mu_g) s_bb;
+ *     cT = (((1 - v) kJ) / T) / alpha;  cO = ((v mu_g) kJ) / alpha;  cS = (((beta / (alpha alpha)) kJ) g) / (1 + (beta / alpha) s_bb);
+ *     term_sj = ((cT u_t_j + cO u_one_j) - cS u_one_j) / gamma.
+ *   weights[w][j] = (sum over the groups of TP_FINISH_DRAWS_PER_WAVE consecutive shifts, in ascending order, of (the group's terms
+ *     added in ascending s starting from 0)) / S.  The grouping and every order depend on (k, S) only: a window's weights are the
+ *     same bit for bit whatever W, its position, or the sub-ranges of the sweep that fed it, and from run to run.
+ * status[w]: the first status of the sweep's shifts s = 0, 1, ... of the window that is not TP_STATUS_OK - the weights row is
+ * then NaN -; else TP_STATUS_NONFINITE when a weight of the row is not finite (beta = 0, det = 0, q = 0 end here); else
+ * TP_STATUS_OK.  aux[w][s] = (s1, s2, s3, det) - Jorion: (s1, s2, s3, q) -, NaN for a shift the sweep flagged.
+ * TP_ERR_INVALID, all checked before anything is waited for, uploaded or queued (a refused call leaves the last finish in place):
+ * an unknown mode; no solve sweep yet; a last sweep that was not R = 2 with default_rhs; a batch gamma other than 1;
+ * TP_FINISH_JORION with S != 1; a NULL n - TP_FINISH_GREYSERMAN: kappa, hyper - with W > 0; a non-finite n, kappa, xi or eta; a
+ * gamma that is 0 or not finite.  kappa and hyper are not read by TP_FINISH_JORION and may be NULL.
+ * The call waits on entry for whatever is queued on the handle's stream - the sweep ends here -, uploads n, kappa and hyper (HOST
+ * pointers, not kept) and queues two launches inside one timed span without waiting for them: kernel_ms, one step of
+ * tp_region_steps; tp_last_launch keeps describing tp_batch_run.  The sweep's solutions are not written.  Buffers (the results,
+ * W x ceil(S / TP_FINISH_DRAWS_PER_WAVE) x k doubles of partial sums and the uploaded scalars) are kept until tp_batch_destroy.
+ * A later tp_batch_solve_sweep[_tiled] that gets as far as its drain replaces the solutions: the finish is then no longer valid,
+ * tp_batch_download_sweep_finish and TP_REPLAY_SRC_SWEEP_FINISH are refused (TP_ERR_INVALID, the message says why). */
+#define TP_FINISH_GREYSERMAN 0
+#define TP_FINISH_JORION     1
+#define TP_FINISH_DRAWS_PER_WAVE 16
+int tp_batch_sweep_finish(tp_batch_t b, int mode, double gamma, const double* n /* [W] */,
+                          const double* kappa /* [W], Greyserman */, const double* hyper /* [W x S x 2] = (xi, eta), Greyserman */);
+/* Waits for the finish and copies out weights [W x k], status [W] and aux [W x S x 4]; each may be NULL. */
+int tp_batch_download_sweep_finish(tp_batch_t b, double* weights /* [W x k] */, int32_t* status /* [W] */, double* aux /* [W x S x 4] */);
 /* Prior sweep: many conjugate priors (n0, w0) per window from ONE pair of Grams - a grid of conjugate specs over the same
  * rebalancing dates (VIX / EPU x vw / ew x mcm_scaling, ref:247-267, 361-380) without a replica of every window per spec.
  * With C = sum (y - ybar)(y - ybar)' the centred intraday scatter of window w, T = X'X, t = X'1, m the window's own
@@ -698,6 +742,7 @@ int tp_replay_run(tp_handle_t h, int64_t D, int32_t ld, const double* S /* [D x 
 #define TP_REPLAY_SRC_SIZE_SWEEP   2  /* tp_batch_size_sweep[_tiled]:   [W x P x S x k],              [W x P x S]           */
 #define TP_REPLAY_SRC_WINDOW_SWEEP 3  /* tp_batch_window_sweep[_tiled]: [W x P x L x k],              [W x P x L]           */
 #define TP_REPLAY_SRC_GRID_SWEEP   4  /* tp_batch_grid_sweep[_tiled]:   [W x P x L x S x k],          [W x P x L x S]       */
+#define TP_REPLAY_SRC_SWEEP_FINISH 5  /* tp_batch_sweep_finish:         weights [W x k],              status [W]            */
 #define TP_REPLAY_BAD_WEIGHTS 2       /* status[p]: a weight row was read whose source status was not TP_STATUS_OK */
 int tp_replay_run_batch(tp_batch_t b, int source,
                         int64_t D, int32_t ld, const double* S, const double* rf_daily,

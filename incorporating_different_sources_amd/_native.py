@@ -39,6 +39,9 @@ REPLAY_SUM_CHECK = 1
 REPLAY_BAD_WEIGHTS = 2
 REPLAY_METRICS = 5
 REPLAY_SRC_RUN, REPLAY_SRC_PRIOR_SWEEP, REPLAY_SRC_SIZE_SWEEP, REPLAY_SRC_WINDOW_SWEEP, REPLAY_SRC_GRID_SWEEP = 0, 1, 2, 3, 4
+REPLAY_SRC_SWEEP_FINISH = 5
+FINISH_GREYSERMAN, FINISH_JORION = 0, 1
+FINISH_DRAWS_PER_WAVE = 16        # TP_FINISH_DRAWS_PER_WAVE: consecutive shifts of one window per wavefront of `sweep_finish`
 SUMMARY_STATS = 32
 SUMMARY_MAX_COSTS = 64
 SUMMARY_OK, SUMMARY_NO_REPLAY, SUMMARY_NONFINITE = 0, 1, 2
@@ -54,6 +57,7 @@ EXPORTS = [
     "tp_host_alloc", "tp_host_free", "tp_batch_set_rhs", "tp_batch_set_shift", "tp_batch_keep_rhs",
     "tp_batch_download_rhs", "tp_batch_keep_posterior", "tp_batch_download_posterior", "tp_batch_run", "tp_batch_download", "tp_batch_download_S1", "tp_batch_download_matrix",
     "tp_batch_solve_sweep", "tp_batch_solve_sweep_tiled", "tp_batch_download_sweep", "tp_batch_download_sweep_rhs",
+    "tp_batch_sweep_finish", "tp_batch_download_sweep_finish",
     "tp_batch_prior_sweep", "tp_batch_prior_sweep_tiled", "tp_batch_download_prior_sweep",
     "tp_batch_size_sweep", "tp_batch_size_sweep_tiled", "tp_batch_download_size_sweep",
     "tp_batch_window_sweep", "tp_batch_window_sweep_tiled", "tp_batch_download_window_sweep",
@@ -131,6 +135,8 @@ def _load():
     lib.tp_batch_solve_sweep_tiled.argtypes = [c_void_p, c_int32, POINTER(c_double), c_int32, POINTER(c_double), c_int32]
     lib.tp_batch_download_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32)]
     lib.tp_batch_download_sweep_rhs.argtypes = [c_void_p, POINTER(c_double)]
+    lib.tp_batch_sweep_finish.argtypes = [c_void_p, c_int, c_double, POINTER(c_double), POINTER(c_double), POINTER(c_double)]
+    lib.tp_batch_download_sweep_finish.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_prior_sweep.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     lib.tp_batch_prior_sweep_tiled.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     lib.tp_batch_download_prior_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
@@ -769,22 +775,23 @@ class Batch:
         self.dev._check(lib.tp_batch_run(self._b))
         return self
 
-    def solve_sweep(self, shift=None, rhs=None, default_rhs=True, out=None):
+    def solve_sweep(self, shift=None, rhs=None, default_rhs=True, out=None, download=True):
         """`tp_batch_solve_sweep` + `tp_batch_download_sweep`: x[w, s, r] = (M_w + d_ws I + e_ws 1 1')^-1 rhs_wr / gamma
         from ONE Gram pass, for `shift` [W x S x 2] = (d, e) (Jeffreys only; None: one unshifted solve) and the
         right-hand sides `rhs` [W x n x k] (a [W x k] array is one column), behind the window's own right-hand side when
         `default_rhs`.  Returns (x [W, S, R, k], status [W, S]).  `out=(x, status)`: write into these arrays (e.g.
-        `pinned_empty`).  The batch's results, settings and kept arrays are left alone."""
-        return self._solve_sweep(lib.tp_batch_solve_sweep, shift, rhs, default_rhs, out)
+        `pinned_empty`).  The batch's results, settings and kept arrays are left alone.  `download=False`: the sweep is queued
+        and None returned - the solutions stay on the device for `sweep_finish` (or a later `download_sweep_rhs`)."""
+        return self._solve_sweep(lib.tp_batch_solve_sweep, shift, rhs, default_rhs, out, download)
 
-    def solve_sweep_tiled(self, shift=None, rhs=None, default_rhs=True, out=None):
+    def solve_sweep_tiled(self, shift=None, rhs=None, default_rhs=True, out=None, download=True):
         """`tp_batch_solve_sweep_tiled` + `tp_batch_download_sweep`: `solve_sweep` for k above `sweep_max_assets()`, every
         (window, shift) pair factorised once by the large-k tiled pipeline with the R right-hand sides riding along as
         columns k .. k+R-1 of the arena (smaller k, or k + R > max_assets() + 1: TP_ERR_UNSUPPORTED).  Same arguments,
         shape checks and return values; `download_sweep_rhs` serves both calls."""
-        return self._solve_sweep(lib.tp_batch_solve_sweep_tiled, shift, rhs, default_rhs, out)
+        return self._solve_sweep(lib.tp_batch_solve_sweep_tiled, shift, rhs, default_rhs, out, download)
 
-    def _solve_sweep(self, call, shift, rhs, default_rhs, out):
+    def _solve_sweep(self, call, shift, rhs, default_rhs, out, download=True):
         W, k = self.W, self.k
         sh = None
         S = 1
@@ -806,6 +813,13 @@ class Batch:
         R = (1 if default_rhs else 0) + n_rhs
         if R < 1 or R > SWEEP_MAX_RHS:
             raise ValueError(f"{R} right-hand sides per window: between 1 and {SWEEP_MAX_RHS} expected")
+        if not download:
+            if out is not None:
+                raise ValueError("out: nothing is downloaded with download=False")
+            self.dev._check(call(self._b, S if sh is not None else 0, _ptr(sh, c_double), n_rhs,
+                                 _ptr(r if n_rhs else None, c_double), 1 if default_rhs else 0))
+            self._sweep_S, self._sweep_R = S, R
+            return None
         if out is not None:
             x, status = out
             if x.shape != (W, S, R, k) or x.dtype != np.float64 or not x.flags.c_contiguous:
@@ -817,9 +831,64 @@ class Batch:
             status = np.empty((W, S), dtype=np.int32)
         self.dev._check(call(self._b, S if sh is not None else 0, _ptr(sh, c_double), n_rhs,
                              _ptr(r if n_rhs else None, c_double), 1 if default_rhs else 0))
+        self._sweep_S, self._sweep_R = S, R
         self.dev._check(lib.tp_batch_download_sweep(self._b, _ptr(x if x.size else None, c_double),
                                                     _ptr(status if status.size else None, c_int32)))
         return x, status
+
+    def download_sweep(self):
+        """(x [W, S, R, k], status [W, S]) of the last `solve_sweep` / `solve_sweep_tiled`, e.g. one queued with
+        `download=False`; the shape is that sweep's."""
+        S, R = getattr(self, "_sweep_S", 0), getattr(self, "_sweep_R", 0)
+        if S < 1 or R < 1:
+            raise ValueError("download_sweep: no solve sweep of this batch yet")
+        x = np.empty((self.W, S, R, self.k), dtype=np.float64)
+        status = np.empty((self.W, S), dtype=np.int32)
+        self.dev._check(lib.tp_batch_download_sweep(self._b, _ptr(x if x.size else None, c_double),
+                                                    _ptr(status if status.size else None, c_int32)))
+        return x, status
+
+    def sweep_finish(self, mode, n, gamma, kappa=None, xi=None, eta=None):
+        """`tp_batch_sweep_finish`: the Greyserman (`FINISH_GREYSERMAN`: `n` [W], `kappa` [W], `xi` and `eta` [W x S]) or
+        Jorion (`FINISH_JORION`: `n` [W] = the windows' row counts, S = 1) weights from the solutions the last
+        `solve_sweep` / `solve_sweep_tiled` of this batch left on the device - R = 2: `default_rhs=True` and ONE caller
+        column, which must be the ones vector; the batch created with gamma = 1, `gamma` is the finish's own.  Nothing comes
+        down: `download_sweep_finish` fetches [W x k], `replay(REPLAY_SRC_SWEEP_FINISH, ...)` reads them where they lie.
+        Shapes are checked here; the library refuses the rest (TangencyError, code ERR_INVALID) before it queues anything."""
+        W = self.W
+        mode = int(mode)
+        nn = np.ascontiguousarray(n, dtype=np.float64)
+        if nn.shape != (W,):
+            raise ValueError(f"n: expected shape ({W},), got {tuple(nn.shape)}")
+        ka = hy = None
+        if mode == FINISH_GREYSERMAN:
+            if kappa is None or xi is None or eta is None:
+                raise ValueError("sweep_finish(FINISH_GREYSERMAN): kappa, xi and eta are needed")
+            ka = np.ascontiguousarray(kappa, dtype=np.float64)
+            x_, e_ = np.asarray(xi, dtype=np.float64), np.asarray(eta, dtype=np.float64)
+            if ka.shape != (W,):
+                raise ValueError(f"kappa: expected shape ({W},), got {tuple(ka.shape)}")
+            if x_.ndim != 2 or x_.shape[0] != W or e_.shape != x_.shape:
+                raise ValueError(f"xi, eta: expected one shape ({W}, S), got {tuple(x_.shape)} and {tuple(e_.shape)}")
+            if x_.shape[1] != getattr(self, "_sweep_S", x_.shape[1]):
+                raise ValueError(f"xi, eta: {x_.shape[1]} draws per window, the last sweep had {self._sweep_S} shifts")
+            hy = np.ascontiguousarray(np.stack([x_, e_], axis=2))
+        self.dev._check(lib.tp_batch_sweep_finish(self._b, mode, float(gamma), _ptr(nn if nn.size else None, c_double),
+                                                  _ptr(ka if ka is not None and ka.size else None, c_double),
+                                                  _ptr(hy if hy is not None and hy.size else None, c_double)))
+        self._finish_S = getattr(self, "_sweep_S", 1)
+        return self
+
+    def download_sweep_finish(self, want_aux=False):
+        """(weights [W x k], status [W], aux [W x S x 4] or None) of the last `sweep_finish`: aux[w, s] = (1'u_one, 1'u_t,
+        t'u_t, det K) - Jorion: q in the fourth slot."""
+        weights = np.empty((self.W, self.k), dtype=np.float64)
+        status = np.empty(self.W, dtype=np.int32)
+        aux = np.empty((self.W, getattr(self, "_finish_S", 1), 4), dtype=np.float64) if want_aux else None
+        self.dev._check(lib.tp_batch_download_sweep_finish(self._b, _ptr(weights if weights.size else None, c_double),
+                                                           _ptr(status if status.size else None, c_int32),
+                                                           _ptr(aux if aux is not None and aux.size else None, c_double)))
+        return weights, status, aux
 
     def download_sweep_rhs(self) -> np.ndarray:
         """[W x k] default right-hand sides (t = X'1, or c S0 w0 + t) the Gram pass of the last `solve_sweep` /

@@ -22,6 +22,7 @@
 
 #include "backtest_replay.h"
 #include "replay_summary.h"
+#include "sweep_finish.h"
 
 #define TP_REGION_MAX_STEPS 512
 
@@ -101,6 +102,12 @@ struct SolveSweepWs {
     DevBuf arena, rinv, flags;
     DevBuf part;                    // tp_batch_size_sweep_tiled borrows that workspace (R = n_size): pieces of its prior products
     int S = 0, R = 0;               // shape of the last sweep (0: none yet)
+    bool default_rhs = false;       // the last sweep solved for the default right-hand side (slot 0 of its R columns)
+    // tp_batch_sweep_finish (sweep_finish.hip): the uploaded scalars n [W], kappa [W] and (xi, eta) [W x S x 2], the groups'
+    // partial sums [W x NG x k] and statuses [W x NG], and the results weights [W x k], status [W], aux [W x S x 4]
+    DevBuf fin_n, fin_kappa, fin_hyper, fin_part, fin_gstatus, fin_weights, fin_status, fin_aux;
+    bool finished = false;          // a finish of the LAST sweep completed its launches (a new sweep clears it)
+    bool finish_stale = false;      // there was a finish, and a later sweep replaced the solutions it read
 };
 
 // Prior sweeps (`ps`) and the size sweep (`zs`): one type, two instances - a size sweep must not disturb what

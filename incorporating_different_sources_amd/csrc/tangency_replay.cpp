@@ -316,6 +316,13 @@ int tp_replay_run_batch(tp_batch_t b, int source, int64_t D, int32_t ld, const d
             producer = "tp_batch_grid_sweep";
             feed.src_weights = (const double*)b->gr.weights.p; feed.src_status = (const int32_t*)b->gr.status.p;
             break;
+        case TP_REPLAY_SRC_SWEEP_FINISH:
+            if (b->sw.finish_stale)
+                return fail(h, TP_ERR_INVALID, "%s: a solve sweep after the last tp_batch_sweep_finish replaced the solutions it read "
+                            "(source %d)", name, source);
+            per_window = b->sw.finished ? 1 : 0; producer = "tp_batch_sweep_finish";
+            feed.src_weights = (const double*)b->sw.fin_weights.p; feed.src_status = (const int32_t*)b->sw.fin_status.p;
+            break;
         default:
             return fail(h, TP_ERR_INVALID, "%s: unknown source %d", name, source);
     }

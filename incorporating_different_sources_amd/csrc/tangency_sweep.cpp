@@ -159,6 +159,8 @@ int solve_sweep_prepare(tp_batch_t b, const char* name, bool tiled, int32_t n_sh
     rc = drain_for_sweep(b);
     if (rc != TP_OK) return rc;
     ws.S = 0; ws.R = 0;
+    if (ws.finished) { ws.finished = false; ws.finish_stale = true; }   // (a finish read the solutions about to be replaced)
+    ws.default_rhs = default_rhs != 0;
     *S_out = S; *R_out = (int)R;
     if (W == 0) { ws.S = S; ws.R = (int)R; return TP_OK; }
     const size_t mat_bytes = sizeof(double) * (size_t)k * k;
@@ -586,6 +588,102 @@ int tp_batch_download_sweep_rhs(tp_batch_t b, double* rhs_out) {
     HIP_TRY(h, hipSetDevice(h->device));
     if (b->W > 0 && !rhs_out) return fail(h, TP_ERR_INVALID, "tp_batch_download_sweep_rhs: rhs_out is NULL");
     return download(h, {{rhs_out, b->sw.rhs0.p, sizeof(double) * (size_t)b->W * b->p.k}});
+}
+
+// Sweep finish (sweep_finish.hip): the Greyserman / Jorion weights from the solutions the last solve sweep of either kind left
+// in sw.x.  Every check comes before the drain; the two launches share one timed span and are not awaited.
+int tp_batch_sweep_finish(tp_batch_t b, int mode, double gamma, const double* n, const double* kappa, const double* hyper) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    SolveSweepWs& sw = b->sw;
+    const char* name = "tp_batch_sweep_finish";
+    const int k = b->p.k;
+    const int64_t W = b->W;
+    if (mode != TP_FINISH_GREYSERMAN && mode != TP_FINISH_JORION) return fail(h, TP_ERR_INVALID, "%s: unknown mode %d", name, mode);
+    const bool grey = mode == TP_FINISH_GREYSERMAN;
+    if (sw.S < 1 || sw.R < 1) return fail(h, TP_ERR_INVALID, "%s: no tp_batch_solve_sweep before it", name);
+    if (sw.R != 2 || !sw.default_rhs)
+        return fail(h, TP_ERR_INVALID, "%s: the last sweep solved %d right-hand sides %s the default one: R = 2, the default right-hand side "
+                    "and one caller column (the ones vector), is expected", name, sw.R, sw.default_rhs ? "with" : "without");
+    if (b->p.gamma != 1.0)
+        return fail(h, TP_ERR_INVALID, "%s: the batch's gamma is %g: the sweep has divided its solutions by it already, a batch created "
+                    "with gamma = 1 is expected", name, b->p.gamma);
+    if (!grey && sw.S != 1)
+        return fail(h, TP_ERR_INVALID, "%s: TP_FINISH_JORION takes one shift per window, the last sweep had S=%d", name, sw.S);
+    if (!std::isfinite(gamma) || gamma == 0.0) return fail(h, TP_ERR_INVALID, "%s: gamma=%g must be finite and not 0", name, gamma);
+    const int S = sw.S;
+    const int64_t NG = (S + TP_FINISH_DRAWS_PER_WAVE - 1) / TP_FINISH_DRAWS_PER_WAVE;
+    if (k > 64 * TP_FINISH_MAX_SLOTS) return fail(h, TP_ERR_UNSUPPORTED, "%s: k=%d exceeds %d", name, k, 64 * TP_FINISH_MAX_SLOTS);
+    if (W > 0x7fffffffLL / NG) return fail(h, TP_ERR_UNSUPPORTED, "%s: W=%lld windows x %lld groups of shifts exceed 2^31", name, (long long)W, (long long)NG);
+    if (W > 0) {
+        if (!n) return fail(h, TP_ERR_INVALID, "%s: n is NULL", name);
+        if (grey && (!kappa || !hyper)) return fail(h, TP_ERR_INVALID, "%s: kappa or hyper is NULL (TP_FINISH_GREYSERMAN)", name);
+        for (int64_t w = 0; w < W; ++w) {
+            if (!std::isfinite(n[w])) return fail(h, TP_ERR_INVALID, "%s: n[%lld] is not finite", name, (long long)w);
+            if (grey && !std::isfinite(kappa[w])) return fail(h, TP_ERR_INVALID, "%s: kappa[%lld] is not finite", name, (long long)w);
+        }
+        if (grey)
+            for (int64_t e = 0; e < W * S; ++e)
+                if (!std::isfinite(hyper[2 * e]) || !std::isfinite(hyper[2 * e + 1]))
+                    return fail(h, TP_ERR_INVALID, "%s: (xi, eta) of window %lld, shift %lld is not finite", name, (long long)(e / S), (long long)(e % S));
+    }
+    // ---- device: drain (the sweep ends here; its span is read), upload, two launches that are not awaited
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int rc = harvest_kernel_time(h);
+    if (rc != TP_OK) return rc;
+    sw.finished = false;
+    sw.finish_stale = false;
+    const size_t Wz = (size_t)W;
+    rc = ensure(h, sw.fin_n, sizeof(double) * Wz, "tp_batch_sweep_finish: n");
+    if (rc == TP_OK && grey) rc = ensure(h, sw.fin_kappa, sizeof(double) * Wz, "tp_batch_sweep_finish: kappa");
+    if (rc == TP_OK && grey) rc = ensure(h, sw.fin_hyper, sizeof(double) * 2 * Wz * S, "tp_batch_sweep_finish: (xi, eta)");
+    if (rc == TP_OK) rc = ensure(h, sw.fin_part, sizeof(double) * Wz * (size_t)NG * k, "tp_batch_sweep_finish: partial sums");
+    if (rc == TP_OK) rc = ensure(h, sw.fin_gstatus, sizeof(int32_t) * Wz * (size_t)NG, "tp_batch_sweep_finish: group statuses");
+    if (rc == TP_OK) rc = ensure(h, sw.fin_weights, sizeof(double) * Wz * k, "tp_batch_sweep_finish: weights");
+    if (rc == TP_OK) rc = ensure(h, sw.fin_status, sizeof(int32_t) * Wz, "tp_batch_sweep_finish: statuses");
+    if (rc == TP_OK) rc = ensure(h, sw.fin_aux, sizeof(double) * 4 * Wz * S, "tp_batch_sweep_finish: aux");
+    if (rc != TP_OK) return rc;
+    if (W > 0) {
+        HIP_TRY(h, hipMemcpyAsync(sw.fin_n.p, n, sizeof(double) * Wz, hipMemcpyHostToDevice, h->stream));
+        if (grey) {
+            HIP_TRY(h, hipMemcpyAsync(sw.fin_kappa.p, kappa, sizeof(double) * Wz, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(sw.fin_hyper.p, hyper, sizeof(double) * 2 * Wz * S, hipMemcpyHostToDevice, h->stream));
+        }
+        HIP_TRY(h, hipStreamSynchronize(h->stream));      // the host arrays are free again
+    }
+    tp_finish_args_t a;
+    memset(&a, 0, sizeof a);
+    a.x = (const double*)sw.x.p; a.xstatus = (const int*)sw.xstatus.p; a.t = (const double*)sw.rhs0.p;
+    a.n = (const double*)sw.fin_n.p; a.kappa = (const double*)sw.fin_kappa.p; a.hyper = (const double*)sw.fin_hyper.p;
+    a.part = (double*)sw.fin_part.p; a.gstatus = (int*)sw.fin_gstatus.p;
+    a.weights = (double*)sw.fin_weights.p; a.status = (int*)sw.fin_status.p; a.aux = (double*)sw.fin_aux.p;
+    a.gamma = gamma;
+    a.W = (int)W; a.S = S; a.k = k; a.mode = grey ? TP_FINISH_KMODE_GREYSERMAN : TP_FINISH_KMODE_JORION;
+    const tp_launch_info_t keep_launch = h->last_launch;  // tp_last_launch keeps describing tp_batch_run
+    Span& span = timed_span(h);
+    HIP_TRY(h, span.begin(h->stream));
+    rc = launched(h, tp_finish_launch(a, h->stream), "sweep finish kernel");
+    h->last_launch = keep_launch;
+    if (rc == TP_OK) rc = timed_done(h, span);
+    if (rc != TP_OK) return rc;
+    sw.finished = true;
+    return TP_OK;
+}
+
+int tp_batch_download_sweep_finish(tp_batch_t b, double* weights, int32_t* status, double* aux) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    const SolveSweepWs& sw = b->sw;
+    if (!sw.finished)
+        return fail(h, TP_ERR_INVALID, sw.finish_stale
+                        ? "tp_batch_download_sweep_finish: a solve sweep after the last tp_batch_sweep_finish replaced the solutions it read"
+                        : "tp_batch_download_sweep_finish: no tp_batch_sweep_finish before it");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t W = (size_t)b->W;
+    return download(h, {{weights, sw.fin_weights.p, sizeof(double) * W * b->p.k},
+                        {status, sw.fin_status.p, sizeof(int32_t) * W},
+                        {aux, sw.fin_aux.p, sizeof(double) * 4 * W * sw.S}});
 }
 
 // Prior sweep.  Per sub-range the Gram pass stores C and T of the sub-range and t, then posterior_prior_sweep_kernel solves

@@ -569,14 +569,35 @@ def _jorion_from_solves(x_t, x_one, t, T, N, gamma):
     return sol / gamma                                                   # ref:893
 
 
+def _finish_sweep(b, k, shift):
+    """Queues on the uploaded batch `b` the solve sweep `Batch.sweep_finish` reads - the shifts `shift` ([W x S x 2], None: one
+    unshifted solve), the right-hand sides [default, 1] - and leaves its solutions on the device.  Returns `b`."""
+    sweep = b.solve_sweep_tiled if k > _native.sweep_max_assets() else b.solve_sweep
+    sweep(shift=shift, rhs=np.ones((b.W, 1, k)), default_rhs=True, download=False)
+    return b
+
+
+# True: `_jorion_batch` takes ONE solve sweep (S = 1, R = 2) and finishes on the device (`Batch.sweep_finish`), so that the
+# weights exist there (`backtest_portfolio_device`).  Off: the sweep loses to the two launches at large W (DESIGN.md section 4e).
+JORION_DEVICE_FINISH = False
+
+
 def _jorion_batch(kw, gamma, k, N):
     """Two launches over the same resident batch: right-hand side t (default) and right-hand side 1.  (One solve sweep
-    with S = 1, R = 2 gives the same pair from one Gram pass, but measured slower at this shape: DESIGN.md section 4e.)"""
+    with S = 1, R = 2 gives the same pair from one Gram pass, but measured slower at this shape: DESIGN.md section 4e.)
+    With JORION_DEVICE_FINISH set: that one sweep, its solutions left on the device, and `Batch.sweep_finish(FINISH_JORION)`
+    - the Sherman-Morrison algebra of `_jorion_from_solves` in a kernel; [W x k] weights and statuses come down.  It loses to
+    the two launches on the device at large W (section 4e) and exists so that Jorion has a device-resident result."""
     dev = _native.default_device()
     W = len(kw["n_rows"])
     b = _native.Batch(dev, "jeffreys", k, N, kw["n_r"], 1.0, W, 0, flags=_native.FLAG_CENTER_BY_ROWS)
     try:
         b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m")})
+        if JORION_DEVICE_FINISH:
+            _finish_sweep(b, k, None).sweep_finish(_native.FINISH_JORION, np.asarray(kw["n_rows"], dtype=np.float64), gamma)
+            weights, status, _ = b.download_sweep_finish()
+            _raise_on_status(status)
+            return weights
         b.keep_rhs()                                       # the first run also leaves t = X'1 (ref:222)
         x_t, status, _ = b.run().download(want_aux=False)
         _raise_on_status(status)
@@ -649,6 +670,15 @@ _GREYSERMAN_SWEEP_BYTES = 1 << 30   # solutions of one sweep (dates x draws x 2 
 # (`Batch.solve_sweep_tiled`, S = draws, R = 2) instead of the replicated batch.  Off until the two have been timed
 # against each other on the device.
 GREYSERMAN_TILED_SWEEP = False
+# True: the sweeps of `_greyserman_batch` leave their solutions on the device and `Batch.sweep_finish` forms the rank-two
+# algebra and the mean over draws there - [W x k] weights come down instead of W x draws x 2 x k solutions.  Off until
+# tools/time_sweep_finish.py has been run on the device.
+GREYSERMAN_DEVICE_FINISH = False
+
+
+def _greyserman_kappa(n_rows):
+    """kappa_h = round(0.1 n) of ref:920, Python's rounding, as `_greyserman_from_solves` forms it."""
+    return np.array([round(0.1 * v) for v in np.asarray(n_rows, dtype=np.float64)], dtype=np.float64)
 
 
 def _greyserman_batch(kw, gamma, k, N, draws=None):
@@ -657,7 +687,9 @@ def _greyserman_batch(kw, gamma, k, N, draws=None):
     per date.  A sweep holds dates x draws x 2 x k solutions on the device and on the host, so the dates go through in
     groups of at most _GREYSERMAN_SWEEP_BYTES of solutions (1,342 dates at k = 50, 469 at k = 143, with 1000 draws); a
     date's result does not depend on the grouping.  Above `sweep_max_assets()`: GREYSERMAN_DRAWS repeated windows per
-    date, two launches per 32 dates - or, with GREYSERMAN_TILED_SWEEP set, the same loop with `Batch.solve_sweep_tiled`."""
+    date, two launches per 32 dates - or, with GREYSERMAN_TILED_SWEEP set, the same loop with `Batch.solve_sweep_tiled`.
+    With GREYSERMAN_DEVICE_FINISH set the solutions of a group stay on the device (they still exist there, so the grouping
+    stays), `Batch.sweep_finish` forms the group's weights and [dates x k] of them come down with the statuses."""
     n_rows = np.asarray(kw["n_rows"])
     W = len(n_rows)
     xi, eta = _greyserman_hyper(W, draws)
@@ -678,6 +710,12 @@ def _greyserman_batch(kw, gamma, k, N, draws=None):
         b = _native.Batch(dev, "jeffreys", k, N, kw["n_r"], 1.0, hi - lo, 0, flags=_native.FLAG_NO_CENTER)
         try:
             b.upload(**sub)
+            if GREYSERMAN_DEVICE_FINISH:
+                _finish_sweep(b, k, shift).sweep_finish(_native.FINISH_GREYSERMAN, n_rows[lo:hi].astype(np.float64), gamma,
+                                                        kappa=_greyserman_kappa(n_rows[lo:hi]), xi=xi[lo:hi], eta=eta[lo:hi])
+                out[lo:hi], status, _ = b.download_sweep_finish()
+                _raise_on_status(status)
+                continue
             u, status = (b.solve_sweep_tiled if tiled else b.solve_sweep)(shift=shift, rhs=np.ones((hi - lo, 1, k)),
                                                                           default_rhs=True)
             _raise_on_status(status.reshape(-1))
@@ -1923,6 +1961,84 @@ def backtest_portfolio(portfolio_spec, ts_start_date, ts_end_date, market_data):
     weights, labels, cols, caps = _weights_for_dates(rebalance_dates, portfolio_spec, market_data)
     tickers = batch.panels_for(market_data, portfolio_spec["rolling_window_frequency"]).tickers
     return _replay_backtest(trading_dates, rebalance_dates, weights, cols, caps, tickers, portfolio_spec, market_data)
+
+
+def backtest_portfolio_device(portfolio_spec, ts_start_date, ts_end_date, market_data, turnover_costs=None):
+    """`backtest_portfolio` for a `greyserman` or `jorion` spec with the weights never leaving the device: the pack of
+    `_weights_for_dates`, ONE batch, its solve sweep (the draws' ridge shifts, or Jorion's single solve; right-hand sides [t, 1]),
+    `Batch.sweep_finish` with the spec's risk aversion, then `Batch.replay(REPLAY_SRC_SWEEP_FINISH, ...)` reads the [W x k]
+    weights where the finish wrote them (no scale: the finish has divided by gamma).  Returns the dict of `_replay_backtest` -
+    equal bit for bit to `_weights_for_dates` with the device finish switched on followed by `replay_backtests_device` - or, with
+    `turnover_costs` (basis points), the metrics table of `summarise_backtests_device` for the spec at every one of these costs
+    (the replay runs at cost 0 and keeps its results on the device).  A date the finish flagged raises what `_raise_on_status`
+    raises; "Weights do not sum to 1." raises the reference's ValueError.
+    When the dates do not fit one sweep's solution budget (_GREYSERMAN_SWEEP_BYTES), or a Greyserman universe above
+    `sweep_max_assets()` without GREYSERMAN_TILED_SWEEP, it is `_weights_for_dates` + `replay_backtests_device` (or
+    `summarise_backtests_device`).  Opt-in: nothing calls it by default."""
+    strategy = portfolio_spec["weighting_strategy"]
+    if strategy not in ("greyserman", "jorion"):
+        raise ValueError(f"backtest_portfolio_device serves greyserman and jorion specs, not {strategy!r}")
+    grey = strategy == "greyserman"
+    trading_dates = [pd.Timestamp(ts) for ts in market_data["stock_prices_df"].index]
+    trading_dates = [ts for ts in trading_dates if ts_start_date <= ts <= ts_end_date]
+    rebalance_dates = rebalancing_schedule(trading_dates, portfolio_spec["rebalancing_frequency"])
+    tickers = batch.panels_for(market_data, portfolio_spec["rolling_window_frequency"]).tickers
+    k, N, gamma = portfolio_spec["size"], portfolio_spec["rolling_window"], portfolio_spec["risk_aversion"]
+    W = len(rebalance_dates)
+    B = GREYSERMAN_DRAWS if grey else 1
+    fits = W * B * 2 * k * 8 <= _GREYSERMAN_SWEEP_BYTES
+    if grey and k > _native.sweep_max_assets() and not GREYSERMAN_TILED_SWEEP:
+        fits = False
+    if not fits:
+        weights, _labels, cols, caps = _weights_for_dates(rebalance_dates, portfolio_spec, market_data)
+        items = [(weights, cols, caps, portfolio_spec)]
+        if turnover_costs is not None:
+            return summarise_backtests_device(trading_dates, rebalance_dates, items, market_data, turnover_costs, tickers=tickers)
+        return replay_backtests_device(trading_dates, rebalance_dates, items, market_data, tickers=tickers)[0]
+    kw, _labels, caps = batch.pack_windows(list(rebalance_dates), portfolio_spec, market_data,
+                                           members_of=_members_provider(market_data), return_caps=True)
+    cols = kw["col_idx"]
+    n_rows = np.asarray(kw["n_rows"])
+    if not grey:
+        kw.pop("start", None)                                 # (as `_weights_for_dates` hands a Jorion pack on)
+    flags = _native.FLAG_NO_CENTER if grey else _native.FLAG_CENTER_BY_ROWS
+    b = _native.Batch(_native.default_device(), "jeffreys", k, N, kw["n_r"], 1.0, W, 0, flags=flags)
+    try:
+        b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m")})
+        if grey:
+            xi, eta = _greyserman_hyper(W, None)
+            shift = np.zeros((W, B, 2))
+            shift[:, :, 0] = eta / 2
+            _finish_sweep(b, k, shift).sweep_finish(_native.FINISH_GREYSERMAN, n_rows.astype(np.float64), gamma,
+                                                    kappa=_greyserman_kappa(n_rows), xi=xi, eta=eta)
+        else:
+            _finish_sweep(b, k, None).sweep_finish(_native.FINISH_JORION, n_rows.astype(np.float64), gamma)
+        S, rf_daily, reb_day = _device_replay_inputs(trading_dates, rebalance_dates, market_data, tickers)
+        one = lambda v, dtype: np.array([v], dtype=dtype)     # noqa: E731
+        table = None
+        replayed = b.replay(
+            _native.REPLAY_SRC_SWEEP_FINISH, S, rf_daily, reb_day, len(tickers), one(k, np.int32),
+            one(gamma if gamma is not None else 1, np.float64),
+            one(portfolio_spec["turnover_cost"] if turnover_costs is None else 0.0, np.float64),
+            one(0, np.int64), one(k, np.int64), one(0, np.int64), one(1, np.int64), one(0, np.int64), one(k, np.int64),
+            np.ascontiguousarray(cols, dtype=np.int32).reshape(-1), np.ascontiguousarray(caps, dtype=np.float64).reshape(-1),
+            w_scale=None, download=turnover_costs is None)
+        if turnover_costs is not None:
+            table = _summary_table(b.dev, trading_dates, [portfolio_spec], market_data, turnover_costs)
+            if table is None:                                     # a replay status: which one decides what is raised, below
+                replayed = b.dev._replay_download(1, len(trading_dates), W)
+        returns, turnover, metrics, rstatus, _bad_day = replayed if replayed is not None else (None, None, None, 0, None)
+        if np.any(np.asarray(rstatus) == _native.REPLAY_BAD_WEIGHTS):
+            _raise_on_status(b.download_sweep_finish()[1])
+            raise RuntimeError("backtest_portfolio_device: the replay read a weight row the finish flagged with an unknown status")
+    finally:
+        b.close()
+    if np.any(np.asarray(rstatus) != 0):
+        logger.error("Weights do not sum to 1.")
+        raise ValueError("Weights do not sum to 1.")
+    if table is not None:
+        return table
+    return _device_replay_results(trading_dates, rebalance_dates, [portfolio_spec], returns, turnover, metrics)[0]
 
 
 def backtest_portfolios(portfolio_specs_dict, ts_start_date, ts_end_date, market_data):
