@@ -50,6 +50,7 @@ extern "C" {
                                  window; the reference returns finite garbage) */
 #define TP_STATUS_NONFINITE 2 /* NaN/Inf in the weights (ref:492-494 raises ValueError) */
 #define TP_STATUS_BAD_DENOM 3 /* n1 - w1'S1 w1 <= 0 (ref:573 has no guard, Appendix B-Q9) */
+#define TP_STATUS_NO_CONVERGENCE 4 /* tp_batch_spectral_greyserman: the eigensolver reached TP_SPECTRAL_MAX_SWEEPS sweeps */
 
 #define TP_AUX_STRIDE 8 /* doubles per window in `aux`: n0, n1, c, q0, q1, n1-q1, 0, 0 */
 
@@ -339,6 +340,56 @@ int tp_batch_sweep_finish(tp_batch_t b, int mode, double gamma, const double* n 
                           const double* kappa /* [W], Greyserman */, const double* hyper /* [W x S x 2] = (xi, eta), Greyserman */);
 /* Waits for the finish and copies out weights [W x k], status [W] and aux [W x S x 4]; each may be NULL. */
 int tp_batch_download_sweep_finish(tp_batch_t b, double* weights /* [W x k] */, int32_t* status /* [W] */, double* aux /* [W x S x 4] */);
+/* Spectral ridge sweep: the Greyserman weights (ref:928-931) of n_shift ridge draws per window from ONE eigendecomposition of
+ * the window's matrix instead of one factorisation per draw - and without the W x S x 2 x k solutions of a solve sweep.  For a
+ * Jeffreys batch created with gamma = 1, k <= tp_sweep_max_assets().  M_w and t_w are what the solve sweep's Gram pass stores
+ * (tp_batch_solve_sweep; the shared block sums are never used: M_w depends on the window's rows alone).  Every shift
+ * d_s = eta_s / 2 is a multiple of the identity, so with M_w = V diag(lambda) V':  (M_w + d_s I)^-1 b = V diag(1 / (lambda_j + d_s)) V'b.
+ * Definitions, all in double, ONE rounding per operation, in this order.
+ * 1. Eigendecomposition (one 256-thread workgroup per window): two-sided cyclic Jacobi on the lower triangle of M_w.  A sweep is
+ *    the m - 1 rounds of a round-robin tournament over m = 2 ceil(k / 2) players: in round r player m - 1 meets player r, and
+ *    for u = 1 .. m / 2 - 1 player (r + u) mod (m - 1) meets player (r - u) mod (m - 1); (p, q) = the smaller and the larger of
+ *    the two, a pair with q = k (k odd) sits out.  A pair is SKIPPED when |a_pq| <= 2^-53 max(sqrt(|a_pp a_qq|), a_max), a_max =
+ *    max_i |M_ii| of the input.  Otherwise theta = (a_qq - a_pp) / (2 a_pq), tt = sign(theta) / (|theta| + sqrt(theta theta + 1))
+ *    (sign(0) = +1), c = 1 / sqrt(tt tt + 1), s = tt c;  a_pp -= tt a_pq, a_qq += tt a_pq, a_pq = 0 exactly.  All rotations of a
+ *    round are formed from the matrix as the round found it and applied together: an element (x, y) with x in pair u, y in pair
+ *    v, u < v, takes pair v's rotation as a column ((e_p, e_q) <- (c e_p - s e_q, s e_p + c e_q)) and then pair u's as a row.
+ *    The columns of V (from the identity) and the two rows t^ = V't (from t_w) and o^ = V'1 (from the ones vector) take the
+ *    column rotation.  It ends after the first sweep without a rotation: lambda_j = a_jj, not sorted.  sweeps[w] counts that
+ *    last sweep too.  After TP_SPECTRAL_MAX_SWEEPS sweeps with rotations: TP_STATUS_NO_CONVERGENCE (never reported as NOT_PD).
+ *    A non-finite element of M_w or t_w: TP_STATUS_NONFINITE before the first sweep, no rotation.
+ * 2. Per shift s, with d = eta / 2 and N = k:  r_j = 1 / (lambda_j + d),  uo_j = r_j o^_j,  ut_j = r_j t^_j,
+ *      s1 = sum_j fl(uo_j o^_j),  s2 = sum_j fl(uo_j t^_j),  s3 = sum_j fl(ut_j t^_j): the lane-local order and the fixed 64-lane
+ *    tree of tp_batch_sweep_finish (lane l owns j = l, l + 64, l + 128).  Then beta, K11, K12, K22, det, c, cA, cB exactly as
+ *    TP_FINISH_GREYSERMAN defines them, and term_sj = cA uo_j - cB ut_j.  A shift with
+ *      min_j lambda_j + d <= (k 2^-52) (max_j lambda_j + d)
+ *    is TP_STATUS_NOT_PD (the tiled sweep's pivot rule, stated on eigenvalues) and contributes nothing.
+ * 3. w^_j = (sum over the groups of TP_FINISH_DRAWS_PER_WAVE consecutive shifts, in ascending order, of (the group's terms added
+ *    in ascending s starting from 0)) / S;  weights[w][i] = sum_j fl(V_ij w^_j), j ascending from 0.
+ * The grouping and every order depend on (k, S) only: a window's weights are the same bit for bit whatever W, its position and
+ * the sub-ranges, and from run to run.
+ * status[w]: the eigensolver's status when it is not TP_STATUS_OK; else the first shift s = 0, 1, ... that is TP_STATUS_NOT_PD -
+ * in both cases the weights row is NaN -; else TP_STATUS_NONFINITE when a weight of the row is not finite (beta = 0, det = 0 end
+ * here); else TP_STATUS_OK.  aux[w][s] = (s1, s2, s3, det), NaN for a flagged shift.
+ * TP_ERR_INVALID, all checked before anything is waited for, uploaded or queued (a refused call leaves the last result in
+ * place): a batch that was not uploaded; not a Jeffreys batch; a batch gamma other than 1; n_shift < 1; a NULL n, kappa or hyper
+ * with W > 0; a non-finite n, kappa, xi or eta; eta < 0; a gamma that is 0 or not finite.  TP_ERR_UNSUPPORTED:
+ * k > tp_sweep_max_assets().  TP_ERR_HIP: an allocation failed - with keep_vectors != 0 the call keeps V of all W windows
+ * (W k k doubles, allocated in the call; the message names the byte count); otherwise V lives per sub-range only.
+ * The call waits on entry like tp_batch_solve_sweep (same gather hand-over), copies n, kappa and hyper (HOST pointers, not kept)
+ * and queues, per sub-range of windows ("sweep_chunk_windows"), the Gram pass and three launches inside one timed span without
+ * waiting for them: kernel_ms, one step of tp_region_steps; tp_last_launch keeps describing tp_batch_run.  It has buffers of its
+ * own, kept until tp_batch_destroy: runs, solve sweeps and an earlier tp_batch_sweep_finish keep their results. */
+#define TP_SPECTRAL_MAX_SWEEPS 32
+int tp_batch_spectral_greyserman(tp_batch_t b, int32_t n_shift, double gamma, const double* n /* [W] */,
+                                 const double* kappa /* [W] */, const double* hyper /* [W x S x 2] = (xi, eta) */,
+                                 int32_t keep_vectors);
+/* Waits for the spectral sweep and copies out weights [W x k], status [W], aux [W x S x 4] = (s1, s2, s3, det), the eigenvalues
+ * lambda [W x k], the sweep counts [W] and the eigenvectors V [W x k x k] (column-major per window: V_ij at [w][j][i]); each may
+ * be NULL.  V needs keep_vectors != 0 in the call (else TP_ERR_INVALID), as does a call before any spectral sweep. */
+int tp_batch_download_spectral(tp_batch_t b, double* weights /* [W x k] */, int32_t* status /* [W] */,
+                               double* aux /* [W x S x 4] */, double* lambda /* [W x k] */, int32_t* sweeps /* [W] */,
+                               double* V /* [W x k x k], needs keep_vectors */);
 /* Prior sweep: many conjugate priors (n0, w0) per window from ONE pair of Grams - a grid of conjugate specs over the same
  * rebalancing dates (VIX / EPU x vw / ew x mcm_scaling, ref:247-267, 361-380) without a replica of every window per spec.
  * With C = sum (y - ybar)(y - ybar)' the centred intraday scatter of window w, T = X'X, t = X'1, m the window's own
@@ -743,6 +794,7 @@ int tp_replay_run(tp_handle_t h, int64_t D, int32_t ld, const double* S /* [D x 
 #define TP_REPLAY_SRC_WINDOW_SWEEP 3  /* tp_batch_window_sweep[_tiled]: [W x P x L x k],              [W x P x L]           */
 #define TP_REPLAY_SRC_GRID_SWEEP   4  /* tp_batch_grid_sweep[_tiled]:   [W x P x L x S x k],          [W x P x L x S]       */
 #define TP_REPLAY_SRC_SWEEP_FINISH 5  /* tp_batch_sweep_finish:         weights [W x k],              status [W]            */
+#define TP_REPLAY_SRC_SPECTRAL     6  /* tp_batch_spectral_greyserman:  weights [W x k],              status [W]            */
 #define TP_REPLAY_BAD_WEIGHTS 2       /* status[p]: a weight row was read whose source status was not TP_STATUS_OK */
 int tp_replay_run_batch(tp_batch_t b, int source,
                         int64_t D, int32_t ld, const double* S, const double* rf_daily,

@@ -28,6 +28,7 @@ TP_ERR_RCCL = -5
 STRATEGY_CONJUGATE = 0
 STRATEGY_JEFFREYS = 1
 STATUS_OK, STATUS_NOT_PD, STATUS_NONFINITE, STATUS_BAD_DENOM = 0, 1, 2, 3
+STATUS_NO_CONVERGENCE = 4          # TP_STATUS_NO_CONVERGENCE: `spectral_greyserman`'s eigensolver reached SPECTRAL_MAX_SWEEPS
 AUX_STRIDE = 8
 FLAG_CENTER_BY_ROWS = 1
 FLAG_NO_CENTER = 2
@@ -40,6 +41,8 @@ REPLAY_BAD_WEIGHTS = 2
 REPLAY_METRICS = 5
 REPLAY_SRC_RUN, REPLAY_SRC_PRIOR_SWEEP, REPLAY_SRC_SIZE_SWEEP, REPLAY_SRC_WINDOW_SWEEP, REPLAY_SRC_GRID_SWEEP = 0, 1, 2, 3, 4
 REPLAY_SRC_SWEEP_FINISH = 5
+REPLAY_SRC_SPECTRAL = 6
+SPECTRAL_MAX_SWEEPS = 32           # TP_SPECTRAL_MAX_SWEEPS
 FINISH_GREYSERMAN, FINISH_JORION = 0, 1
 FINISH_DRAWS_PER_WAVE = 16        # TP_FINISH_DRAWS_PER_WAVE: consecutive shifts of one window per wavefront of `sweep_finish`
 SUMMARY_STATS = 32
@@ -58,6 +61,7 @@ EXPORTS = [
     "tp_batch_download_rhs", "tp_batch_keep_posterior", "tp_batch_download_posterior", "tp_batch_run", "tp_batch_download", "tp_batch_download_S1", "tp_batch_download_matrix",
     "tp_batch_solve_sweep", "tp_batch_solve_sweep_tiled", "tp_batch_download_sweep", "tp_batch_download_sweep_rhs",
     "tp_batch_sweep_finish", "tp_batch_download_sweep_finish",
+    "tp_batch_spectral_greyserman", "tp_batch_download_spectral",
     "tp_batch_prior_sweep", "tp_batch_prior_sweep_tiled", "tp_batch_download_prior_sweep",
     "tp_batch_size_sweep", "tp_batch_size_sweep_tiled", "tp_batch_download_size_sweep",
     "tp_batch_window_sweep", "tp_batch_window_sweep_tiled", "tp_batch_download_window_sweep",
@@ -137,6 +141,9 @@ def _load():
     lib.tp_batch_download_sweep_rhs.argtypes = [c_void_p, POINTER(c_double)]
     lib.tp_batch_sweep_finish.argtypes = [c_void_p, c_int, c_double, POINTER(c_double), POINTER(c_double), POINTER(c_double)]
     lib.tp_batch_download_sweep_finish.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
+    lib.tp_batch_spectral_greyserman.argtypes = [c_void_p, c_int32, c_double, POINTER(c_double), POINTER(c_double), POINTER(c_double), c_int32]
+    lib.tp_batch_download_spectral.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double), POINTER(c_double),
+                                               POINTER(c_int32), POINTER(c_double)]
     lib.tp_batch_prior_sweep.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     lib.tp_batch_prior_sweep_tiled.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     lib.tp_batch_download_prior_sweep.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]
@@ -889,6 +896,53 @@ class Batch:
                                                            _ptr(status if status.size else None, c_int32),
                                                            _ptr(aux if aux is not None and aux.size else None, c_double)))
         return weights, status, aux
+
+    def spectral_greyserman(self, n, gamma, kappa, xi, eta, keep_vectors=False):
+        """`tp_batch_spectral_greyserman`: the Greyserman weights of the draws `xi`, `eta` [W x S] (`n`, `kappa` [W]) from ONE
+        eigendecomposition per window - the ridge shifts eta / 2 share the eigenvectors of the window's matrix - instead of S
+        factorisations; no solve sweep before it, no W x S x 2 x k solutions.  A Jeffreys batch created with gamma = 1,
+        k <= `sweep_max_assets()`; `gamma` is the call's own.  `keep_vectors`: the eigenvectors of every window are kept for
+        `download_spectral(want_vectors=True)`.  Nothing comes down: `download_spectral` fetches the results,
+        `replay(REPLAY_SRC_SPECTRAL, ...)` reads the weights where they lie.  Shapes are checked here; the library refuses the
+        rest (TangencyError) before it queues anything."""
+        W = self.W
+        nn = np.ascontiguousarray(n, dtype=np.float64)
+        ka = np.ascontiguousarray(kappa, dtype=np.float64)
+        x_, e_ = np.asarray(xi, dtype=np.float64), np.asarray(eta, dtype=np.float64)
+        if nn.shape != (W,):
+            raise ValueError(f"n: expected shape ({W},), got {tuple(nn.shape)}")
+        if ka.shape != (W,):
+            raise ValueError(f"kappa: expected shape ({W},), got {tuple(ka.shape)}")
+        if x_.ndim != 2 or x_.shape[0] != W or e_.shape != x_.shape:
+            raise ValueError(f"xi, eta: expected one shape ({W}, S), got {tuple(x_.shape)} and {tuple(e_.shape)}")
+        S = x_.shape[1]
+        hy = np.ascontiguousarray(np.stack([x_, e_], axis=2))
+        self.dev._check(lib.tp_batch_spectral_greyserman(self._b, S, float(gamma), _ptr(nn if nn.size else None, c_double),
+                                                         _ptr(ka if ka.size else None, c_double),
+                                                         _ptr(hy if hy.size else None, c_double), 1 if keep_vectors else 0))
+        self._spectral_S = S
+        return self
+
+    def download_spectral(self, want_aux=False, want_spectrum=False, want_vectors=False):
+        """(weights [W x k], status [W], aux [W x S x 4] or None) of the last `spectral_greyserman`: aux[w, s] = (s1, s2, s3,
+        det K).  `want_spectrum`: (lambda [W x k] - not sorted -, sweeps [W]) are appended; `want_vectors` (the call needs
+        `keep_vectors=True`): V [W x k x k] with V[w, :, j] the eigenvector of lambda[w, j]."""
+        W, k = self.W, self.k
+        weights = np.empty((W, k), dtype=np.float64)
+        status = np.empty(W, dtype=np.int32)
+        aux = np.empty((W, getattr(self, "_spectral_S", 1), 4), dtype=np.float64) if want_aux else None
+        lam = np.empty((W, k), dtype=np.float64) if want_spectrum else None
+        sweeps = np.empty(W, dtype=np.int32) if want_spectrum else None
+        V = np.empty((W, k, k), dtype=np.float64) if want_vectors else None
+        opt = lambda a, t: _ptr(a if a is not None and a.size else None, t)   # noqa: E731
+        self.dev._check(lib.tp_batch_download_spectral(self._b, opt(weights, c_double), opt(status, c_int32), opt(aux, c_double),
+                                                       opt(lam, c_double), opt(sweeps, c_int32), opt(V, c_double)))
+        out = (weights, status, aux)
+        if want_spectrum:
+            out += (lam, sweeps)
+        if want_vectors:
+            out += (V.transpose(0, 2, 1),)                   # (the library's layout is column-major per window)
+        return out
 
     def download_sweep_rhs(self) -> np.ndarray:
         """[W x k] default right-hand sides (t = X'1, or c S0 w0 + t) the Gram pass of the last `solve_sweep` /

@@ -25,5 +25,26 @@ struct tp_finish_args_t {
     int W, S, k, mode;
 };
 
+// The scalar algebra of TP_FINISH_GREYSERMAN, shared with the spectral sweep (posterior_spectral.hip): one rounding per
+// operation, in the order include/tangency_posterior.h documents.  c = tp_finish_greyserman_scale(gamma, N, n).
+struct tp_finish_coeffs_t { double det, cA, cB; };
+
+__device__ __forceinline__ double tp_finish_greyserman_scale(double gamma, double N, double n) {
+    return ((1 / gamma) * ((N + n) + 1)) * (1 - 1 / n);
+}
+
+__device__ __forceinline__ tp_finish_coeffs_t tp_finish_greyserman_coeffs(double s1, double s2, double s3, double n, double kappa,
+                                                                          double xi, double eta, double c) {
+    const double beta = eta / 2 + kappa * (xi * xi);
+    const double K11 = 1 / beta + s1;
+    const double K12 = s2 - (kappa * xi) / beta;
+    const double K22 = (s3 - n) - (kappa * eta) / (2 * beta);
+    tp_finish_coeffs_t r;
+    r.det = K11 * K22 - K12 * K12;
+    r.cA = c * (K12 / r.det);
+    r.cB = c * (K11 / r.det);
+    return r;
+}
+
 // the partial sums of every (window, group), then every window's weights and status: two launches on `st`
 hipError_t tp_finish_launch(const tp_finish_args_t& a, hipStream_t st);

@@ -59,7 +59,7 @@ __global__ __launch_bounds__(64) void finish_group_kernel(const tp_finish_args_t
     double c = 0.0, kappa = 0.0, kJ = 0.0;
     if (MODE == TP_FINISH_KMODE_GREYSERMAN) {
         kappa = a.kappa[w];
-        c = ((1 / a.gamma) * ((N + n) + 1)) * (1 - 1 / n);
+        c = tp_finish_greyserman_scale(a.gamma, N, n);
     } else {
         kJ = (((n - N) - 2) * (n - 1)) / n;
     }
@@ -92,15 +92,10 @@ __global__ __launch_bounds__(64) void finish_group_kernel(const tp_finish_args_t
             wave_sums(v);
             const double s1 = v[0], s2 = v[1], s3 = v[2];
             if (MODE == TP_FINISH_KMODE_GREYSERMAN) {
-                const double beta = eta / 2 + kappa * (xi * xi);
-                const double K11 = 1 / beta + s1;
-                const double K12 = s2 - (kappa * xi) / beta;
-                const double K22 = (s3 - n) - (kappa * eta) / (2 * beta);
-                const double det = K11 * K22 - K12 * K12;
-                const double cA = c * (K12 / det), cB = c * (K11 / det);
+                const tp_finish_coeffs_t f = tp_finish_greyserman_coeffs(s1, s2, s3, n, kappa, xi, eta, c);
 #pragma unroll
-                for (int i = 0; i < NS; ++i) acc[i] += cA * uo[i] - cB * ut[i];
-                if (lane == 0) { aux[0] = s1; aux[1] = s2; aux[2] = s3; aux[3] = det; }
+                for (int i = 0; i < NS; ++i) acc[i] += f.cA * uo[i] - f.cB * ut[i];
+                if (lane == 0) { aux[0] = s1; aux[1] = s2; aux[2] = s3; aux[3] = f.det; }
             } else {
                 const double T = n;
                 const double sbb = kJ * s1, sab = (kJ * s2) / T, saa = (kJ * s3) / (T * T);

@@ -23,6 +23,7 @@
 #include "backtest_replay.h"
 #include "replay_summary.h"
 #include "sweep_finish.h"
+#include "posterior_spectral.h"
 
 #define TP_REGION_MAX_STEPS 512
 
@@ -110,6 +111,21 @@ struct SolveSweepWs {
     bool finish_stale = false;      // there was a finish, and a later sweep replaced the solutions it read
 };
 
+// Spectral ridge sweep (`sp`, tp_batch_spectral_greyserman, posterior_spectral.hip): buffers of its own throughout - the outputs
+// of the run kernel that serves as its Gram pass included -, so that it leaves runs, solve sweeps and a sweep finish alone.
+struct SpectralWs {
+    DevBuf gw, gs, ga;              // outputs of the run kernel that serves as the Gram pass
+    DevBuf t, post;                 // every window's t [W x k]; the matrices [chunk x k x k] of ONE sub-range at a time
+    DevBuf V;                       // eigenvectors: [chunk x k x k] of one sub-range, or [W x k x k] (keep_vectors)
+    DevBuf lambda, that, ohat;      // [W x k] each
+    DevBuf sweeps, jstatus;         // [W] Jacobi sweeps and the eigensolver's own status
+    DevBuf n, kappa, hyper;         // the uploaded scalars n [W], kappa [W] and (xi, eta) [W x S x 2]
+    DevBuf part, gstatus;           // the groups' partial sums [W x NG x k] and statuses [W x NG]
+    DevBuf weights, status, aux;    // the results: [W x k], [W], [W x S x 4]
+    int S = 0;                      // draws of the last call (0: none yet)
+    bool kept_vectors = false;      // the last call kept V of every window
+};
+
 // Prior sweeps (`ps`) and the size sweep (`zs`): one type, two instances - a size sweep must not disturb what
 // tp_batch_download_prior_sweep returns, and the reverse.  C / T hold the matrices of ONE sub-range at a time: the intraday
 // scatters and daily Grams (a Jeffreys size sweep: M in T, no C).
@@ -153,6 +169,7 @@ struct tp_batch_s {
     DevBuf post;                                              // kept posterior matrices [post_count x k x k] (tp_batch_keep_posterior)
     int64_t post_w0 = 0, post_count = 0;
     SolveSweepWs sw;                                          // tp_batch_solve_sweep / _solve_sweep_tiled
+    SpectralWs sp;                                            // tp_batch_spectral_greyserman
     PriorSweepWs ps, zs;                                      // tp_batch_prior_sweep / _prior_sweep_tiled; tp_batch_size_sweep / _size_sweep_tiled
     WindowSweepWs wn;                                         // tp_batch_window_sweep / _window_sweep_tiled
     GridSweepWs gr;                                           // tp_batch_grid_sweep / _grid_sweep_tiled

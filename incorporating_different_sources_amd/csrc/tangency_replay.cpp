@@ -323,6 +323,10 @@ int tp_replay_run_batch(tp_batch_t b, int source, int64_t D, int32_t ld, const d
             per_window = b->sw.finished ? 1 : 0; producer = "tp_batch_sweep_finish";
             feed.src_weights = (const double*)b->sw.fin_weights.p; feed.src_status = (const int32_t*)b->sw.fin_status.p;
             break;
+        case TP_REPLAY_SRC_SPECTRAL:
+            per_window = b->sp.S < 1 ? 0 : 1; producer = "tp_batch_spectral_greyserman";
+            feed.src_weights = (const double*)b->sp.weights.p; feed.src_status = (const int32_t*)b->sp.status.p;
+            break;
         default:
             return fail(h, TP_ERR_INVALID, "%s: unknown source %d", name, source);
     }

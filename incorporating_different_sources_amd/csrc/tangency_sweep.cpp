@@ -1,6 +1,6 @@
 // tangency_sweep.cpp - the sweeps of the C-ABI of libtangency.so (include/tangency_posterior.h): many solves per window
 // from one Gram pass - tp_batch_solve_sweep, _prior_sweep, _size_sweep, _window_sweep, _grid_sweep, the five tiled forms above
-// tp_sweep_max_assets(), and their downloads.  Every sweep is: checks, a drain of the handle's stream, its workspace (SolveSweepWs / PriorSweepWs,
+// tp_sweep_max_assets(), the sweep finish and the spectral ridge sweep (tp_batch_spectral_greyserman), and their downloads.  Every sweep is: checks, a drain of the handle's stream, its workspace (SolveSweepWs / PriorSweepWs,
 // tangency_host.h), then per sub-range of windows a Gram stage and a solve stage inside one timed span.
 #include <cmath>
 #include <cstring>
@@ -684,6 +684,125 @@ int tp_batch_download_sweep_finish(tp_batch_t b, double* weights, int32_t* statu
     return download(h, {{weights, sw.fin_weights.p, sizeof(double) * W * b->p.k},
                         {status, sw.fin_status.p, sizeof(int32_t) * W},
                         {aux, sw.fin_aux.p, sizeof(double) * 4 * W * sw.S}});
+}
+
+// Spectral ridge sweep (posterior_spectral.hip).  Per sub-range the batch's own run kernel stores the matrices of the sub-range
+// and every window's t into the spectral workspace (the solve sweep's Gram pass, on buffers of its own), then one
+// eigendecomposition per window, the partial sums of every (window, group of draws) in the eigenbasis and the weights.
+// Every check comes before the drain: a refused call leaves the last result in place.
+int tp_batch_spectral_greyserman(tp_batch_t b, int32_t n_shift, double gamma, const double* n, const double* kappa,
+                                 const double* hyper, int32_t keep_vectors) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    SpectralWs& sp = b->sp;
+    const char* name = "tp_batch_spectral_greyserman";
+    const int k = b->p.k;
+    const int64_t W = b->W;
+    if (b->p.strategy != TP_STRATEGY_JEFFREYS) return fail(h, TP_ERR_INVALID, "%s applies to the Jeffreys strategy only", name);
+    if (!b->uploaded) return fail(h, TP_ERR_INVALID, "%s before tp_batch_upload", name);
+    if (b->p.gamma != 1.0)
+        return fail(h, TP_ERR_INVALID, "%s: the batch's gamma is %g: a batch created with gamma = 1 is expected (the call takes "
+                    "gamma itself)", name, b->p.gamma);
+    if (n_shift < 1) return fail(h, TP_ERR_INVALID, "%s: n_shift=%d < 1", name, n_shift);
+    if (!std::isfinite(gamma) || gamma == 0.0) return fail(h, TP_ERR_INVALID, "%s: gamma=%g must be finite and not 0", name, gamma);
+    const int S = n_shift;
+    const int64_t NG = (S + TP_FINISH_DRAWS_PER_WAVE - 1) / TP_FINISH_DRAWS_PER_WAVE;
+    if (W > 0) {
+        if (!n || !kappa || !hyper) return fail(h, TP_ERR_INVALID, "%s: %s is NULL", name, !n ? "n" : !kappa ? "kappa" : "hyper");
+        for (int64_t w = 0; w < W; ++w) {
+            if (!std::isfinite(n[w])) return fail(h, TP_ERR_INVALID, "%s: n[%lld] is not finite", name, (long long)w);
+            if (!std::isfinite(kappa[w])) return fail(h, TP_ERR_INVALID, "%s: kappa[%lld] is not finite", name, (long long)w);
+        }
+        for (int64_t e = 0; e < W * S; ++e) {
+            if (!std::isfinite(hyper[2 * e]) || !std::isfinite(hyper[2 * e + 1]))
+                return fail(h, TP_ERR_INVALID, "%s: (xi, eta) of window %lld, shift %lld is not finite", name, (long long)(e / S), (long long)(e % S));
+            if (hyper[2 * e + 1] < 0.0)
+                return fail(h, TP_ERR_INVALID, "%s: eta of window %lld, shift %lld is negative", name, (long long)(e / S), (long long)(e % S));
+        }
+    }
+    int rc = check_sweep_k(h, false, name, "", k);
+    if (rc != TP_OK) return rc;
+    if (W > 0x7fffffffLL / NG) return fail(h, TP_ERR_UNSUPPORTED, "%s: W=%lld windows x %lld groups of shifts exceed 2^31", name, (long long)W, (long long)NG);
+    rc = drain_for_sweep(b);
+    if (rc != TP_OK) return rc;
+    sp.S = 0;
+    if (W == 0) { sp.S = S; sp.kept_vectors = keep_vectors != 0; return TP_OK; }
+    const size_t mat_bytes = sizeof(double) * (size_t)k * k;
+    const size_t Wz = (size_t)W;
+    // one sub-range keeps two k x k matrices per window (M and, unless every V is kept, V): the sweeps' workspace rule
+    const int64_t chunk = sweep_chunk(h, (keep_vectors ? 1 : 2) * mat_bytes, NG, W, true);
+    const std::string what = std::string(name) + ": ";
+    rc = ensure(h, sp.post, mat_bytes * (size_t)chunk, (what + "matrices of one sub-range").c_str());
+    if (rc == TP_OK) {
+        const size_t vbytes = mat_bytes * (keep_vectors ? Wz : (size_t)chunk);
+        const std::string vwhat = what + (keep_vectors ? "eigenvectors of all windows, " + std::to_string(vbytes) + " bytes (keep_vectors)"
+                                                       : std::string("eigenvectors of one sub-range"));
+        rc = ensure(h, sp.V, vbytes, vwhat.c_str());
+    }
+    if (rc == TP_OK) rc = ensure(h, sp.gw, sizeof(double) * Wz * k, (what + "weights of the Gram pass").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.gs, sizeof(int32_t) * Wz, (what + "statuses of the Gram pass").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.ga, sizeof(double) * Wz * TP_AUX_STRIDE, (what + "aux of the Gram pass").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.t, sizeof(double) * Wz * k, (what + "right-hand sides t").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.lambda, sizeof(double) * Wz * k, (what + "eigenvalues").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.that, sizeof(double) * Wz * k, (what + "rotated t").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.ohat, sizeof(double) * Wz * k, (what + "rotated ones").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.sweeps, sizeof(int32_t) * Wz, (what + "sweep counts").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.jstatus, sizeof(int32_t) * Wz, (what + "eigensolver statuses").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.n, sizeof(double) * Wz, (what + "n").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.kappa, sizeof(double) * Wz, (what + "kappa").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.hyper, sizeof(double) * 2 * Wz * S, (what + "(xi, eta)").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.part, sizeof(double) * Wz * (size_t)NG * k, (what + "partial sums").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.gstatus, sizeof(int32_t) * Wz * (size_t)NG, (what + "group statuses").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.weights, sizeof(double) * Wz * k, (what + "weights").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.status, sizeof(int32_t) * Wz, (what + "statuses").c_str());
+    if (rc == TP_OK) rc = ensure(h, sp.aux, sizeof(double) * 4 * Wz * S, (what + "aux").c_str());
+    if (rc != TP_OK) return rc;
+    // the caller's arrays: copied here, no host pointer is kept
+    HIP_TRY(h, hipMemcpyAsync(sp.n.p, n, sizeof(double) * Wz, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(sp.kappa.p, kappa, sizeof(double) * Wz, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(sp.hyper.p, hyper, sizeof(double) * 2 * Wz * S, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // the copies are done when the call returns, pinned host memory or not
+    tp_kargs_t a = neutral_kargs(b);                   // (no shared block sums: M_w comes from the window's rows alone)
+    a.weights = (double*)sp.gw.p; a.status = (int*)sp.gs.p; a.aux = (double*)sp.ga.p;
+    a.out_rhs = (double*)sp.t.p;
+    a.out_post = (double*)sp.post.p;
+    tp_spectral_args_t sa;
+    memset(&sa, 0, sizeof sa);
+    sa.post = (const double*)sp.post.p; sa.t = (const double*)sp.t.p;
+    sa.V = (double*)sp.V.p;
+    sa.lambda = (double*)sp.lambda.p; sa.that = (double*)sp.that.p; sa.ohat = (double*)sp.ohat.p;
+    sa.sweeps = (int*)sp.sweeps.p; sa.jstatus = (int*)sp.jstatus.p;
+    sa.n = (const double*)sp.n.p; sa.kappa = (const double*)sp.kappa.p; sa.hyper = (const double*)sp.hyper.p;
+    sa.part = (double*)sp.part.p; sa.gstatus = (int*)sp.gstatus.p;
+    sa.weights = (double*)sp.weights.p; sa.status = (int*)sp.status.p; sa.aux = (double*)sp.aux.p;
+    sa.gamma = gamma;
+    sa.S = S; sa.k = k;
+    return run_sweep(b, chunk, [&](int64_t w0, int64_t nw) {
+        a.w_first = w0; a.w_count = nw;
+        a.post_w0 = w0; a.post_count = nw;
+        const int rcl = launch(b, a, nw, false);
+        if (rcl != TP_OK) return rcl;
+        sa.w_first = w0; sa.w_count = nw; sa.v_first = keep_vectors ? w0 : 0;
+        return launched(h, tp_spectral_launch(sa, h->stream), "spectral sweep kernel");
+    }, [&] { sp.S = S; sp.kept_vectors = keep_vectors != 0; });
+}
+
+int tp_batch_download_spectral(tp_batch_t b, double* weights, int32_t* status, double* aux, double* lambda, int32_t* sweeps,
+                               double* V) {
+    if (!b) return TP_ERR_INVALID;
+    tp_handle_t h = b->h;
+    const SpectralWs& sp = b->sp;
+    if (sp.S < 1) return fail(h, TP_ERR_INVALID, "tp_batch_download_spectral: no tp_batch_spectral_greyserman before it");
+    if (V && !sp.kept_vectors)
+        return fail(h, TP_ERR_INVALID, "tp_batch_download_spectral: V asked for, but the last tp_batch_spectral_greyserman had keep_vectors = 0");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t W = (size_t)b->W, k = (size_t)b->p.k;
+    return download(h, {{weights, sp.weights.p, sizeof(double) * W * k},
+                        {status, sp.status.p, sizeof(int32_t) * W},
+                        {aux, sp.aux.p, sizeof(double) * 4 * W * sp.S},
+                        {lambda, sp.lambda.p, sizeof(double) * W * k},
+                        {sweeps, sp.sweeps.p, sizeof(int32_t) * W},
+                        {V, sp.V.p, sizeof(double) * W * k * k}});
 }
 
 // Prior sweep.  Per sub-range the Gram pass stores C and T of the sub-range and t, then posterior_prior_sweep_kernel solves

@@ -665,6 +665,31 @@ def _greyserman_from_solves(u_t, u_one, t, n, xi, eta, k, gamma):
     return (scale[:, :, None] * x).mean(axis=1)
 
 
+def _greyserman_from_spectrum(lam, V, t, n, xi, eta, k, gamma):
+    """`_greyserman_from_solves` from ONE eigendecomposition T = V diag(lam) V' per window instead of the solves: every ridge
+    matrix B_b = T + (eta_b/2) I has the eigenvectors of T, so with t^ = V't, o^ = V'1 and r_bj = 1 / (lam_j + eta_b/2)
+        u_one = V (r_b o^),  u_t = V (r_b t^),  1'u_one = sum_j r_bj o^_j^2,  1'u_t = sum_j r_bj o^_j t^_j,  t'u_t = sum_j r_bj t^_j^2,
+    the rank-two algebra is that of `_greyserman_from_solves`, and the mean over the draws is taken in the eigenbasis: one
+    product with V per window.  The numpy mirror of `Batch.spectral_greyserman` (same algebra, numpy's orders of summation).
+    Shapes: lam [W x k]; V [W x k x k] with V[w, :, j] the eigenvector of lam[w, j]; t [W x k]; n [W]; xi, eta [W x B]."""
+    lam, V, t = np.asarray(lam, dtype=np.float64), np.asarray(V, dtype=np.float64), np.asarray(t, dtype=np.float64)
+    xi, eta = np.asarray(xi, dtype=np.float64), np.asarray(eta, dtype=np.float64)
+    n = np.asarray(n, dtype=np.float64)[:, None]
+    kappa = np.array([round(0.1 * v) for v in n[:, 0]], dtype=np.float64)[:, None]       # ref:920
+    that = np.einsum("wij,wi->wj", V, t)[:, None, :]
+    ohat = V.sum(axis=1)[:, None, :]
+    r = 1 / (lam[:, None, :] + (eta / 2)[:, :, None])
+    uo, ut = r * ohat, r * that
+    beta = eta / 2 + kappa * xi ** 2
+    K11 = 1 / beta + (uo * ohat).sum(axis=2)
+    K12 = (uo * that).sum(axis=2) - kappa * xi / beta
+    K22 = (ut * that).sum(axis=2) - n - kappa * eta / (2 * beta)
+    det = K11 * K22 - K12 ** 2
+    x = (K12 / det)[:, :, None] * uo - (K11 / det)[:, :, None] * ut                      # V' D_h^-1 a_h
+    scale = 1 / gamma * (k + n + 1) * (1 - 1 / n)                                        # ref:931 with nu_h = k
+    return np.einsum("wij,wj->wi", V, (scale[:, :, None] * x).mean(axis=1))
+
+
 _GREYSERMAN_SWEEP_BYTES = 1 << 30   # solutions of one sweep (dates x draws x 2 x k doubles, on the device and on the host)
 # Sizes above `_native.sweep_max_assets()`: True takes one window per date and one tiled solve sweep
 # (`Batch.solve_sweep_tiled`, S = draws, R = 2) instead of the replicated batch.  Off until the two have been timed
@@ -674,6 +699,17 @@ GREYSERMAN_TILED_SWEEP = False
 # algebra and the mean over draws there - [W x k] weights come down instead of W x draws x 2 x k solutions.  Off until
 # tools/time_sweep_finish.py has been run on the device.
 GREYSERMAN_DEVICE_FINISH = False
+# True: up to `sweep_max_assets()` `_greyserman_batch` takes ONE batch over all dates and `Batch.spectral_greyserman` - one
+# eigendecomposition per date instead of one factorisation per draw, no solutions buffer and so no grouping of the dates.
+# Off whatever tools/time_spectral.py measures: opt-in.
+GREYSERMAN_SPECTRAL = False
+
+
+def _raise_on_spectral_status(status):
+    """`_raise_on_status`, and the eigensolver's own refusal."""
+    _raise_on_status(status)
+    if (np.asarray(status) == _native.STATUS_NO_CONVERGENCE).any():
+        raise RuntimeError("greyserman: the eigensolver of the spectral sweep did not converge for a date")
 
 
 def _greyserman_kappa(n_rows):
@@ -689,7 +725,8 @@ def _greyserman_batch(kw, gamma, k, N, draws=None):
     date's result does not depend on the grouping.  Above `sweep_max_assets()`: GREYSERMAN_DRAWS repeated windows per
     date, two launches per 32 dates - or, with GREYSERMAN_TILED_SWEEP set, the same loop with `Batch.solve_sweep_tiled`.
     With GREYSERMAN_DEVICE_FINISH set the solutions of a group stay on the device (they still exist there, so the grouping
-    stays), `Batch.sweep_finish` forms the group's weights and [dates x k] of them come down with the statuses."""
+    stays), `Batch.sweep_finish` forms the group's weights and [dates x k] of them come down with the statuses.
+    With GREYSERMAN_SPECTRAL set, up to `sweep_max_assets()`: one batch over all dates and `Batch.spectral_greyserman`."""
     n_rows = np.asarray(kw["n_rows"])
     W = len(n_rows)
     xi, eta = _greyserman_hyper(W, draws)
@@ -697,6 +734,16 @@ def _greyserman_batch(kw, gamma, k, N, draws=None):
     if tiled and not GREYSERMAN_TILED_SWEEP:
         return _greyserman_batch_repeated(kw, gamma, k, N, xi, eta)
     dev = _native.default_device()
+    if GREYSERMAN_SPECTRAL and not tiled:                 # no solutions on the device: every date in one batch
+        b = _native.Batch(dev, "jeffreys", k, N, kw["n_r"], 1.0, W, 0, flags=_native.FLAG_NO_CENTER)
+        try:
+            b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m")})
+            b.spectral_greyserman(n_rows.astype(np.float64), gamma, _greyserman_kappa(n_rows), xi, eta)
+            weights, status, _ = b.download_spectral()
+        finally:
+            b.close()
+        _raise_on_spectral_status(status)
+        return weights
     B = eta.shape[1]
     per_window = ("start", "row_idx", "n_rows", "col_idx", "rf_adj")
     group = max(1, _GREYSERMAN_SWEEP_BYTES // (B * 2 * k * 8))
@@ -1967,7 +2014,9 @@ def backtest_portfolio_device(portfolio_spec, ts_start_date, ts_end_date, market
     """`backtest_portfolio` for a `greyserman` or `jorion` spec with the weights never leaving the device: the pack of
     `_weights_for_dates`, ONE batch, its solve sweep (the draws' ridge shifts, or Jorion's single solve; right-hand sides [t, 1]),
     `Batch.sweep_finish` with the spec's risk aversion, then `Batch.replay(REPLAY_SRC_SWEEP_FINISH, ...)` reads the [W x k]
-    weights where the finish wrote them (no scale: the finish has divided by gamma).  Returns the dict of `_replay_backtest` -
+    weights where the finish wrote them (no scale: the finish has divided by gamma).  A `greyserman` spec with
+    GREYSERMAN_SPECTRAL set, up to `sweep_max_assets()`: `Batch.spectral_greyserman` in place of the sweep and the finish, read
+    through REPLAY_SRC_SPECTRAL, whatever the number of dates.  Returns the dict of `_replay_backtest` -
     equal bit for bit to `_weights_for_dates` with the device finish switched on followed by `replay_backtests_device` - or, with
     `turnover_costs` (basis points), the metrics table of `summarise_backtests_device` for the spec at every one of these costs
     (the replay runs at cost 0 and keeps its results on the device).  A date the finish flagged raises what `_raise_on_status`
@@ -1989,6 +2038,10 @@ def backtest_portfolio_device(portfolio_spec, ts_start_date, ts_end_date, market
     fits = W * B * 2 * k * 8 <= _GREYSERMAN_SWEEP_BYTES
     if grey and k > _native.sweep_max_assets() and not GREYSERMAN_TILED_SWEEP:
         fits = False
+    spectral = grey and GREYSERMAN_SPECTRAL and k <= _native.sweep_max_assets()
+    if spectral:
+        fits = True                                           # (the spectral sweep keeps no solutions: no budget to fit)
+    source = _native.REPLAY_SRC_SPECTRAL if spectral else _native.REPLAY_SRC_SWEEP_FINISH
     if not fits:
         weights, _labels, cols, caps = _weights_for_dates(rebalance_dates, portfolio_spec, market_data)
         items = [(weights, cols, caps, portfolio_spec)]
@@ -2005,7 +2058,10 @@ def backtest_portfolio_device(portfolio_spec, ts_start_date, ts_end_date, market
     b = _native.Batch(_native.default_device(), "jeffreys", k, N, kw["n_r"], 1.0, W, 0, flags=flags)
     try:
         b.upload(**{key: val for key, val in kw.items() if key not in ("n_r", "m")})
-        if grey:
+        if spectral:
+            xi, eta = _greyserman_hyper(W, None)
+            b.spectral_greyserman(n_rows.astype(np.float64), gamma, _greyserman_kappa(n_rows), xi, eta)
+        elif grey:
             xi, eta = _greyserman_hyper(W, None)
             shift = np.zeros((W, B, 2))
             shift[:, :, 0] = eta / 2
@@ -2017,7 +2073,7 @@ def backtest_portfolio_device(portfolio_spec, ts_start_date, ts_end_date, market
         one = lambda v, dtype: np.array([v], dtype=dtype)     # noqa: E731
         table = None
         replayed = b.replay(
-            _native.REPLAY_SRC_SWEEP_FINISH, S, rf_daily, reb_day, len(tickers), one(k, np.int32),
+            source, S, rf_daily, reb_day, len(tickers), one(k, np.int32),
             one(gamma if gamma is not None else 1, np.float64),
             one(portfolio_spec["turnover_cost"] if turnover_costs is None else 0.0, np.float64),
             one(0, np.int64), one(k, np.int64), one(0, np.int64), one(1, np.int64), one(0, np.int64), one(k, np.int64),
@@ -2029,7 +2085,10 @@ def backtest_portfolio_device(portfolio_spec, ts_start_date, ts_end_date, market
                 replayed = b.dev._replay_download(1, len(trading_dates), W)
         returns, turnover, metrics, rstatus, _bad_day = replayed if replayed is not None else (None, None, None, 0, None)
         if np.any(np.asarray(rstatus) == _native.REPLAY_BAD_WEIGHTS):
-            _raise_on_status(b.download_sweep_finish()[1])
+            if spectral:
+                _raise_on_spectral_status(b.download_spectral()[1])
+            else:
+                _raise_on_status(b.download_sweep_finish()[1])
             raise RuntimeError("backtest_portfolio_device: the replay read a weight row the finish flagged with an unknown status")
     finally:
         b.close()
